@@ -24,7 +24,10 @@ the 12 GB decides up to 10-15 % of the loop's speed on some boxes (tools/placeme
 could gain by choosing among `--placement-tries` candidate pools is measured AFTER the headline and reported separately as
 `config.best_placement` (never `value`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+
+`--dump-outputs DIR` (one GPU) writes what the last timed step returned -- the merged map, as a fixed seeded sample of its values --
+to DIR/merged_sample.npy, so that two builds run with the same arguments can be compared output for output.
 
 N > 1 runs one rank per GPU over RCCL; started without WORLD_SIZE in the environment, `python bench.py --gpus N` launches itself
 under torch.distributed.run (127.0.0.1, a free port).  Before anything is timed every rank checks the rows it owns against the
@@ -74,7 +77,7 @@ def parse():
     ap.add_argument("--unplanned", action="store_true", help="A/B: TileMerger without crops= (lazily built norm_mask + separate merge pass)")
     ap.add_argument("--no-defer", action="store_true", help="A/B: planned merger without deferred band merging (accumulators in HBM)")
     ap.add_argument("--ramp-ms", type=float, default=400.0, help="minimum untimed GPU work before the warm-up; the ramp then goes on (bounded by "
-                    "--ramp-max-ms) until three consecutive groups of 10 steps agree within 1.5 %: a fresh box needs a moment to leave its "
+                    "--ramp-max-ms) until three consecutive groups of 10 steps agree within 1.5 %%: a fresh box needs a moment to leave its "
                     "low-power state and to fault the 12 GB of model outputs in")
     ap.add_argument("--ramp-max-ms", type=float, default=4000.0)
     ap.add_argument("--repeats", type=int, default=5, help="the K timed steps are run this many times (each run bracketed by barrier + "
@@ -83,7 +86,42 @@ def parse():
     ap.add_argument("--no-variants", action="store_true", help="skip the secondary timings (no-defer / unplanned / literal drop-in sequence)")
     ap.add_argument("--defer-rows", type=int, default=0, help="rows of the image merged per deferred launch (0: the library default, 1024)")
     ap.add_argument("--diag", action="store_true", help="print per-step / per-call timing diagnostics to stderr")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned in its "
+                    "last timed step as DIR/<name>.npy (float32 / float64; an output of more than 4 Mi values as the values at a fixed, "
+                    "seeded set of positions, DIR/<name>_sample.npy): the inputs are seeded, so two builds run with the same arguments "
+                    "can be compared output for output (single GPU only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs covers the single-GPU path (--gpus 1)")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: values kept of a larger output (16 MiB in float32)
+DUMP_LIMIT = 64 << 20          # bytes written in all
+DUMP_SEED = 20240611
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: every tensor of ``outputs`` ({name: device tensor}) as ``dirname/<name>.npy`` in float32 (float64 stays float64).
+    A tensor of more than DUMP_SAMPLE values is written as its values at sorted positions of the flattened tensor drawn from a
+    fixed seed (duplicates dropped), ``<name>_sample.npy``: the same positions in every run for the same shape."""
+    arrays = {}
+    for name, t in outputs.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat, name = flat[torch.from_numpy(pos).to(flat.device)], name + "_sample"
+        else:
+            flat = flat.reshape(t.shape)
+        arrays[name] = flat.to(torch.float64 if flat.dtype == torch.float64 else torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT} byte limit"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"[bench] --dump-outputs: {', '.join(f'{n}.npy {a.shape}' for n, a in arrays.items())} -> {dirname}", file=sys.stderr, flush=True)
 
 
 def self_launch(args):
@@ -543,11 +581,13 @@ def main_cfg5(args):
     for _ in range(max(args.warmup, 20)):
         step()
     runs = []
-    for _ in range(max(1, args.repeats)):
+    n_runs = max(1, args.repeats)
+    for i in range(n_runs):
         sync()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             step()
+        out = step()
         sync()
         wall = time.perf_counter() - t0
         if use_dist:
@@ -555,6 +595,9 @@ def main_cfg5(args):
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             wall = float(tmax.item())
         runs.append(wall)
+        if args.dump_outputs and i == n_runs - 1:     # what the last timed step returned
+            dump_outputs(args.dump_outputs, {"merged": out})
+        del out
     elapsed = sorted(runs)[len(runs) // 2]
     ms_per_step = elapsed / args.steps * 1e3
     my_bytes = sum(y.numel() for y in ys) * 4 + C * (r1 - r0) * n * 4
@@ -655,6 +698,8 @@ def main():
 
     # ---- this rank's share of the tiles, and their (synthetic) model outputs resident in HBM -------------------
     sharded = use_dist
+    if args.dump_outputs and sharded:
+        sys.exit("bench.py: --dump-outputs covers the single-device merge, not the sharded one")
     planned = deferred = False
     fallback = None   # set when the requested merger could not be used and a slower one was (reported in the JSON line)
     partition = os.environ.get("PTB_BENCH_PARTITION", "tiles")   # "tiles": 45 / 46 tiles per rank at N = 8; "rows": whole tile rows
@@ -880,14 +925,16 @@ def main():
     host_ms = (time.perf_counter() - th0) * 1e3
     sync()
 
-    def timed_run(fn, k):
-        """EXACTLY k steps bracketed by barrier + synchronize on both sides; (wall seconds [max over ranks], HIP-event ms)."""
+    def timed_run(fn, k, keep=None):
+        """EXACTLY k steps bracketed by barrier + synchronize on both sides; (wall seconds [max over ranks], HIP-event ms).
+        ``keep``: a list that receives what the last step returned (--dump-outputs)."""
         sync()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         e0.record()
-        for _ in range(k):
+        for _ in range(k - 1):
             fn()
+        out = fn()
         e1.record()
         sync()
         wall = time.perf_counter() - t0
@@ -895,9 +942,15 @@ def main():
             tmax = torch.tensor([wall], device=dev, dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             wall = float(tmax.item())
+        if keep is not None:
+            keep.append(out)
         return wall, e0.elapsed_time(e1)
 
-    runs = [timed_run(step, args.steps) for _ in range(max(1, args.repeats))]
+    n_runs = max(1, args.repeats)
+    last_out = []     # --dump-outputs: what the last timed step of the last run returned (earlier runs keep nothing alive)
+    runs = [timed_run(step, args.steps, keep=last_out if args.dump_outputs and i == n_runs - 1 else None) for i in range(n_runs)]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"merged": last_out.pop()})
     # ---- N = 1: the timed path's OUTPUT, checked right after the timed runs against the plain HIP merger (accumulate now, divide in
     # merge(): the reference's data flow, tiles.py:321-346, pinned to the oracle and to the reference's goldens by the -m gpu suite) on
     # the same model outputs: every value of the merged map, not a digest.  Planned and deferred mergers are bit-identical to it.

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz by running the UNMODIFIED reference (/root/reference) on seeded inputs.
+"""Generate tests/golden/*.npz by running the UNMODIFIED reference on seeded inputs.
 
-Test infrastructure only.  Run in the build container (the reference does not exist on the GPU box):
+Test infrastructure only.  Run where a checkout of the reference exists (the GPU box has none), named by PTB_REFERENCE:
 
-    python oracle/make_golden.py
+    PTB_REFERENCE=<reference checkout> python oracle/make_golden.py
 
 The reference is imported behind oracle/ref_shim (a cv2 / torchvision stand-in: the reference's
 utils/__init__ imports both, neither wheel is installed here).  No reference source is copied;
@@ -20,7 +20,9 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-REF = os.environ.get("PTB_REFERENCE", "/root/reference")
+REF = os.environ.get("PTB_REFERENCE")
+if not REF or not os.path.isdir(os.path.join(REF, "pytorch_toolbelt")):
+    raise SystemExit("set PTB_REFERENCE to a checkout of the unmodified reference (the directory holding pytorch_toolbelt/)")
 sys.path.insert(0, os.path.join(HERE, "ref_shim"))
 sys.path.insert(0, REF)
 warnings.filterwarnings("ignore")

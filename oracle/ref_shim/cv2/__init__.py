@@ -1,5 +1,5 @@
 """TEST-HARNESS ONLY: minimal stand-in for OpenCV so the *unmodified* reference
-(/root/reference) can be imported in a container that has no cv2 wheel.
+checkout can be imported in a container that has no cv2 wheel.
 
 Only the zero-padding used by pytorch_toolbelt/inference/tiles.py:161,182,220
 (cv2.copyMakeBorder with BORDER_CONSTANT) carries arithmetic; it is np.pad.

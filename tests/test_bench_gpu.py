@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -38,6 +39,27 @@ def test_single_gpu_line():
     assert 5000.0 < d["value"] < 16000.0
     par = d["config"]["parity"]       # the timed path's output against the plain merger, every value of the merged map
     assert par["bit_identical"] is True and par["max_abs_diff_vs_plain_merger"] == 0.0 and par["values_checked"] == 4 * 5120 * 5120
+
+
+def test_dump_outputs_is_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: what the timed path returned in its last timed step -- the merged 4 x 5120 x 5120 map, as the values at a
+    fixed, seeded sample of its positions -- in float32, 64 MB at most.  The inputs are seeded, so another run (here with another
+    --steps) writes the same values; the run's parity field ties the timed output to the plain merger's."""
+    dumps = []
+    for steps in (1, 3):
+        out = tmp_path / f"steps{steps}"
+        run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--repeats", "1",
+                              "--no-secondary", "--no-cpu-baseline", "--no-variants", "--placement-tries", "1", "--ramp-max-ms", "300",
+                              "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert run.returncode == 0, run.stderr[-3000:]
+        d = _line(run.stdout)
+        assert d["steps"] == steps and d["config"]["parity"]["bit_identical"] is True
+        assert sorted(f.name for f in out.iterdir()) == ["merged_sample.npy"]
+        a = np.load(out / "merged_sample.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and 4_000_000 < a.size <= 1 << 22 and a.nbytes <= 64 << 20
+        assert np.isfinite(a).all() and float(np.abs(a).max()) > 0
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_two_ranks_on_one_gpu_take_the_sharded_pipelined_path():

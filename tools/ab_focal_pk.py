@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_toolbelt_amd import losses as L, _native as N
 dev = torch.device("cuda:0")
 pads = [torch.empty(int(os.environ.get("PAD_GB", "0")) << 30, dtype=torch.uint8, device=dev)] if os.environ.get("PAD_GB") else []

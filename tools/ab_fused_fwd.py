@@ -1,8 +1,9 @@
 """A/B of the fused focal + Dice + Jaccard forward at BASELINE cfg4 ([32,16,512,512]): ptb_set_tunable key 8 (prefetch of the next
 pixel group) x key 4 (workgroups per launch).  Prints ms per criterion call (kernel + epilogue + finalize) and the loss value."""
+import os
 import sys
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_toolbelt_amd import losses as L, _native as N
 
 dev = torch.device("cuda:0")

@@ -1,7 +1,8 @@
+import os
 import sys
 
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_toolbelt_amd import losses as L, _native as N
 dev = torch.device("cuda:0")
 x = torch.randn((32, 16, 512, 512), device=dev)

@@ -1,8 +1,9 @@
 """A/B of the softmax focal (CrossEntropyFocalLoss) backward at BASELINE cfg4: tunable 7 = 0 (two transcendental passes), 2, 4
 (per-class terms kept in registers, 2 / 4 pixels per lane).  Prints forward+backward ms and a checksum of the gradient."""
+import os
 import sys
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_toolbelt_amd import losses as L, _native as N
 
 dev = torch.device("cuda:0")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Build container only: time the UNMODIFIED reference (/root/reference behind oracle/ref_shim) on the headline loop next to
+"""Build container only: time the UNMODIFIED reference (the checkout named by PTB_REFERENCE, behind oracle/ref_shim) on the headline loop next to
 oracle/torch_chain.py (what bench.py's cpu_baseline leg times on the GPU box, where the reference does not exist).
-    python tools/cpu_baseline_crosscheck.py            -> one line per implementation, same host, same threads"""
+    PTB_REFERENCE=<reference checkout> python tools/cpu_baseline_crosscheck.py            -> one line per implementation, same host, same threads"""
 import os
 import sys
 import time
@@ -9,7 +9,9 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle", "ref_shim"))
-sys.path.insert(0, os.environ.get("PTB_REFERENCE", "/root/reference"))
+if not os.environ.get("PTB_REFERENCE"):
+    raise SystemExit("set PTB_REFERENCE to a checkout of the unmodified reference")
+sys.path.insert(0, os.environ["PTB_REFERENCE"])
 import torch  # noqa: E402
 
 from oracle import torch_chain as TC  # noqa: E402

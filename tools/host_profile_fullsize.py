@@ -1,5 +1,5 @@
-import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_toolbelt_amd.inference import tta
 from pytorch_toolbelt_amd.inference.tiles import ImageSlicer, TileMerger
 dev = torch.device("cuda:0")

@@ -4,7 +4,7 @@
 #   microbenchmarks.   usage: bash tools/profile_round.sh r02
 set -u
 TAG=${1:-r03}
-R=/root/repo
+R="$(cd "$(dirname "$0")/.." && pwd)"
 O=$R/gpurun_out/profiles
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

@@ -1,8 +1,8 @@
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from torch import nn
-sys.path.insert(0, "/root/repo/tools")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from e2e_bench import DummyUNet
 dev = torch.device("cuda:0")
 for width in (32, 16, 8):
