@@ -59,6 +59,10 @@ typedef void* ptb_stream_t; /* hipStream_t */
 #define PTB_F32 0
 #define PTB_F16 1
 #define PTB_BF16 2
+/* further element types of the volumes ptb_volume_split reads (every one widens to fp32 exactly) */
+#define PTB_U8 3
+#define PTB_I16 4
+#define PTB_U16 5
 /* or-ed into the `in_dtype` of ptb_deaug_accumulate_t / ptb_accumulate_planned(2) / ptb_merge_band / ptb_band_plan_submit(_rank): the
  * reduced value is rounded to the (fp16 / bf16) source type -- round to nearest even, NaN -> quiet NaN, like torch's `.to(dtype)` --
  * before it is multiplied by the window.  That is what the reference's two calls compute on half-precision model outputs
@@ -315,6 +319,30 @@ int ptb_ensemble_reduce(const float* const* inputs, int T, int reduction, int ac
  * added); norm[roi] += weight.  Out-of-range rois -> PTB_EBOUNDS.  merge = ptb_merge_div with HW = D*H*W. */
 int ptb_volume_accumulate(float* volume, float* norm, const float* weight, const float* tiles, const int64_t* zs, const int64_t* ys,
                           const int64_t* xs, int B, int C, int d, int h, int w, int D, int H, int W, ptb_stream_t stream);
+
+/* ---- Loop edges of the 3-D tiles on the device (VolumeSlicer.split / VolumeMerger.merge + crop; no single counterpart) ----
+ * ptb_volume_split == VolumeSlicer.split (inference/tiles_3d.py: np.pad with constant `value`, a copy per tile) -> channels first
+ * ([d, h, w, C] -> [C, d, h, w]; a [D, H, W] volume is C = 1) -> np.stack -> .float() [-> * scale[c] + bias[c], product rounded,
+ * then the sum] [-> .to(out_dtype), round to nearest even]: volume DEVICE [D, H, W, C] contiguous of in_dtype (PTB_F32, PTB_F16,
+ * PTB_BF16, PTB_U8, PTB_I16, PTB_U16); zs/ys/xs HOST int64[B] = tile origins in VOLUME coordinates (the slicer's bbox_crops:
+ * voxels outside the volume read pad_value, which the caller has already cast to in_dtype); scale/bias HOST float[C] or both
+ * NULL; out DEVICE [B, C, d, h, w] of out_dtype (PTB_F32, PTB_F16, PTB_BF16).  C <= 16 (PTB_EUNSUPPORTED otherwise). */
+int ptb_volume_split(const void* volume, int in_dtype, int D, int H, int W, int C, const int64_t* zs, const int64_t* ys,
+                     const int64_t* xs, int B, int d, int h, int w, const float* scale, const float* bias, float pad_value,
+                     int out_dtype, void* out, ptb_stream_t stream);
+/* output kinds of ptb_volume_merge_crop (0..3 are the `kind` codes of ptb_merge_crop) */
+#define PTB_CROP_F32 0
+#define PTB_CROP_U8 1         /* truncating cast, as ptb_merge_crop */
+#define PTB_CROP_ARGMAX_U8 2  /* argmax over channels: first maximum, NaN counts as maximum; layout ignored */
+#define PTB_CROP_ARGMAX_I64 3
+#define PTB_CROP_F16 4        /* round to nearest even of the fp32 quotient */
+#define PTB_CROP_BF16 5
+/* ptb_volume_merge_crop == VolumeMerger.merge (volume / norm_mask, ptb_merge_div: correctly rounded, no eps clamp)
+ * -> [(slice(None), z0:z0+OD, y0:y0+OH, x0:x0+OW)] (VolumeSlicer.orignal_image_roi) -> layout -> .to(dtype) | .argmax(0):
+ * volume DEVICE fp32 [C, D, H, W], norm DEVICE fp32 [D, H, W]; layout 0: out [C, OD, OH, OW], 1: out [OD, OH, OW, C];
+ * kind = PTB_CROP_*; argmax kinds write [OD, OH, OW].  A window outside the accumulator -> PTB_EBOUNDS. */
+int ptb_volume_merge_crop(const float* volume, const float* norm, int C, int D, int H, int W, int z0, int y0, int x0, int OD, int OH,
+                          int OW, int layout, int kind, void* out, ptb_stream_t stream);
 
 /* ---- {fliplr,flipud,flips,d2,d4}_image_deaugment (inference/tta.py:287-316,344-365,442-467,503-524) -------------
  * in [V*B, C, H, W] (chunk-major: rows [k*B,(k+1)*B) are view k), views HOST int[V] = inverse transform of each chunk.

@@ -21,6 +21,8 @@ IDENT, TRANSPOSE, FLIPUD, ROT90_CW, FLIPLR, ROT90_CCW, ROT180, ANTITRANSPOSE = r
 RED_SUM, RED_MEAN, RED_GMEAN, RED_HMEAN, RED_HARMONIC1P, RED_LOGODD, RED_LOG1P = range(7)
 F32, F16, BF16 = range(3)   # PTB_F32 / PTB_F16 / PTB_BF16: element type of the model outputs a `_t` entry point reads
 DTYPE_CODES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
+U8, I16, U16 = 3, 4, 5      # PTB_U8 / PTB_I16 / PTB_U16: further volume element types of ptb_volume_split
+VOLUME_DTYPE_CODES = {torch.uint8: U8, torch.int16: I16, torch.uint16: U16, torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32}
 ROUND_SRC = 0x100           # PTB_ROUND_SRC, or-ed into a dtype code: round the reduced value to the (half) source type before blending
 
 EFRESH = -5
@@ -130,6 +132,9 @@ SIGNATURES = {
     "ptb_volume_accumulate": (_c_int, [_vp, _vp, _vp, _vp, _i64p, _i64p, _i64p] + [_c_int] * 8 + [_vp]),
     "ptb_ensemble_reduce": (_c_int, [_vpp, _c_int, _c_int, _c_int, _c_f, _c_int, _c_int, _c_i64, _vp, _vp]),
     "ptb_merge_crop": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "ptb_volume_split": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _i64p, _i64p, _i64p, _c_int, _c_int, _c_int, _c_int, _fp, _fp, _c_f,
+                                  _c_int, _vp, _vp]),
+    "ptb_volume_merge_crop": (_c_int, [_vp, _vp] + [_c_int] * 12 + [_vp, _vp]),
 }
 
 _lib = None

@@ -102,8 +102,87 @@ class VolumeSlicer:
     def crop_to_orignal_size(self, volume):
         return volume[self.orignal_image_roi]
 
+    # ------------------------------------------------------------------ device-side split
+    def split_device(self, volume: torch.Tensor, indices=None, scale=None, bias=None, value=0, dtype=torch.float32) -> torch.Tensor:
+        """Model input for the tiles ``indices`` straight from a volume that already lives in HBM, as one HIP launch per 64 tiles.
+
+        Equals ``np.stack([np.moveaxis(t, -1, 0) if t.ndim == 4 else t[None] for t in self.split(volume, value)])[indices]`` as a
+        float32 tensor (optionally ``* scale[c] + bias[c]``), converted to ``dtype`` -- with no padded copy of the volume, no
+        per-tile copies and no upload.  ``volume``: CUDA ``[D, H, W]`` or ``[D, H, W, C]`` (C <= 16) of uint8, int16, uint16,
+        float16, bfloat16 or float32; ``indices``: None (all tiles), a slice, or a sequence of tile indices; ``scale`` / ``bias``:
+        per-channel sequences (both or neither); ``value``: constant border, cast to the volume's dtype first (as ``np.pad``
+        does); ``dtype``: torch.float32, torch.float16 or torch.bfloat16 (round to nearest even).  Returns ``[n, C, d, h, w]``.
+        """
+        N.require_device(volume, "VolumeSlicer.split_device")
+        code = N.VOLUME_DTYPE_CODES.get(volume.dtype)
+        if code is None:
+            raise NotImplementedError(f"split_device takes a uint8, int16, uint16, float16, bfloat16 or float32 volume, got {volume.dtype}")
+        out_code = N.DTYPE_CODES.get(dtype)
+        if out_code is None:
+            raise NotImplementedError(f"split_device writes float32, float16 or bfloat16, not {dtype}")
+        if volume.dim() not in (3, 4) or tuple(volume.shape[:3]) != tuple(int(s) for s in self.volume_shape):
+            raise ValueError(f"Volume shape {tuple(volume.shape)} is not equal to the expected {tuple(int(s) for s in self.volume_shape)}")
+        channels = 1 if volume.dim() == 3 else int(volume.shape[3])
+        if channels < 1 or channels > 16:
+            raise NotImplementedError(f"split_device takes at most 16 channels, got {channels}")
+        if (scale is None) != (bias is None):
+            raise ValueError("scale and bias go together")
+        if indices is None:
+            boxes = self.bbox_crops
+        elif isinstance(indices, slice):
+            boxes = self.bbox_crops[indices]
+        else:
+            boxes = [self.bbox_crops[int(i)] for i in np.asarray(indices, dtype=np.int64).reshape(-1)]
+        d, h, w = (int(s) for s in self.tile_size)
+        n = len(boxes)
+        out = torch.empty((n, channels, d, h, w), device=volume.device, dtype=dtype)
+        if n == 0:
+            return out
+        starts = np.ascontiguousarray(np.array([[s.start for s in box] for box in boxes], dtype=np.int64).T)
+        # np.pad assigns the border value into an array of the volume's dtype (the host copy of a bfloat16 volume is float32)
+        host_dtype = np.float32 if volume.dtype == torch.bfloat16 else torch.empty(0, dtype=volume.dtype).numpy().dtype
+        pad = float(np.asarray(value).astype(host_dtype))
+        fa = None
+        if scale is not None:
+            sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float32).reshape(-1), (channels,)))
+            bi = np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.float32).reshape(-1), (channels,)))
+            fa = (sc.ctypes.data_as(N._fp), bi.ctypes.data_as(N._fp))
+        volume = volume.contiguous()
+        D, H, W = (int(s) for s in self.volume_shape)
+        lib = N.load()
+        with N.on_device(volume.device):
+            rc = lib.ptb_volume_split(volume.data_ptr(), code, D, H, W, channels, starts[0].ctypes.data_as(N._i64p),
+                                      starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), n, d, h, w,
+                                      fa[0] if fa else None, fa[1] if fa else None, pad, out_code, out.data_ptr(),
+                                      N.stream_ptr(volume.device))
+        N.bump()
+        N.check(rc, "VolumeSlicer.split_device")
+        return out
+
     def _mean(self, volume_size):
         return np.ones(volume_size, dtype=np.float32)
+
+
+_CROP_KINDS = {torch.float32: 0, torch.uint8: 1, torch.float16: 4, torch.bfloat16: 5}     # PTB_CROP_*
+_ARGMAX_KINDS = {torch.uint8: (2, torch.uint8), torch.int64: (3, torch.int64), torch.float32: (3, torch.int64)}
+
+
+def _crop_window(crop, shape, layout):
+    """``crop`` (a VolumeSlicer: its ``orignal_image_roi``, or ``(z0, y0, x0, D, H, W)``) -> the window, checked against the
+    accumulator's ``(D', H', W')``."""
+    if isinstance(crop, VolumeSlicer):
+        roi = crop.orignal_image_roi
+        window = tuple(int(s.start) for s in roi) + tuple(int(s.stop - s.start) for s in roi)
+    else:
+        window = tuple(int(v) for v in crop)
+        if len(window) != 6:
+            raise ValueError("a crop window is (z0, y0, x0, depth, height, width)")
+    if layout not in ("cdhw", "dhwc"):
+        raise ValueError(f"layout must be 'cdhw' or 'dhwc', got {layout!r}")
+    for a in range(3):
+        if window[a] < 0 or window[3 + a] < 0 or window[a] + window[3 + a] > shape[a]:
+            raise ValueError("crop window is outside the accumulator")
+    return window
 
 
 def _roi_starts(rois, tile):
@@ -201,6 +280,43 @@ class VolumeMerger:
         N.check(rc, "VolumeMerger.merge")
         return out if self.dtype == torch.float32 else out.to(self.dtype)
 
+    def merge_crop(self, crop, layout: str = "cdhw", dtype=torch.float32, argmax: bool = False) -> torch.Tensor:
+        """``merge()`` + crop + layout + cast in one pass that reads and writes only the cropped window.
+
+        Equals ``merger.merge()[(slice(None),) + window]`` (moved to ``layout``, ``.to(dtype)``) or, with ``argmax=True``, its
+        ``.argmax(0)`` -- without the second padded ``[C, D', H', W']`` volume.  ``crop``: a ``VolumeSlicer`` (its
+        ``orignal_image_roi``) or ``(z0, y0, x0, D, H, W)``; ``layout``: "cdhw" | "dhwc"; ``dtype``: torch.float32 | float16 |
+        bfloat16 (round to nearest even) | uint8 (truncating cast, like ``TileMerger.merge_crop``); with ``argmax=True``: torch.uint8
+        or torch.int64 (the default float32 gives int64) class indices ``[D, H, W]``.
+        """
+        shape = tuple(int(s) for s in self.volume.shape[1:])
+        z0, y0, x0, od, oh, ow = _crop_window(crop, shape, layout)
+        if argmax:
+            if dtype not in _ARGMAX_KINDS:
+                raise NotImplementedError(f"merge_crop: argmax dtype {dtype} is not supported")
+            kind, out_dtype = _ARGMAX_KINDS[dtype]
+            out_shape = (od, oh, ow)
+        else:
+            if dtype not in _CROP_KINDS:
+                raise NotImplementedError(f"merge_crop: dtype {dtype} is not supported")
+            kind, out_dtype = _CROP_KINDS[dtype], dtype
+            out_shape = (self.channels, od, oh, ow) if layout == "cdhw" else (od, oh, ow, self.channels)
+        for t in (self.volume, self.norm_mask):
+            N.require_device(t, "VolumeMerger.merge_crop")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("VolumeMerger accumulators must be contiguous float32 tensors")
+        out = torch.empty(out_shape, device=self.volume.device, dtype=out_dtype)
+        if out.numel() == 0:
+            return out
+        lib = N.load()
+        dev = self.volume.device
+        with N.on_device(dev):
+            rc = lib.ptb_volume_merge_crop(self.volume.data_ptr(), self.norm_mask.data_ptr(), self.channels, *shape, z0, y0, x0, od, oh, ow,
+                                           1 if layout == "dhwc" else 0, kind, out.data_ptr(), N.stream_ptr(dev))
+        N.bump()
+        N.check(rc, "VolumeMerger.merge_crop")
+        return out
+
 
 class HostBackedVolumeMerger(VolumeMerger):
     """``VolumeMerger(device="cpu")`` (and ``dtype=torch.float64`` on any device): the reference's torch-op merger
@@ -239,3 +355,16 @@ class HostBackedVolumeMerger(VolumeMerger):
 
     def merge(self) -> torch.Tensor:
         return self.volume / self.norm_mask
+
+    def merge_crop(self, crop, layout: str = "cdhw", dtype=torch.float32, argmax: bool = False) -> torch.Tensor:
+        """``VolumeMerger.merge_crop`` with torch ops: the cropped window of ``merge()``, moved and converted."""
+        z0, y0, x0, od, oh, ow = _crop_window(crop, tuple(int(s) for s in self.volume.shape[1:]), layout)
+        window = self.merge()[:, z0:z0 + od, y0:y0 + oh, x0:x0 + ow]
+        if argmax:
+            if dtype not in _ARGMAX_KINDS:
+                raise NotImplementedError(f"merge_crop: argmax dtype {dtype} is not supported")
+            return window.argmax(dim=0).to(_ARGMAX_KINDS[dtype][1])
+        if dtype not in _CROP_KINDS:
+            raise NotImplementedError(f"merge_crop: dtype {dtype} is not supported")
+        out = window.permute(1, 2, 3, 0) if layout == "dhwc" else window
+        return out.to(dtype).contiguous()
