@@ -298,6 +298,22 @@ int ptb_rect_add(float* dst, const float* src, int C, int rows, int cols, int64_
 int ptb_split_tiles_u8(const uint8_t* image, int IH, int IW, int IC, const int64_t* xs, const int64_t* ys, int B, int th, int tw,
                        int V, const int* views, const float* scale, const float* bias, int pad_value, float* out,
                        ptb_stream_t stream);
+/* border codes of ptb_split_tiles: OpenCV's cv2.BORDER_* numbers (TRANSPARENT = 5 and ISOLATED = 16 -> PTB_EUNSUPPORTED) */
+#define PTB_BORDER_CONSTANT 0     /* iiiiii|abcdefgh|iiiiiii, i = pad_value */
+#define PTB_BORDER_REPLICATE 1    /* aaaaaa|abcdefgh|hhhhhhh */
+#define PTB_BORDER_REFLECT 2      /* fedcba|abcdefgh|hgfedcb */
+#define PTB_BORDER_WRAP 3         /* cdefgh|abcdefgh|abcdefg */
+#define PTB_BORDER_REFLECT_101 4  /* gfedcb|abcdefgh|gfedcba */
+/* ptb_split_tiles == ptb_split_tiles_u8 for further element types and borders, with the batch written as out_dtype:
+ * ImageSlicer.split(image, border, value) (the border pads the WHOLE image, margins of any width; rows and columns map
+ * independently, as np.pad does) -> HWC->CHW -> .float() [-> * scale[c] + bias[c]] [-> *_image_augment] [-> .to(out_dtype),
+ * round to nearest even].  image DEVICE [IH, IW, IC] contiguous of in_dtype (PTB_U8, PTB_U16, PTB_I16; float sources ->
+ * PTB_EUNSUPPORTED); pad_value = the border value already cast to in_dtype (an integer in its range; read for
+ * PTB_BORDER_CONSTANT only); out DEVICE [V*B, IC, th, tw] of out_dtype (PTB_F32, PTB_F16, PTB_BF16), chunk-major.  The other
+ * arguments are those of ptb_split_tiles_u8.  IC <= 16, V <= 8. */
+int ptb_split_tiles(const void* image, int in_dtype, int IH, int IW, int IC, const int64_t* xs, const int64_t* ys, int B, int th,
+                    int tw, int V, const int* views, const float* scale, const float* bias, int border, float pad_value,
+                    int out_dtype, void* out, ptb_stream_t stream);
 /* ptb_merge_crop == TileMerger.merge (tiles.py:345-346) -> np.moveaxis(.., 0, -1) -> .astype(uint8) | argmax
  * -> ImageSlicer.crop_to_orignal_size (tiles.py:271-280; README.md:225-226): window [top, top+OH) x [left, left+OW) of
  * image[C,H,W] / norm[H,W] (norm == NULL: image is already normalised).  layout 0: out [C, OH, OW], 1: out [OH, OW, C].  kind 0: float32; 1: uint8 by truncating

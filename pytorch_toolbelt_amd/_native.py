@@ -23,6 +23,9 @@ F32, F16, BF16 = range(3)   # PTB_F32 / PTB_F16 / PTB_BF16: element type of the 
 DTYPE_CODES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 U8, I16, U16 = 3, 4, 5      # PTB_U8 / PTB_I16 / PTB_U16: further volume element types of ptb_volume_split
 VOLUME_DTYPE_CODES = {torch.uint8: U8, torch.int16: I16, torch.uint16: U16, torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32}
+IMAGE_DTYPE_CODES = {torch.uint8: U8, torch.uint16: U16, torch.int16: I16}   # image element types of ptb_split_tiles
+# PTB_BORDER_*: OpenCV's border codes (cv2.BORDER_CONSTANT .. cv2.BORDER_REFLECT_101)
+BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101 = range(5)
 ROUND_SRC = 0x100           # PTB_ROUND_SRC, or-ed into a dtype code: round the reduced value to the (half) source type before blending
 
 EFRESH = -5
@@ -123,6 +126,8 @@ SIGNATURES = {
     "ptb_lovasz_bwd": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_int, _c_i64, _c_f, _vp]),
     "ptb_deaug_accumulate": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _ip, _c_int, _i64p, _i64p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp]),
     "ptb_split_tiles_u8": (_c_int, [_vp, _c_int, _c_int, _c_int, _i64p, _i64p, _c_int, _c_int, _c_int, _c_int, _ip, _fp, _fp, _c_int, _vp, _vp]),
+    "ptb_split_tiles": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _i64p, _i64p, _c_int, _c_int, _c_int, _c_int, _ip, _fp, _fp, _c_int, _c_f,
+                                 _c_int, _vp, _vp]),
     "ptb_pointwise_loss_fwd": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_int, _c_f, _c_f, _c_f, _c_f, _vp]),
     "ptb_pointwise_loss_apply": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_int, _c_f, _c_f, _c_f, _c_f, _vp]),
     "ptb_bitempered_binary_fwd": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_f, _c_f, _c_f, _c_int, _c_int, _c_f, _vp]),

@@ -241,11 +241,37 @@ __device__ __forceinline__ float4 round_src4(const float4 v, int on) {
 
 __device__ __forceinline__ float comp(const float4& v, int m) { return m == 0 ? v.x : (m == 1 ? v.y : (m == 2 ? v.z : v.w)); }
 
+// fp32 -> the bits of a PTB_F16 / PTB_BF16 output element, round to nearest even (torch's .to(dtype); v_cvt_pk_bf16_f32 on gfx950)
+template <int OUT>
+__device__ __forceinline__ unsigned short half_bits(float f) {
+    if constexpr (OUT == PTB_F16) return __builtin_bit_cast(unsigned short, (_Float16)f);
+    else return __builtin_bit_cast(unsigned short, (__bf16)f);
+}
+
+// 4 consecutive output elements at element offset `off` of `dst`, whose element type is OUT: fp32 as one 16-byte store, fp16 / bf16
+// rounded (half_bits) as one 8-byte store (off % 4 == 0 and an 8-byte aligned dst)
+template <int OUT>
+__device__ __forceinline__ void out_store4_as(float* dst, long long off, const float4 v) {
+    if constexpr (OUT == PTB_F32) {
+        out_store4(dst + off, v);
+    } else {
+        typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+        const u2 w{(unsigned)half_bits<OUT>(v.x) | ((unsigned)half_bits<OUT>(v.y) << 16), (unsigned)half_bits<OUT>(v.z) | ((unsigned)half_bits<OUT>(v.w) << 16)};
+        u2* p = reinterpret_cast<u2*>(reinterpret_cast<unsigned short*>(dst) + off);
+#if PTB_NT_OUT
+        __builtin_nontemporal_store(w, p);
+#else
+        *p = w;
+#endif
+    }
+}
+
 // One source chunk (this thread's float4 `v` at chunk-local (r, 4q); chunk origin (x0, y0), extent cw x ch of tile b,
 // channel c) written to all a.nviews views of the chunk-major output [V*B, C, H, W].  Row-preserving views are stored
 // straight from the registers at mirrored addresses; the transposing views share one transposed, XOR-swizzled LDS copy
-// of the chunk (ST[c][r] = S[r][c]) read back with ds_read_b128.  `st` = CW*CH floats of LDS.
-template <int CH, bool NONLIN>
+// of the chunk (ST[c][r] = S[r][c]) read back with ds_read_b128.  `st` = CW*CH floats of LDS.  OUT: element type of a.dst (PTB_F32;
+// the split kernels also write PTB_F16 / PTB_BF16 -- converted at the store, the LDS tile stays fp32).
+template <int CH, bool NONLIN, int OUT = PTB_F32>
 __device__ __forceinline__ void scatter_chunk(const ViewArgs& a, int B, int b, int c, int x0, int y0, int cw, int ch, float4 v,
                                               float* st, int tid) {
     constexpr int SL = CH / 4;  // 16-byte slots per LDS row
@@ -265,7 +291,7 @@ __device__ __forceinline__ void scatter_chunk(const ViewArgs& a, int B, int b, i
                 const float4 x4 = ld16<true>(a.weight + off);
                 w.x *= red_dpre(x4.x, a.op); w.y *= red_dpre(x4.y, a.op); w.z *= red_dpre(x4.z, a.op); w.w *= red_dpre(x4.w, a.op);
             }
-            out_store4(a.dst + off, w);
+            out_store4_as<OUT>(a.dst, off, w);
         }
     }
     if (!any_t) return;
@@ -292,7 +318,7 @@ __device__ __forceinline__ void scatter_chunk(const ViewArgs& a, int B, int b, i
                 const float4 x4 = ld16<true>(a.weight + off);
                 w.x *= red_dpre(x4.x, a.op); w.y *= red_dpre(x4.y, a.op); w.z *= red_dpre(x4.z, a.op); w.w *= red_dpre(x4.w, a.op);
             }
-            out_store4(a.dst + off, w);
+            out_store4_as<OUT>(a.dst, off, w);
         }
     }
 }

@@ -44,13 +44,6 @@ __device__ __forceinline__ float widen(const void* p, long long i) {
     else return (float)static_cast<const uint16_t*>(p)[i];
 }
 
-// fp32 -> the output type's bits, round to nearest even (torch's .to(dtype))
-template <int OUT>
-__device__ __forceinline__ unsigned short half_bits(float f) {
-    if constexpr (OUT == PTB_F16) return __builtin_bit_cast(unsigned short, (_Float16)f);
-    else return __builtin_bit_cast(unsigned short, (__bf16)f);
-}
-
 template <int IN, int OUT, bool VEC>
 __global__ __launch_bounds__(256) void volume_split_kernel(const VolSplitArgs a) {
     __shared__ __attribute__((aligned(16))) float st[VSPLIT_LDS];

@@ -206,22 +206,32 @@ class ImageSlicer:
         return crop
 
     # ------------------------------------------------------------------ device-side split
-    def split_device(self, image: torch.Tensor, indices=None, augment=None, scale=None, bias=None, value: int = 0) -> torch.Tensor:
-        """Model input for the tiles ``indices`` straight from a uint8 image that already lives in HBM.
+    def split_device(self, image: torch.Tensor, indices=None, augment=None, scale=None, bias=None, value: int = 0,
+                     border_type=BORDER_CONSTANT, dtype=torch.float32) -> torch.Tensor:
+        """Model input for the tiles ``indices`` straight from an 8- or 16-bit image that already lives in HBM.
 
-        Equals ``torch.stack([image_to_tensor(t) for t in self.split(image)][indices]).float()`` (optionally
-        ``* scale[c] + bias[c]`` and then ``tta.<augment>_image_augment``) -- the front of the reference's loop
-        (README.md:209-216; tiles.py:177-204; utils/torch_utils.py:204-231) -- but as ONE HIP launch: no padded copy,
-        no per-tile HWC->CHW copies, no fp32 upload.  ``image``: CUDA uint8 ``[H, W, C]`` or ``[H, W]``;
-        ``indices``: None (all tiles), a slice, or a sequence of tile indices; ``augment``: None | "fliplr" | "flipud" |
-        "flips" | "d2" | "d4"; ``scale`` / ``bias``: per-channel sequences (both or neither); ``value``: constant border.
-        Returns fp32 ``[V*n, C, tile_h, tile_w]``, chunk-major like the augment functions.
+        Equals ``torch.stack([image_to_tensor(t) for t in self.split(image, border_type, value)][indices]).float()``
+        (optionally ``* scale[c] + bias[c]``, then ``tta.<augment>_image_augment``, then ``.to(dtype)``) -- the front of the
+        reference's loop (README.md:209-216; tiles.py:177-204; utils/torch_utils.py:204-231) -- but as ONE HIP launch per 64 tiles:
+        no padded copy, no per-tile HWC->CHW copies, no fp32 upload.  ``image``: CUDA ``[H, W, C]`` (C <= 16) or ``[H, W]`` of
+        uint8, uint16 or int16; ``indices``: None (all tiles), a slice, or a sequence of tile indices; ``augment``: None | "fliplr" |
+        "flipud" | "flips" | "d2" | "d4"; ``scale`` / ``bias``: per-channel sequences (both or neither); ``value``: the border of
+        ``BORDER_CONSTANT``, cast to the image's dtype first as ``np.pad`` does (uint8 images take 0..255, as before);
+        ``border_type``: OpenCV's codes 0..4 with the semantics of :meth:`split` (the border pads the whole image);
+        ``dtype``: torch.float32, torch.float16 or torch.bfloat16 (round to nearest even).
+        Returns ``[V*n, C, tile_h, tile_w]`` of ``dtype``, chunk-major like the augment functions.
         """
         from .tta import AUGMENT_VIEWS
 
         N.require_device(image, "ImageSlicer.split_device")
-        if image.dtype != torch.uint8:
-            raise NotImplementedError(f"split_device takes a uint8 image, got {image.dtype}")
+        code = N.IMAGE_DTYPE_CODES.get(image.dtype)
+        if code is None:
+            raise NotImplementedError(f"split_device takes a uint8, uint16 or int16 image, got {image.dtype}")
+        out_code = N.DTYPE_CODES.get(dtype)
+        if out_code is None:
+            raise NotImplementedError(f"split_device writes float32, float16 or bfloat16, not {dtype}")
+        if border_type != BORDER_CONSTANT and border_type not in _NP_PAD_MODE:
+            raise NotImplementedError(f"border_type={border_type} is not supported")
         if image.dim() not in (2, 3) or image.shape[0] != self.image_height or image.shape[1] != self.image_width:
             raise ValueError(f"image of shape {tuple(image.shape)} does not match the slicer ({self.image_height}, {self.image_width})")
         if augment is not None and augment not in AUGMENT_VIEWS:
@@ -241,9 +251,15 @@ class ImageSlicer:
             boxes = self.bbox_crops[np.asarray(indices, dtype=np.int64).reshape(-1)]
         n = len(boxes)
         image = image.contiguous()
-        out = torch.empty((len(views) * n, channels, th, tw), device=image.device, dtype=torch.float32)
+        out = torch.empty((len(views) * n, channels, th, tw), device=image.device, dtype=dtype)
         if n == 0:
             return out
+        if border_type != BORDER_CONSTANT:
+            pad = 0.0
+        elif image.dtype == torch.uint8:
+            pad = float(int(value))     # (the uint8 path's contract: an integer border value in 0..255, else "invalid argument")
+        else:                           # np.pad assigns the value into an array of the image's dtype: -1 -> 65535 for uint16
+            pad = float(np.asarray(value).astype(torch.empty(0, dtype=image.dtype).numpy().dtype))
         xy = np.ascontiguousarray(np.asarray(boxes, dtype=np.int64)[:, :2].T)
         fa = None
         if scale is not None:
@@ -252,10 +268,10 @@ class ImageSlicer:
             fa = (sc.ctypes.data_as(N._fp), bi.ctypes.data_as(N._fp))
         lib = N.load()
         with N.on_device(image.device):
-            rc = lib.ptb_split_tiles_u8(image.data_ptr(), self.image_height, self.image_width, channels,
-                                        xy[0].ctypes.data_as(N._i64p), xy[1].ctypes.data_as(N._i64p), n, th, tw,
-                                        len(views), N.int_array(views), fa[0] if fa else None, fa[1] if fa else None,
-                                        int(value), out.data_ptr(), N.stream_ptr(image.device))
+            rc = lib.ptb_split_tiles(image.data_ptr(), code, self.image_height, self.image_width, channels,
+                                     xy[0].ctypes.data_as(N._i64p), xy[1].ctypes.data_as(N._i64p), n, th, tw,
+                                     len(views), N.int_array(views), fa[0] if fa else None, fa[1] if fa else None,
+                                     int(border_type), pad, out_code, out.data_ptr(), N.stream_ptr(image.device))
         N.bump()
         N.check(rc, "ImageSlicer.split_device")
         return out
