@@ -316,9 +316,9 @@ int ptb_split_tiles(const void* image, int in_dtype, int IH, int IW, int IC, con
                     int out_dtype, void* out, ptb_stream_t stream);
 /* ptb_merge_crop == TileMerger.merge (tiles.py:345-346) -> np.moveaxis(.., 0, -1) -> .astype(uint8) | argmax
  * -> ImageSlicer.crop_to_orignal_size (tiles.py:271-280; README.md:225-226): window [top, top+OH) x [left, left+OW) of
- * image[C,H,W] / norm[H,W] (norm == NULL: image is already normalised).  layout 0: out [C, OH, OW], 1: out [OH, OW, C].  kind 0: float32; 1: uint8 by truncating
- * cast (numpy .astype on x86-64: low byte of the int32 truncation, 0 for NaN / out of int32 range); 2 / 3: argmax over
- * channels as uint8 / int64 [OH, OW] (first maximum, NaN counts as maximum; layout ignored). */
+ * image[C,H,W] / norm[H,W] (norm == NULL: image is already normalised).  layout 0: out [C, OH, OW], 1: out [OH, OW, C].
+ * kind = PTB_CROP_F32, PTB_CROP_U8, PTB_CROP_ARGMAX_U8 or PTB_CROP_ARGMAX_I64 (0..3, defined with ptb_volume_merge_crop below;
+ * argmax kinds write [OH, OW]); the fp16 / bf16 kinds 4 and 5 -> PTB_EINVAL.  A window outside the accumulator -> PTB_EBOUNDS. */
 int ptb_merge_crop(const float* image, const float* norm, int C, int H, int W, int top, int left, int OH, int OW, int layout,
                    int kind, void* out, ptb_stream_t stream);
 
@@ -346,9 +346,9 @@ int ptb_volume_accumulate(float* volume, float* norm, const float* weight, const
 int ptb_volume_split(const void* volume, int in_dtype, int D, int H, int W, int C, const int64_t* zs, const int64_t* ys,
                      const int64_t* xs, int B, int d, int h, int w, const float* scale, const float* bias, float pad_value,
                      int out_dtype, void* out, ptb_stream_t stream);
-/* output kinds of ptb_volume_merge_crop (0..3 are the `kind` codes of ptb_merge_crop) */
+/* output kinds of ptb_volume_merge_crop (0..5) and ptb_merge_crop (0..3) */
 #define PTB_CROP_F32 0
-#define PTB_CROP_U8 1         /* truncating cast, as ptb_merge_crop */
+#define PTB_CROP_U8 1         /* truncating cast (numpy .astype on x86-64: low byte of the int32 truncation, 0 for NaN / out of int32 range) */
 #define PTB_CROP_ARGMAX_U8 2  /* argmax over channels: first maximum, NaN counts as maximum; layout ignored */
 #define PTB_CROP_ARGMAX_I64 3
 #define PTB_CROP_F16 4        /* round to nearest even of the fp32 quotient */

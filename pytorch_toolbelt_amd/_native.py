@@ -21,6 +21,12 @@ IDENT, TRANSPOSE, FLIPUD, ROT90_CW, FLIPLR, ROT90_CCW, ROT180, ANTITRANSPOSE = r
 RED_SUM, RED_MEAN, RED_GMEAN, RED_HMEAN, RED_HARMONIC1P, RED_LOGODD, RED_LOG1P = range(7)
 F32, F16, BF16 = range(3)   # PTB_F32 / PTB_F16 / PTB_BF16: element type of the model outputs a `_t` entry point reads
 DTYPE_CODES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
+# PTB_CROP_*: output kinds of ptb_volume_merge_crop (0..5) and ptb_merge_crop (0..3), by (argmax, requested dtype) -> (kind, output dtype)
+CROP_F32, CROP_U8, CROP_ARGMAX_U8, CROP_ARGMAX_I64, CROP_F16, CROP_BF16 = range(6)
+CROP_KINDS = {(False, torch.float32): (CROP_F32, torch.float32), (False, torch.uint8): (CROP_U8, torch.uint8),
+              (False, torch.float16): (CROP_F16, torch.float16), (False, torch.bfloat16): (CROP_BF16, torch.bfloat16),
+              (True, torch.uint8): (CROP_ARGMAX_U8, torch.uint8), (True, torch.int64): (CROP_ARGMAX_I64, torch.int64),
+              (True, torch.float32): (CROP_ARGMAX_I64, torch.int64)}
 U8, I16, U16 = 3, 4, 5      # PTB_U8 / PTB_I16 / PTB_U16: further volume element types of ptb_volume_split
 VOLUME_DTYPE_CODES = {torch.uint8: U8, torch.int16: I16, torch.uint16: U16, torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32}
 IMAGE_DTYPE_CODES = {torch.uint8: U8, torch.uint16: U16, torch.int16: I16}   # image element types of ptb_split_tiles

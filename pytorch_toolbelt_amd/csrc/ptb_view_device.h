@@ -1,5 +1,6 @@
-// Device-side pieces shared by the view kernels (ptb_views.hip) and the loop-edge kernels (ptb_edges.hip):
-// launch descriptors, TTA reductions, the XOR-swizzled LDS tile and the "one chunk -> all V views" scatter.
+// Device-side pieces shared by the view kernels (ptb_views.hip) and the loop-edge kernels (ptb_edges.hip, ptb_volume_edges.hip,
+// ptb_merge_crop.hip): launch descriptors, TTA reductions, the XOR-swizzled LDS tile, the "one chunk -> all V views" scatter and
+// the element conversions.
 #pragma once
 #include <initializer_list>
 
@@ -246,6 +247,17 @@ template <int OUT>
 __device__ __forceinline__ unsigned short half_bits(float f) {
     if constexpr (OUT == PTB_F16) return __builtin_bit_cast(unsigned short, (_Float16)f);
     else return __builtin_bit_cast(unsigned short, (__bf16)f);
+}
+
+// element i of an IN-typed array as fp32 (exact for every element type); IN = PTB_F32 .. PTB_U16
+template <int IN>
+__device__ __forceinline__ float widen(const void* p, long long i) {
+    if constexpr (IN == PTB_F32) return static_cast<const float*>(p)[i];
+    else if constexpr (IN == PTB_F16) return (float)static_cast<const _Float16*>(p)[i];
+    else if constexpr (IN == PTB_BF16) return __uint_as_float((unsigned)static_cast<const unsigned short*>(p)[i] << 16);
+    else if constexpr (IN == PTB_U8) return (float)static_cast<const uint8_t*>(p)[i];
+    else if constexpr (IN == PTB_I16) return (float)static_cast<const int16_t*>(p)[i];
+    else return (float)static_cast<const uint16_t*>(p)[i];
 }
 
 // 4 consecutive output elements at element offset `off` of `dst`, whose element type is OUT: fp32 as one 16-byte store, fp16 / bf16

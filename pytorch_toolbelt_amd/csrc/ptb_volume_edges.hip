@@ -1,16 +1,16 @@
-// ptb_volume_edges.hip -- the two ends of the 3-D tiled-inference loop, on the device (the 3-D counterpart of ptb_edges.hip):
+// ptb_volume_edges.hip -- the 3-D tiled-inference loop on the device, up to the merge (the 3-D counterpart of ptb_edges.hip):
 //
 //   * ptb_volume_split: VolumeSlicer.split (inference/tiles_3d.py; np.pad + a copy per tile) + channels first + .float()
 //     [+ per-channel affine] [+ .to(half)] from a device-resident [D, H, W(, C)] volume (uint8 / int16 / uint16 / fp16 / bf16 /
 //     fp32) straight into the model batch [n, C, d, h, w].  No padded volume, no per-tile copies, no fp32 upload.
-//   * ptb_volume_merge_crop: VolumeMerger.merge (volume / norm_mask, ptb_merge_div) + crop to VolumeSlicer.orignal_image_roi
-//     [+ channels last] [+ cast | argmax over channels] in one pass that reads and writes only the cropped window.
+//   * ptb_volume_accumulate: VolumeMerger.integrate_batch, tile after tile into the [C, D, H, W] accumulator.
 //
-// Both are HBM-bound streaming kernels.  The split kernel is write-bound (4 / sizeof(in) fp32 output bytes per input byte):
+// The merge + crop of the accumulator is ptb_merge_crop.hip (shared with the 2-D loop).  Both kernels here are HBM-bound
+// streaming kernels.  The split kernel is write-bound (4 / sizeof(in) fp32 output bytes per input byte):
 // a workgroup owns a chunk of consecutive rows (z, y) of one tile, gathers it -- all channels of contiguous input row runs,
 // pad voxels included -- into channel planes in LDS, then writes each channel's rows with 16-byte stores per lane (for
 // full-width chunks a channel's rows are one contiguous run of the output).
-#include "ptb_edges_device.h"
+#include "ptb_view_device.h"
 
 namespace ptb {
 
@@ -32,17 +32,6 @@ struct VolSplitArgs {
     float scale[MAX_VSPLIT_C], bias[MAX_VSPLIT_C];
     int tz[VSPLIT_GROUP], ty[VSPLIT_GROUP], tx[VSPLIT_GROUP];  // tile origins in volume coordinates; may overhang any face
 };
-
-// element i of the volume as fp32 (exact for every supported dtype); IN = PTB_F32 .. PTB_U16
-template <int IN>
-__device__ __forceinline__ float widen(const void* p, long long i) {
-    if constexpr (IN == PTB_F32) return static_cast<const float*>(p)[i];
-    else if constexpr (IN == PTB_F16) return (float)static_cast<const _Float16*>(p)[i];
-    else if constexpr (IN == PTB_BF16) return __uint_as_float((unsigned)static_cast<const unsigned short*>(p)[i] << 16);
-    else if constexpr (IN == PTB_U8) return (float)static_cast<const uint8_t*>(p)[i];
-    else if constexpr (IN == PTB_I16) return (float)static_cast<const int16_t*>(p)[i];
-    else return (float)static_cast<const uint16_t*>(p)[i];
-}
 
 template <int IN, int OUT, bool VEC>
 __global__ __launch_bounds__(256) void volume_split_kernel(const VolSplitArgs a) {
@@ -136,138 +125,6 @@ __global__ __launch_bounds__(256) void volume_split_kernel(const VolSplitArgs a)
     }
 }
 
-// ------------------------------------------------------------------------------------------------ merge + crop
-enum { VCROP_F32 = PTB_CROP_F32, VCROP_U8 = PTB_CROP_U8, VCROP_ARGMAX_U8 = PTB_CROP_ARGMAX_U8, VCROP_ARGMAX_I64 = PTB_CROP_ARGMAX_I64,
-       VCROP_F16 = PTB_CROP_F16, VCROP_BF16 = PTB_CROP_BF16 };
-
-struct VolCropArgs {
-    const float* vol;   // [C, D, H, W] accumulator
-    const float* norm;  // [D, H, W]
-    void* out;
-    int C, D, H, W;
-    int z0, y0, x0, OD, OH, OW;
-};
-
-// nv (<= 4) consecutive output elements starting at element `o`, converted to KIND; one 16 / 8 / 4 B store when aligned
-template <int KIND>
-__device__ __forceinline__ void store_out(void* out, long long o, const float* v, int nv) {
-    if constexpr (KIND == VCROP_F32) {
-        store_f32x4(static_cast<float*>(out) + o, v, nv);
-    } else if constexpr (KIND == VCROP_U8) {
-        uint8_t b[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) b[m] = cast_u8(v[m]);
-        store_u8x4(static_cast<uint8_t*>(out) + o, b, nv);
-    } else {
-        constexpr int OUT = KIND == VCROP_F16 ? PTB_F16 : PTB_BF16;
-        unsigned short* p = static_cast<unsigned short*>(out) + o;
-        unsigned short b[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) b[m] = half_bits<OUT>(v[m]);
-        if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
-            typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-            *reinterpret_cast<u2*>(p) = u2{(unsigned)b[0] | ((unsigned)b[1] << 16), (unsigned)b[2] | ((unsigned)b[3] << 16)};
-        } else {
-            for (int m = 0; m < nv; ++m) p[m] = b[m];
-        }
-    }
-}
-
-// Output voxel group t (4 consecutive x of one output row) -> its source offset, output voxel offset and width
-struct CropPos { long long src, dst; int nv; };
-__device__ __forceinline__ CropPos crop_pos(const VolCropArgs& a, long long t, int groups_x) {
-    const long long row = t / groups_x;
-    const int x = (int)(t - row * groups_x) * 4;
-    const int z = (int)(row / a.OH), y = (int)(row - (long long)z * a.OH);
-    CropPos p;
-    p.src = ((long long)(a.z0 + z) * a.H + a.y0 + y) * a.W + a.x0 + x;
-    p.dst = row * a.OW + x;
-    p.nv = min(4, a.OW - x);
-    return p;
-}
-
-// Channel-planar outputs ([C, OD, OH, OW]) and argmax: one pass over the channels with running state, any C.
-template <int KIND>
-__global__ __launch_bounds__(256) void volume_crop_planar_kernel(const VolCropArgs a, bool vec) {
-    const int groups_x = (a.OW + 3) / 4;
-    const long long total = (long long)a.OD * a.OH * groups_x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long iplane = (long long)a.D * a.H * a.W, oplane = (long long)a.OD * a.OH * a.OW;
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-        const CropPos p = crop_pos(a, t, groups_x);
-        float n[4], v[4];
-        float best[4] = {0.f, 0.f, 0.f, 0.f};
-        int arg[4] = {0, 0, 0, 0};
-        load_px4(a.norm + p.src, p.nv, vec, n);
-        for (int c = 0; c < a.C; ++c) {
-            load_px4(a.vol + c * iplane + p.src, p.nv, vec, v);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) v[m] = __fdiv_rn(v[m], n[m]);  // ptb_merge_div: no eps clamp
-            if constexpr (KIND == VCROP_ARGMAX_U8 || KIND == VCROP_ARGMAX_I64) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {  // first maximum wins; NaN counts as the maximum (torch argmax)
-                    const bool take = c == 0 ? true : (v[m] > best[m] || (v[m] != v[m] && best[m] == best[m]));
-                    best[m] = take ? v[m] : best[m];
-                    arg[m] = take ? c : arg[m];
-                }
-            } else {
-                store_out<KIND>(a.out, c * oplane + p.dst, v, p.nv);
-            }
-        }
-        if constexpr (KIND == VCROP_ARGMAX_U8) {
-            uint8_t b[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) b[m] = (uint8_t)arg[m];
-            store_u8x4(static_cast<uint8_t*>(a.out) + p.dst, b, p.nv);
-        } else if constexpr (KIND == VCROP_ARGMAX_I64) {
-            long long* o = static_cast<long long*>(a.out) + p.dst;
-            for (int m = 0; m < p.nv; ++m) o[m] = arg[m];
-        }
-    }
-}
-
-// Channel-last outputs ([OD, OH, OW, C]).  CT in 2..4: the CT channels of 4 voxels held in registers, so the thread's 4 * CT
-// contiguous output elements leave as CT full-width stores.  CT == 0: any C, element by element (not a tuned path).
-template <int KIND, int CT>
-__global__ __launch_bounds__(256) void volume_crop_dhwc_kernel(const VolCropArgs a, bool vec) {
-    const int groups_x = (a.OW + 3) / 4;
-    const long long total = (long long)a.OD * a.OH * groups_x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long iplane = (long long)a.D * a.H * a.W;
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-        const CropPos p = crop_pos(a, t, groups_x);
-        float n[4];
-        load_px4(a.norm + p.src, p.nv, vec, n);
-        if constexpr (CT == 0) {
-            for (int c = 0; c < a.C; ++c) {
-                float v[4];
-                load_px4(a.vol + c * iplane + p.src, p.nv, vec, v);
-                for (int m = 0; m < p.nv; ++m) {
-                    const float q[4] = {__fdiv_rn(v[m], n[m]), 0.f, 0.f, 0.f};
-                    store_out<KIND>(a.out, (p.dst + m) * a.C + c, q, 1);
-                }
-            }
-        } else {
-            float v[CT][4];
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                load_px4(a.vol + c * iplane + p.src, p.nv, vec, v[c]);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) v[c][m] = __fdiv_rn(v[c][m], n[m]);
-            }
-            // element e = m * CT + c of the thread's contiguous run; group g = elements 4g .. 4g+3
-#pragma unroll
-            for (int g = 0; g < CT; ++g) {
-                float b[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) b[j] = v[(4 * g + j) % CT][(4 * g + j) / CT];
-                const int left = p.nv * CT - 4 * g;
-                if (left > 0) store_out<KIND>(a.out, p.dst * CT + 4 * g, b, left < 4 ? left : 4);
-            }
-        }
-    }
-}
-
 template <int IN, int OUT>
 int launch_split(VolSplitArgs& g, const int64_t* zs, const int64_t* ys, const int64_t* xs, int B, bool vec, hipStream_t s) {
     for (int b0 = 0; b0 < B; b0 += VSPLIT_GROUP) {
@@ -290,16 +147,55 @@ int launch_split_in(int out_dtype, VolSplitArgs& g, const int64_t* zs, const int
     return launch_split<IN, PTB_BF16>(g, zs, ys, xs, B, vec, s);
 }
 
-template <int KIND>
-void launch_crop(const VolCropArgs& a, int layout, bool vec, dim3 grid, hipStream_t s) {
-    if constexpr (KIND == VCROP_ARGMAX_U8 || KIND == VCROP_ARGMAX_I64) {
-        hipLaunchKernelGGL(volume_crop_planar_kernel<KIND>, grid, dim3(256), 0, s, a, vec);
-    } else {
-        if (layout == 0 || a.C == 1) hipLaunchKernelGGL(volume_crop_planar_kernel<KIND>, grid, dim3(256), 0, s, a, vec);
-        else if (a.C == 2) hipLaunchKernelGGL((volume_crop_dhwc_kernel<KIND, 2>), grid, dim3(256), 0, s, a, vec);
-        else if (a.C == 3) hipLaunchKernelGGL((volume_crop_dhwc_kernel<KIND, 3>), grid, dim3(256), 0, s, a, vec);
-        else if (a.C == 4) hipLaunchKernelGGL((volume_crop_dhwc_kernel<KIND, 4>), grid, dim3(256), 0, s, a, vec);
-        else hipLaunchKernelGGL((volume_crop_dhwc_kernel<KIND, 0>), grid, dim3(256), 0, s, a, vec);
+// ------------------------------------------------------------------------------------------------ accumulate
+// VolumeMerger.integrate_batch (reference inference/tiles_3d.py:195-208): volume[:, z:z+d, y:y+h, x:x+w] += tile * weight,
+// norm_mask[...] += weight, tile after tile.  One launch per tile: a tile never overlaps itself, so every launch owns
+// its accumulator region exclusively (race-free without atomics) and the stream order reproduces the reference's
+// sequential fp32 order bit for bit.  A 3-D tile is megabytes, so a launch per tile is not launch-bound.
+struct VolArgs {
+    float* volume;        // [C, D, H, W]
+    float* norm;          // [D, H, W]
+    const float* weight;  // [d, h, w]
+    const float* tile;    // [C, d, h, w]
+    int C, d, h, w, D, H, W;
+    int z0, y0, x0;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void volume_accumulate_kernel(const VolArgs a) {
+    constexpr int PIX = VEC ? 4 : 1;
+    const int wq = (a.w + PIX - 1) / PIX;
+    const long long per_chan = (long long)a.d * a.h * wq;
+    const long long total = per_chan * a.C;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long tplane = (long long)a.d * a.h * a.w, vplane = (long long)a.D * a.H * a.W;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int c = (int)(i / per_chan);
+        long long r = i - (long long)c * per_chan;
+        const int q = (int)(r % wq);
+        r /= wq;
+        const int y = (int)(r % a.h), z = (int)(r / a.h);
+        const long long toff = ((long long)z * a.h + y) * a.w + (long long)q * PIX;
+        const long long voff = ((long long)(a.z0 + z) * a.H + (a.y0 + y)) * a.W + a.x0 + (long long)q * PIX;
+        if (VEC) {
+            const float4 t = *reinterpret_cast<const float4*>(a.tile + c * tplane + toff);
+            const float4 w4 = *reinterpret_cast<const float4*>(a.weight + toff);
+            float4* vp = reinterpret_cast<float4*>(a.volume + c * vplane + voff);
+            float4 v = *vp;
+            v.x = __fadd_rn(v.x, __fmul_rn(t.x, w4.x)); v.y = __fadd_rn(v.y, __fmul_rn(t.y, w4.y));
+            v.z = __fadd_rn(v.z, __fmul_rn(t.z, w4.z)); v.w = __fadd_rn(v.w, __fmul_rn(t.w, w4.w));
+            *vp = v;
+            if (c == 0) {
+                float4* np = reinterpret_cast<float4*>(a.norm + voff);
+                float4 n = *np;
+                n.x = __fadd_rn(n.x, w4.x); n.y = __fadd_rn(n.y, w4.y); n.z = __fadd_rn(n.z, w4.z); n.w = __fadd_rn(n.w, w4.w);
+                *np = n;
+            }
+        } else {
+            const float wv = a.weight[toff];
+            a.volume[c * vplane + voff] = __fadd_rn(a.volume[c * vplane + voff], __fmul_rn(a.tile[c * tplane + toff], wv));
+            if (c == 0) a.norm[voff] = __fadd_rn(a.norm[voff], wv);
+        }
     }
 }
 
@@ -351,26 +247,27 @@ extern "C" int ptb_volume_split(const void* volume, int in_dtype, int D, int H, 
     }
 }
 
-extern "C" int ptb_volume_merge_crop(const float* volume, const float* norm, int C, int D, int H, int W, int z0, int y0, int x0, int OD,
-                                     int OH, int OW, int layout, int kind, void* out, ptb_stream_t stream) {
-    if (!volume || !norm || !out || C < 1 || D < 1 || H < 1 || W < 1 || OD < 0 || OH < 0 || OW < 0) return PTB_EINVAL;
-    if (layout < 0 || layout > 1 || kind < VCROP_F32 || kind > VCROP_BF16) return PTB_EINVAL;
-    if (z0 < 0 || y0 < 0 || x0 < 0 || (long long)z0 + OD > D || (long long)y0 + OH > H || (long long)x0 + OW > W) return PTB_EBOUNDS;
-    if (kind == VCROP_ARGMAX_U8 && C > 256) return PTB_EUNSUPPORTED;
-    if (OD == 0 || OH == 0 || OW == 0) return PTB_OK;
-    const VolCropArgs a{volume, norm, out, C, D, H, W, z0, y0, x0, OD, OH, OW};
-    const long long total = (long long)OD * OH * ((OW + 3) / 4);
-    const long long want = (total + 255) / 256;
-    const dim3 grid((unsigned)(want < 16384 ? want : 16384));
-    hipStream_t s = (hipStream_t)stream;
-    const bool vec = !g_force_scalar && W % 4 == 0 && x0 % 4 == 0 && aligned16(volume) && aligned16(norm);
-    switch (kind) {
-        case VCROP_F32: launch_crop<VCROP_F32>(a, layout, vec, grid, s); break;
-        case VCROP_U8: launch_crop<VCROP_U8>(a, layout, vec, grid, s); break;
-        case VCROP_ARGMAX_U8: launch_crop<VCROP_ARGMAX_U8>(a, layout, vec, grid, s); break;
-        case VCROP_ARGMAX_I64: launch_crop<VCROP_ARGMAX_I64>(a, layout, vec, grid, s); break;
-        case VCROP_F16: launch_crop<VCROP_F16>(a, layout, vec, grid, s); break;
-        default: launch_crop<VCROP_BF16>(a, layout, vec, grid, s); break;
+extern "C" int ptb_volume_accumulate(float* volume, float* norm, const float* weight, const float* tiles, const int64_t* zs,
+                                     const int64_t* ys, const int64_t* xs, int B, int C, int d, int h, int w, int D, int H, int W,
+                                     ptb_stream_t stream) {
+    if (!volume || !norm || !weight || !tiles || !zs || !ys || !xs) return PTB_EINVAL;
+    if (B < 0 || C < 1 || d < 1 || h < 1 || w < 1 || D < 1 || H < 1 || W < 1) return PTB_EINVAL;
+    for (int b = 0; b < B; ++b)
+        if (zs[b] < 0 || ys[b] < 0 || xs[b] < 0 || zs[b] + d > D || ys[b] + h > H || xs[b] + w > W) return PTB_EBOUNDS;
+    VolArgs a{volume, norm, weight, nullptr, C, d, h, w, D, H, W, 0, 0, 0};
+    const long long tile_elems = (long long)C * d * h * w;
+    const bool base_vec = !g_force_scalar && w % 4 == 0 && W % 4 == 0 && aligned16(volume) && aligned16(norm) && aligned16(weight) &&
+                          aligned16(tiles) && tile_elems % 4 == 0;
+    for (int b = 0; b < B; ++b) {
+        a.tile = tiles + (long long)b * tile_elems;
+        a.z0 = (int)zs[b]; a.y0 = (int)ys[b]; a.x0 = (int)xs[b];
+        const bool vec = base_vec && a.x0 % 4 == 0;
+        const long long items = (long long)C * d * h * (vec ? w / 4 : w);
+        const long long want = (items + 255) / 256;
+        const dim3 grid((unsigned)(want < 16384 ? want : 16384)), block(256);
+        if (vec) hipLaunchKernelGGL(ptb::volume_accumulate_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(ptb::volume_accumulate_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+        if (int rc = ptb::check_launch()) return rc;
     }
-    return check_launch();
+    return PTB_OK;
 }

@@ -380,6 +380,26 @@ def _device_window(weight: np.ndarray, device, signature=None):
     return cached.clone()
 
 
+def _crop_window(crop, shape, layout):
+    """``crop`` (an ImageSlicer: its margins and image size, or ``(top, left, height, width)``) -> the window, checked against the
+    accumulator's ``(H', W')``."""
+    if isinstance(crop, ImageSlicer):
+        top, left, oh, ow = crop.margin_top, crop.margin_left, crop.image_height, crop.image_width
+    else:
+        top, left, oh, ow = (int(v) for v in crop)
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
+    if top < 0 or left < 0 or oh < 0 or ow < 0 or top + oh > shape[0] or left + ow > shape[1]:
+        raise ValueError("crop window is outside the accumulator")
+    return top, left, oh, ow
+
+
+def _crop_kind(dtype, argmax):
+    """(PTB_CROP_* kind, output dtype) of a 2-D ``merge_crop``: ptb_merge_crop writes kinds 0..3 (no float16 / bfloat16 output)."""
+    kind = N.CROP_KINDS.get((bool(argmax), dtype))
+    if kind is None or kind[0] > N.CROP_ARGMAX_I64:
+        raise NotImplementedError(f"merge_crop: dtype {dtype} is not supported")
+    return kind
 
 
 class TileMerger:
@@ -786,9 +806,6 @@ class TileMerger:
         out = self._incremental.merge_into(self._image)
         return out if self.dtype == torch.float32 else out.to(self.dtype)
 
-
-    _CROP_KINDS = {"float32": (0, torch.float32), "uint8": (1, torch.uint8), "argmax_u8": (2, torch.uint8), "argmax_i64": (3, torch.int64)}
-
     def merge_crop(self, crop, layout: str = "hwc", dtype=torch.float32, argmax: bool = False) -> torch.Tensor:
         """``merge()`` + channel-last + cast + ``crop_to_orignal_size`` in one pass over the cropped window only.
 
@@ -799,21 +816,8 @@ class TileMerger:
         torch.uint8 (truncating cast, like ``ndarray.astype``); ``argmax=True`` returns ``[H, W]`` class indices
         (``dtype`` uint8 or int64) instead.
         """
-        if isinstance(crop, ImageSlicer):
-            top, left, oh, ow = crop.margin_top, crop.margin_left, crop.image_height, crop.image_width
-        else:
-            top, left, oh, ow = (int(v) for v in crop)
-        if layout not in ("hwc", "chw"):
-            raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
-        if argmax:
-            key = {torch.uint8: "argmax_u8", torch.int64: "argmax_i64", torch.float32: "argmax_i64"}.get(dtype)
-        else:
-            key = {torch.float32: "float32", torch.uint8: "uint8"}.get(dtype)
-        if key is None:
-            raise NotImplementedError(f"merge_crop: dtype {dtype} is not supported")
-        kind, out_dtype = self._CROP_KINDS[key]
-        if top < 0 or left < 0 or oh < 0 or ow < 0 or top + oh > self.image_height or left + ow > self.image_width:
-            raise ValueError("crop window is outside the accumulator")
+        top, left, oh, ow = _crop_window(crop, (self.image_height, self.image_width), layout)
+        kind, out_dtype = _crop_kind(dtype, argmax)
         self._selfplan.note()
         planned = self._merged is not None
         if planned:
@@ -908,23 +912,13 @@ class HostBackedTileMerger(TileMerger):
         return self._host.image
 
     def merge_crop(self, crop, layout: str = "hwc", dtype=torch.float32, argmax: bool = False) -> torch.Tensor:
-        if isinstance(crop, ImageSlicer):
-            top, left, oh, ow = crop.margin_top, crop.margin_left, crop.image_height, crop.image_width
-        else:
-            top, left, oh, ow = (int(v) for v in crop)
-        if layout not in ("hwc", "chw"):
-            raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
-        if top < 0 or left < 0 or oh < 0 or ow < 0 or top + oh > self.image_height or left + ow > self.image_width:
-            raise ValueError("crop window is outside the accumulator")
+        top, left, oh, ow = _crop_window(crop, (self.image_height, self.image_width), layout)
         window = self.merge()[:, top:top + oh, left:left + ow]
+        _, out_dtype = _crop_kind(dtype, argmax)
         if argmax:
-            if dtype not in (torch.uint8, torch.int64, torch.float32):
-                raise NotImplementedError(f"merge_crop: dtype {dtype} is not supported")
-            return window.argmax(dim=0).to(torch.uint8 if dtype == torch.uint8 else torch.int64)
-        if dtype not in (torch.float32, torch.uint8):
-            raise NotImplementedError(f"merge_crop: dtype {dtype} is not supported")
+            return window.argmax(dim=0).to(out_dtype)
         out = window.permute(1, 2, 0) if layout == "hwc" else window
-        return out.to(dtype).contiguous()
+        return out.to(out_dtype).contiguous()
 
 
 class CudaTileMerger(TileMerger):

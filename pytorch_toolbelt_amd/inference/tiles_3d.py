@@ -163,8 +163,12 @@ class VolumeSlicer:
         return np.ones(volume_size, dtype=np.float32)
 
 
-_CROP_KINDS = {torch.float32: 0, torch.uint8: 1, torch.float16: 4, torch.bfloat16: 5}     # PTB_CROP_*
-_ARGMAX_KINDS = {torch.uint8: (2, torch.uint8), torch.int64: (3, torch.int64), torch.float32: (3, torch.int64)}
+def _crop_kind(dtype, argmax):
+    """(PTB_CROP_* kind, output dtype) of a 3-D ``merge_crop``."""
+    kind = N.CROP_KINDS.get((bool(argmax), dtype))
+    if kind is None:
+        raise NotImplementedError(f"merge_crop: argmax dtype {dtype} is not supported" if argmax else f"merge_crop: dtype {dtype} is not supported")
+    return kind
 
 
 def _crop_window(crop, shape, layout):
@@ -291,15 +295,10 @@ class VolumeMerger:
         """
         shape = tuple(int(s) for s in self.volume.shape[1:])
         z0, y0, x0, od, oh, ow = _crop_window(crop, shape, layout)
+        kind, out_dtype = _crop_kind(dtype, argmax)
         if argmax:
-            if dtype not in _ARGMAX_KINDS:
-                raise NotImplementedError(f"merge_crop: argmax dtype {dtype} is not supported")
-            kind, out_dtype = _ARGMAX_KINDS[dtype]
             out_shape = (od, oh, ow)
         else:
-            if dtype not in _CROP_KINDS:
-                raise NotImplementedError(f"merge_crop: dtype {dtype} is not supported")
-            kind, out_dtype = _CROP_KINDS[dtype], dtype
             out_shape = (self.channels, od, oh, ow) if layout == "cdhw" else (od, oh, ow, self.channels)
         for t in (self.volume, self.norm_mask):
             N.require_device(t, "VolumeMerger.merge_crop")
@@ -360,11 +359,8 @@ class HostBackedVolumeMerger(VolumeMerger):
         """``VolumeMerger.merge_crop`` with torch ops: the cropped window of ``merge()``, moved and converted."""
         z0, y0, x0, od, oh, ow = _crop_window(crop, tuple(int(s) for s in self.volume.shape[1:]), layout)
         window = self.merge()[:, z0:z0 + od, y0:y0 + oh, x0:x0 + ow]
+        _, out_dtype = _crop_kind(dtype, argmax)
         if argmax:
-            if dtype not in _ARGMAX_KINDS:
-                raise NotImplementedError(f"merge_crop: argmax dtype {dtype} is not supported")
-            return window.argmax(dim=0).to(_ARGMAX_KINDS[dtype][1])
-        if dtype not in _CROP_KINDS:
-            raise NotImplementedError(f"merge_crop: dtype {dtype} is not supported")
+            return window.argmax(dim=0).to(out_dtype)
         out = window.permute(1, 2, 3, 0) if layout == "dhwc" else window
-        return out.to(dtype).contiguous()
+        return out.to(out_dtype).contiguous()

@@ -212,7 +212,7 @@ def test_full_size_cfg2_edges(dev):
 @pytest.mark.parametrize("C", [2, 3, 4])
 def test_merge_crop_fp32_channel_last_repack(C, dev):
     """fp32 channel-last output with a width that is a multiple of 4: the lanes' runs are exchanged through LDS before they
-    are stored (csrc/ptb_edges.hip) -- more than one workgroup iteration, a partial last workgroup, aligned and unaligned
+    are stored (csrc/ptb_merge_crop.hip) -- more than one workgroup iteration, a partial last workgroup, aligned and unaligned
     windows; bit-exact against the oracle."""
     from pytorch_toolbelt_amd.inference.tiles import TileMerger
 

@@ -1,5 +1,6 @@
 """CPU: the 3-D loop edges -- ptb_volume_split / ptb_volume_merge_crop are declared and exported, refuse bad arguments before any
-launch, VolumeSlicer.split_device refuses host tensors, and HostBackedVolumeMerger.merge_crop equals the reference expressions."""
+launch (as does the 2-D ptb_merge_crop, which shares the merge + crop kernels), VolumeSlicer.split_device refuses host tensors, and
+HostBackedVolumeMerger.merge_crop equals the reference expressions."""
 import ctypes
 import os
 import re
@@ -72,6 +73,30 @@ def test_volume_merge_crop_refuses_bad_arguments():
     assert _crop(lib, window=(0, 0, 1, 4, 4, 8)) == -4
     assert _crop(lib, C=300, kind=2) == -2
     assert _crop(lib, window=(0, 0, 0, 0, 4, 4)) == 0     # empty window: nothing to launch
+
+
+def _crop2(lib, image=FAKE, norm=FAKE, C=2, window=(0, 0, 4, 4), layout=0, kind=0, out=FAKE):
+    return lib.ptb_merge_crop(image, norm, C, 8, 8, *window, layout, kind, out, None)
+
+
+def test_merge_crop_refuses_bad_arguments():
+    """ptb_merge_crop (2-D) keeps its own checks and their order: the window is checked before layout and kind, kinds 4 and 5
+    (fp16 / bf16 output) are refused, and norm may be NULL."""
+    N, lib = _lib()
+    assert _crop2(lib, image=None) == -1 and _crop2(lib, out=None) == -1
+    assert _crop2(lib, C=0) == -1
+    assert _crop2(lib, window=(0, 0, -1, 4)) == -1
+    assert _crop2(lib, window=(5, 0, 4, 4)) == -4
+    assert _crop2(lib, window=(0, -1, 4, 4)) == -4
+    assert _crop2(lib, window=(0, 1, 4, 8)) == -4
+    assert _crop2(lib, window=(5, 0, 4, 4), layout=2, kind=6) == -4    # the window first
+    assert _crop2(lib, layout=2) == -1 and _crop2(lib, layout=-1) == -1
+    for kind in (-1, 4, 5, 6):
+        assert _crop2(lib, kind=kind) == -1, kind
+        assert _crop2(lib, norm=None, kind=kind) == -1, kind
+    assert _crop2(lib, C=300, kind=2) == -2
+    assert _crop2(lib, window=(0, 0, 0, 4)) == 0 and _crop2(lib, window=(0, 0, 4, 0)) == 0     # empty window: nothing to launch
+    assert _crop2(lib, norm=None, window=(0, 0, 0, 4)) == 0                                   # norm == NULL is accepted
 
 
 def test_split_device_has_no_cpu_fallback():

@@ -140,18 +140,22 @@ def test_merge_crop_matches_merge_then_crop(C):
             assert got.dtype == out and torch.equal(got, full.argmax(0).to(out)), (C, nan, dtype)
 
 
-def test_merge_crop_windows():
-    slicer, merger = _merger(4, seed=11)
+@pytest.mark.parametrize("C", [2, 3, 4])
+def test_merge_crop_windows(C):
+    slicer, merger = _merger(C, seed=11)
     full = merger.merge()
     D, H, W = full.shape[1:]
-    # unaligned origins, widths that are not multiples of 4, the whole accumulator, a single voxel, an empty window
-    for z0, y0, x0, od, oh, ow in ((1, 2, 3, 5, 7, 9), (0, 0, 0, D, H, W), (D - 1, H - 1, W - 1, 1, 1, 1), (0, 4, 4, 3, 2, 8)):
+    # unaligned origins, widths that are not multiples of 4, the whole accumulator, a single voxel, an empty window; fp32 "dhwc"
+    # with OW % 4 == 0 exchanges its stores through LDS: group counts that are not multiples of 256 (5 * 9 * 3; 23 * 18 * 6 over
+    # several workgroups, from an unaligned origin)
+    for z0, y0, x0, od, oh, ow in ((1, 2, 3, 5, 7, 9), (0, 0, 0, D, H, W), (D - 1, H - 1, W - 1, 1, 1, 1), (0, 4, 4, 3, 2, 8),
+                                   (1, 2, 4, 5, 9, 12), (0, 0, 2, D, H, 24)):
         win = full[:, z0:z0 + od, y0:y0 + oh, x0:x0 + ow]
         for layout in ("cdhw", "dhwc"):
             got = merger.merge_crop((z0, y0, x0, od, oh, ow), layout=layout)
             torch.testing.assert_close(got, win if layout == "cdhw" else win.permute(1, 2, 3, 0), rtol=0, atol=0, equal_nan=True)
         assert torch.equal(merger.merge_crop((z0, y0, x0, od, oh, ow), argmax=True), win.argmax(0))
-    assert merger.merge_crop((0, 0, 0, 0, 3, 3)).shape == (4, 0, 3, 3)
+    assert merger.merge_crop((0, 0, 0, 0, 3, 3)).shape == (C, 0, 3, 3)
     with pytest.raises(ValueError):
         merger.merge_crop((0, 0, 1, D, H, W))
 

@@ -7,7 +7,7 @@ split:  every tile of the volume in batches of --batch tiles, for int16 C = 1 (C
         MR / microscopy) volumes, fp32 and bf16 outputs.  Bytes the algorithm needs: each tile's input voxels read once, its output
         written once (n * d * h * w * C * (sizeof(in) + sizeof(out))).
 merge:  merge_crop of the [C, 512, 512, 512] accumulator to the volume, C = 1 and 4, fp32 / bf16 values and the uint8 argmax label
-        map.  Bytes: the window's C accumulator planes and the normaliser read once, the output written once.
+        map, channels first ("cdhw"); for C = 4 also fp32 channels last ("dhwc").  Bytes: the window's C accumulator planes and the normaliser read once, the output written once.
 
 Each configuration is warmed up, then a full pass is timed --repeats times; the median is reported.  GB/s = bytes / time; "of 8 TB/s"
 is that rate over the MI355X's HBM peak.  Prints one line per configuration and, with --out, writes them as JSON.
@@ -89,10 +89,13 @@ def main():
         merger.volume.uniform_(0, 1, generator=gen)
         merger.norm_mask.uniform_(1, 8, generator=gen)
         vox = int(np.prod(SHAPE))
-        for label, kw, out_bytes in (("fp32", dict(dtype=torch.float32), 4 * C), ("bf16", dict(dtype=torch.bfloat16), 2 * C),
-                                     ("argmax uint8", dict(argmax=True, dtype=torch.uint8), 1)):
+        configs = (("cdhw -> fp32", dict(dtype=torch.float32), 4 * C), ("cdhw -> bf16", dict(dtype=torch.bfloat16), 2 * C),
+                   ("cdhw -> argmax uint8", dict(argmax=True, dtype=torch.uint8), 1))
+        if C == 4:
+            configs += (("dhwc -> fp32", dict(layout="dhwc", dtype=torch.float32), 4 * C),)
+        for label, kw, out_bytes in configs:
             nbytes = vox * (4 * C + 4 + out_bytes)
-            rows.append(row("merge", f"C={C} cdhw -> {label}", nbytes, timed(lambda: merger.merge_crop(slicer, **kw), args.repeats)))
+            rows.append(row("merge", f"C={C} {label}", nbytes, timed(lambda: merger.merge_crop(slicer, **kw), args.repeats)))
         del merger
         torch.cuda.empty_cache()
     if args.out:
