@@ -360,6 +360,36 @@ int ptb_volume_split(const void* volume, int in_dtype, int D, int H, int W, int 
 int ptb_volume_merge_crop(const float* volume, const float* norm, int C, int D, int H, int W, int z0, int y0, int x0, int OD, int OH,
                           int OW, int layout, int kind, void* out, ptb_stream_t stream);
 
+/* ---- Mirror test-time augmentation of 3-D tiles (inference/tta_3d.py; no reference counterpart: the spec is the torch expression
+ * cat([x.flip(dims_v)]) / stack([y_v.flip(dims_v)]).reduce(0)) -------------------------------------------------------------------
+ * A view is a 3-bit mask: bit 0 flips W, bit 1 flips H, bit 2 flips D (view m of [B, C, D, H, W] = x.flip(dims) with dims holding 2
+ * if m & 4, 3 if m & 2, 4 if m & 1).  A flip is its own inverse, so de-augmentation uses the same masks.  masks HOST int[nviews],
+ * each 0..7; 1 <= nviews <= 8.  Batches are chunk-major: row v * B + b holds view v of tile b.  dtype = PTB_F32, PTB_F16 or
+ * PTB_BF16.  Every argument is validated before anything is launched; one [D, H, W] plane of more than 2^31 - 2^21 voxels
+ * -> PTB_EUNSUPPORTED.
+ * ptb_volume_mirror: in_is_batch = 1: src [B, C, D, H, W] -> dst [V*B, C, D, H, W], dst[v*B + b] = flip_v(src[b]) (augment);
+ * in_is_batch = 0: src [V*B, C, D, H, W] -> dst [V, B, C, D, H, W], dst[v, b] = flip_v(src[v*B + b]) (the un-flipped stack).
+ * dst has the type of src (a bit copy). */
+int ptb_volume_mirror(const void* src, int dtype, void* dst, int nviews, const int* masks, int in_is_batch, int B, int C, int D, int H,
+                      int W, ptb_stream_t stream);
+/* ptb_volume_mirror_reduce: src [V*B, C, D, H, W] -> dst [B, C, D, H, W] = reduce_v flip_v(src[v*B + b]), reduction = PTB_RED_*
+ * (the operations of ptb_deaug_reduce), summed in fp32 in view order; written in the source type (fp16 / bf16: round to nearest
+ * even). */
+int ptb_volume_mirror_reduce(const void* src, int dtype, void* dst, int nviews, const int* masks, int reduction, int B, int C, int D,
+                             int H, int W, ptb_stream_t stream);
+/* ptb_volume_mirror_accumulate == ptb_volume_mirror_reduce followed by ptb_volume_accumulate, bit for bit, in one pass per tile:
+ * tiles DEVICE [V*B, C, d, h, w] of in_dtype (read natively); volume / norm / weight / zs / ys / xs as for ptb_volume_accumulate.
+ * For b = 0..B-1 in order: t = reduce_v flip_v(tiles[v*B + b]) rounded to in_dtype; volume[:, roi] += t * weight (product rounded,
+ * then added); norm[roi] += weight.  Out-of-range rois -> PTB_EBOUNDS. */
+int ptb_volume_mirror_accumulate(float* volume, float* norm, const float* weight, const void* tiles, int in_dtype, int nviews,
+                                 const int* masks, int reduction, const int64_t* zs, const int64_t* ys, const int64_t* xs, int B, int C,
+                                 int d, int h, int w, int D, int H, int W, ptb_stream_t stream);
+/* ptb_volume_split_mirror == ptb_volume_split followed by ptb_volume_mirror (in_is_batch = 1) over the whole call: out DEVICE
+ * [V*B, C, d, h, w] of out_dtype, row v*B + b = view v of tile b.  ptb_volume_split is this with nviews = 1, masks = {0}. */
+int ptb_volume_split_mirror(const void* volume, int in_dtype, int D, int H, int W, int C, const int64_t* zs, const int64_t* ys,
+                            const int64_t* xs, int B, int d, int h, int w, const float* scale, const float* bias, float pad_value,
+                            int nviews, const int* masks, int out_dtype, void* out, ptb_stream_t stream);
+
 /* ---- {fliplr,flipud,flips,d2,d4}_image_deaugment (inference/tta.py:287-316,344-365,442-467,503-524) -------------
  * in [V*B, C, H, W] (chunk-major: rows [k*B,(k+1)*B) are view k), views HOST int[V] = inverse transform of each chunk.
  * out [B, C, H, W] = reduce_k view_k(in[k*B + b]).  V <= 8.  Transposing views require H == W. */

@@ -14,6 +14,8 @@ import numpy as np
 import torch
 
 from .. import _native as N
+from . import _host
+from .tta_3d import flip_view, mirror_views
 
 __all__ = ["VolumeSlicer", "VolumeMerger"]
 
@@ -103,7 +105,7 @@ class VolumeSlicer:
         return volume[self.orignal_image_roi]
 
     # ------------------------------------------------------------------ device-side split
-    def split_device(self, volume: torch.Tensor, indices=None, scale=None, bias=None, value=0, dtype=torch.float32) -> torch.Tensor:
+    def split_device(self, volume: torch.Tensor, indices=None, scale=None, bias=None, value=0, dtype=torch.float32, mirror=None) -> torch.Tensor:
         """Model input for the tiles ``indices`` straight from a volume that already lives in HBM, as one HIP launch per 64 tiles.
 
         Equals ``np.stack([np.moveaxis(t, -1, 0) if t.ndim == 4 else t[None] for t in self.split(volume, value)])[indices]`` as a
@@ -112,8 +114,13 @@ class VolumeSlicer:
         float16, bfloat16 or float32; ``indices``: None (all tiles), a slice, or a sequence of tile indices; ``scale`` / ``bias``:
         per-channel sequences (both or neither); ``value``: constant border, cast to the volume's dtype first (as ``np.pad``
         does); ``dtype``: torch.float32, torch.float16 or torch.bfloat16 (round to nearest even).  Returns ``[n, C, d, h, w]``.
+
+        ``mirror``: None, or a mirror string of ``tta_3d`` ("d" .. "dhw"): the result is then
+        ``mirror_volume_augment(split_device(...), mirror)``, ``[V*n, C, d, h, w]`` chunk-major, written by the same launches (each
+        staged chunk is stored once per view).
         """
         N.require_device(volume, "VolumeSlicer.split_device")
+        views = (0,) if mirror is None else mirror_views(mirror)
         code = N.VOLUME_DTYPE_CODES.get(volume.dtype)
         if code is None:
             raise NotImplementedError(f"split_device takes a uint8, int16, uint16, float16, bfloat16 or float32 volume, got {volume.dtype}")
@@ -135,7 +142,7 @@ class VolumeSlicer:
             boxes = [self.bbox_crops[int(i)] for i in np.asarray(indices, dtype=np.int64).reshape(-1)]
         d, h, w = (int(s) for s in self.tile_size)
         n = len(boxes)
-        out = torch.empty((n, channels, d, h, w), device=volume.device, dtype=dtype)
+        out = torch.empty((len(views) * n, channels, d, h, w), device=volume.device, dtype=dtype)
         if n == 0:
             return out
         starts = np.ascontiguousarray(np.array([[s.start for s in box] for box in boxes], dtype=np.int64).T)
@@ -151,10 +158,16 @@ class VolumeSlicer:
         D, H, W = (int(s) for s in self.volume_shape)
         lib = N.load()
         with N.on_device(volume.device):
-            rc = lib.ptb_volume_split(volume.data_ptr(), code, D, H, W, channels, starts[0].ctypes.data_as(N._i64p),
-                                      starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), n, d, h, w,
-                                      fa[0] if fa else None, fa[1] if fa else None, pad, out_code, out.data_ptr(),
-                                      N.stream_ptr(volume.device))
+            if mirror is None:
+                rc = lib.ptb_volume_split(volume.data_ptr(), code, D, H, W, channels, starts[0].ctypes.data_as(N._i64p),
+                                          starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), n, d, h, w,
+                                          fa[0] if fa else None, fa[1] if fa else None, pad, out_code, out.data_ptr(),
+                                          N.stream_ptr(volume.device))
+            else:
+                rc = lib.ptb_volume_split_mirror(volume.data_ptr(), code, D, H, W, channels, starts[0].ctypes.data_as(N._i64p),
+                                                 starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), n, d, h, w,
+                                                 fa[0] if fa else None, fa[1] if fa else None, pad, len(views), N.int_array(views),
+                                                 out_code, out.data_ptr(), N.stream_ptr(volume.device))
         N.bump()
         N.check(rc, "VolumeSlicer.split_device")
         return out
@@ -242,11 +255,14 @@ class VolumeMerger:
         self.volume = torch.zeros((channels, *shape), device=device, dtype=dtype)
         self.norm_mask = torch.zeros((1, *shape), device=device, dtype=dtype)
 
-    def _accumulate(self, batch, rois):
+    def _check_accumulators(self, what):
         for t in (self.volume, self.norm_mask, self.weight):
-            N.require_device(t, "VolumeMerger")
+            N.require_device(t, what)
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError("VolumeMerger accumulators must be contiguous float32 tensors")
+
+    def _accumulate(self, batch, rois):
+        self._check_accumulators("VolumeMerger")
         d, h, w = (int(s) for s in self.weight.shape[1:])
         if tuple(batch.shape[1:]) != (self.channels, d, h, w):
             raise RuntimeError(f"tile batch of shape {tuple(batch.shape)} does not match [B, {self.channels}, {d}, {h}, {w}]")
@@ -271,6 +287,45 @@ class VolumeMerger:
         if len(batch) != len(rois):
             raise ValueError("Number of images in batch does not correspond to number of coordinates")
         self._accumulate(batch.detach().to(device=self.volume.device, dtype=torch.float32).contiguous(), rois)
+
+    def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean"):
+        """Fused ``integrate_batch(mirror_volume_deaugment(batch, mirror, reduction), rois)``, bit for bit.
+
+        ``batch``: the model output for the ``mirror_volume_augment``-ed tiles, ``[V*B, C, d, h, w]`` chunk-major, float32, float16 or
+        bfloat16, on the merger's CUDA device (read as it is, no float32 copy; unlike ``integrate_batch``, a host batch is refused
+        rather than uploaded -- de-augment it with ``mirror_volume_deaugment`` first).  One launch per tile un-flips the V views, reduces them in fp32 in view
+        order (a half-precision result is rounded to the batch's dtype, as ``mirror_volume_deaugment`` returns it) and blends.  A
+        reduction that cannot be fused (a callable or None) raises ValueError."""
+        from .tta import _reduction_code
+
+        views = mirror_views(mirror)
+        if len(batch) != len(views) * len(rois):
+            raise ValueError("Number of images in batch does not correspond to number of coordinates x views")
+        code = _reduction_code(reduction)
+        if code is None:
+            raise ValueError(f"reduction={reduction!r} cannot be fused into the tile merge")
+        self._check_accumulators("VolumeMerger")
+        dtype = N.DTYPE_CODES.get(batch.dtype)
+        if dtype is None:
+            raise NotImplementedError(f"integrate_batch_deaugment takes float32, float16 or bfloat16 batches, got {batch.dtype}")
+        N.require_device(batch, "VolumeMerger.integrate_batch_deaugment")
+        d, h, w = (int(s) for s in self.weight.shape[1:])
+        if tuple(batch.shape[1:]) != (self.channels, d, h, w):
+            raise RuntimeError(f"tile batch of shape {tuple(batch.shape)} does not match [V*B, {self.channels}, {d}, {h}, {w}]")
+        if batch.device != self.volume.device:
+            raise ValueError(f"integrate_batch_deaugment: batch is on {batch.device}, the accumulators on {self.volume.device}")
+        batch = batch.detach().contiguous()
+        starts = _roi_starts(rois, (d, h, w))
+        D, H, W = (int(s) for s in self.volume.shape[1:])
+        lib = N.load()
+        dev = self.volume.device
+        with N.on_device(dev):
+            rc = lib.ptb_volume_mirror_accumulate(self.volume.data_ptr(), self.norm_mask.data_ptr(), self.weight.data_ptr(), batch.data_ptr(),
+                                                  dtype, len(views), N.int_array(views), code, starts[0].ctypes.data_as(N._i64p),
+                                                  starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), len(rois),
+                                                  self.channels, d, h, w, D, H, W, N.stream_ptr(dev))
+        N.bump()
+        N.check(rc, "VolumeMerger.integrate_batch_deaugment")
 
     def merge(self) -> torch.Tensor:
         """``volume / norm_mask`` as a new tensor (no eps clamp: never-covered voxels are NaN)."""
@@ -351,6 +406,21 @@ class HostBackedVolumeMerger(VolumeMerger):
         if len(batch) != len(rois):
             raise ValueError("Number of images in batch does not correspond to number of coordinates")
         self._blend(batch.to(device=self.volume.device, dtype=self.volume.dtype), rois)
+
+    def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean"):
+        """``VolumeMerger.integrate_batch_deaugment`` in torch ops: the views un-flipped and reduced in the batch's dtype
+        (``_host.reduce_stack``), then blended by ``integrate_batch``."""
+        from .tta import _reduction_code
+
+        views = mirror_views(mirror)
+        if len(batch) != len(views) * len(rois):
+            raise ValueError("Number of images in batch does not correspond to number of coordinates x views")
+        code = _reduction_code(reduction)
+        if code is None:
+            raise ValueError(f"reduction={reduction!r} cannot be fused into the tile merge")
+        batch = batch.to(device=self.volume.device)
+        stack = torch.stack([flip_view(c, m) for c, m in zip(torch.chunk(batch, len(views)), views)])
+        self.integrate_batch(_host.reduce_stack(stack, code), rois)
 
     def merge(self) -> torch.Tensor:
         return self.volume / self.norm_mask
