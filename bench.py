@@ -21,24 +21,33 @@ All four produce bit-identical results (tests/test_tiles_gpu.py).
 `value` is measured on the model-output pool exactly as torch's allocator first hands it out: a ramp until the step time has
 settled, the W warm-up steps, and EXACTLY K timed steps `--repeats` times (value = the median run).  Which device memory backs
 the 12 GB decides up to 10-15 % of the loop's speed on some boxes (tools/placement_map.py); what a process that owns its buffers
-could gain by choosing among `--placement-tries` candidate pools is measured AFTER the headline and reported separately as
-`config.best_placement` (never `value`).
+could gain by choosing among `--placement-tries` candidate pools is measured AFTER the headline (with `--full`) and reported
+separately as `config.best_placement` (never `value`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up, ramp and warm-up, the timed steps, `--dump-outputs`, the JSON line.
+`--full` adds everything else the benchmark measures or checks, all of it after the headline was timed: the timed output against
+the plain merger (`config.parity`, a mismatch fails the run), the secondary timings of the API variants (`config.variants`), the
+roofline block with this box's read ceiling, the placement search (`config.best_placement`), the other BASELINE configs and the
+end-to-end loops on this GPU (`config.secondary`) and the CPU baselines (`cpu_baseline`); for N > 1 the parity of every rank's band
+before timing and the exchange's cost (`config.sharded`).  `--no-variants`, `--no-secondary`, `--no-cpu-baseline` and
+`--placement-tries 1` leave single parts of it out.
 
 `--dump-outputs DIR` (one GPU) writes what the last timed step returned -- the merged map, as a fixed seeded sample of its values --
 to DIR/merged_sample.npy, so that two builds run with the same arguments can be compared output for output.
 
 N > 1 runs one rank per GPU over RCCL; started without WORLD_SIZE in the environment, `python bench.py --gpus N` launches itself
-under torch.distributed.run (127.0.0.1, a free port).  Before anything is timed every rank checks the rows it owns against the
-SINGLE-DEVICE merge of the same (per-tile seeded) model outputs; the JSON line carries `config.sharded.parity_max_abs_diff` and
-`rccl_ranks` (ranks whose exchange is the library's own RCCL communicator), and a parity failure fails the run.  The 361 tiles of ONE image are sharded over the
+under torch.distributed.run (127.0.0.1, a free port).  With `--full`, before anything is timed every rank checks the rows it owns
+against the SINGLE-DEVICE merge of the same (per-tile seeded) model outputs; the JSON line carries `config.sharded.parity_max_abs_diff`
+and `rccl_ranks` (ranks whose exchange is the library's own RCCL communicator), and a parity failure fails the run.  The 361 tiles of ONE image are sharded over the
 ranks as contiguous tile ranges (45 / 46 tiles each at N = 8), neighbouring ranks exchange their 256-row halo rectangles
 point-to-point over xGMI (one ncclGroup per image on the library's own communicator) and every rank merges its own band (strong
 scaling: total work per step is fixed).  Steps are pipelined (`merge_async`): image i's exchange runs beside image i+1's kernels;
-the K timed steps are K whole images, the last one completed inside the timed region.  `config.sharded` reports, per rank, the
-compute-only time, the bytes per link and the exchange left exposed in pipelined and in latency mode (PTB_BENCH_SHARDED_MODE=sync
-makes latency mode the headline).  Rank 0 prints one JSON line.
+the K timed steps are K whole images, the last one completed inside the timed region.  `config.sharded` names the mode, the
+exchange and the partition; with `--full` it also reports, per rank, the compute-only time, the bytes per link and the exchange
+left exposed in pipelined and in latency mode (PTB_BENCH_SHARDED_MODE=sync makes latency mode the headline).  Rank 0 prints one
+JSON line.
 """
 import argparse
 import gc
@@ -66,13 +75,17 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the checks and side measurements: parity with the plain "
+                    "merger, API variants, roofline and read ceiling, placement search, secondary configs, CPU baselines (N > 1: band "
+                    "parity before timing, exchange cost)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg5"], help="cfg2 (default): the headline tiled + d4 merge (BASELINE "
                     "configs[1], sharded over the ranks = configs[2]); cfg5: multiscale 0.75/1.0/1.25 + fliplr TTA, gmean, on 4096x4096 "
                     "(BASELINE configs[4]), output row strips over the ranks")
     ap.add_argument("--chunk-rows", type=int, default=0, help="override the view-kernel chunk rows (16|32|64)")
     ap.add_argument("--memset-accumulators", action="store_true", help="A/B: zero the accumulators with a memset each step instead of first-touch stores")
-    ap.add_argument("--placement-tries", type=int, default=8, help="candidate placements of the model-output pool tried in the untimed set-up (1 = take the first)")
+    ap.add_argument("--placement-tries", type=int, default=8, help="with --full: candidate placements of the model-output pool tried after the "
+                    "headline (1 = no search)")
     ap.add_argument("--tunable", action="append", default=[], help="key=value passed to ptb_set_tunable (A/B experiments)")
     ap.add_argument("--unplanned", action="store_true", help="A/B: TileMerger without crops= (lazily built norm_mask + separate merge pass)")
     ap.add_argument("--no-defer", action="store_true", help="A/B: planned merger without deferred band merging (accumulators in HBM)")
@@ -82,8 +95,8 @@ def parse():
     ap.add_argument("--ramp-max-ms", type=float, default=4000.0)
     ap.add_argument("--repeats", type=int, default=5, help="the K timed steps are run this many times (each run bracketed by barrier + "
                     "synchronize); `value` is the MEDIAN run, all runs are listed in config.repeat_ms_per_step")
-    ap.add_argument("--no-secondary", action="store_true", help="skip config.secondary (cfg4 losses, cfg5 multiscale, Lovasz on this GPU)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the secondary timings (no-defer / unplanned / literal drop-in sequence)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip config.secondary (cfg4 losses, cfg5 multiscale, Lovasz on this GPU)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the secondary timings (no-defer / unplanned / literal drop-in sequence)")
     ap.add_argument("--defer-rows", type=int, default=0, help="rows of the image merged per deferred launch (0: the library default, 1024)")
     ap.add_argument("--diag", action="store_true", help="print per-step / per-call timing diagnostics to stderr")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned in its "
@@ -143,7 +156,7 @@ def cpu_baseline(slicer, max_seconds=25.0):
     """The reference's own CPU data flow (oracle/torch_chain.py: chunk + inverse views + stack + mean, sequential slice
     `+=`, image / norm_mask -- tta.py:442-467, tiles.py:321-346 -- as multi-threaded torch-CPU ops on all physical cores of this
     host) over the tiles of ONE whole image (same geometry, same batch size); stops early after `max_seconds` and extrapolates
-    the remaining batches, so the default bench run stays bounded on a slow host.  kind = "port": the reference package itself
+    the remaining batches, so a `--full` run stays bounded on a slow host.  kind = "port": the reference package itself
     does not exist on the GPU box; in the build container the same chain was timed next to the unmodified reference
     (BASELINE.md / DESIGN.md section 5)."""
     from oracle import torch_chain as TC
@@ -619,7 +632,7 @@ def main_cfg5(args):
                          "frac": round(my_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
                          "algorithmic_bytes_per_launch": my_bytes, "avg_launch_ms": round(ms_per_step, 5)},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import torch_chain as TC
 
             cores, _logical, model = TC.host_description()
@@ -809,12 +822,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- N > 1: parity before anything is timed.  This rank's band of ONE synchronously merged image against the rows the plain
+    # ---- N > 1, --full: parity before anything is timed.  This rank's band of ONE synchronously merged image against the rows the plain
     # single-device merger produces for the same model outputs (every tile that touches the owned rows, regenerated from its seed,
     # integrated in the single-device order).  "pixel_rows" is bit-identical by construction; tile partitions add the neighbours'
     # partial sums in another association: a few 1e-7 on O(1) values, against the 1e-5 of BASELINE.json.
     parity = None
-    if sharded:
+    if sharded and args.full:
         merger.reset()
         for t, c in zip(batch_tensors, batch_crops):
             merger.integrate_batch_deaugment(t, c, group="d4", reduction="mean")
@@ -951,11 +964,12 @@ def main():
     runs = [timed_run(step, args.steps, keep=last_out if args.dump_outputs and i == n_runs - 1 else None) for i in range(n_runs)]
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, {"merged": last_out.pop()})
+    # ---- the headline is measured; what follows up to the JSON line runs with --full only, apart from config.sharded's description.
     # ---- N = 1: the timed path's OUTPUT, checked right after the timed runs against the plain HIP merger (accumulate now, divide in
     # merge(): the reference's data flow, tiles.py:321-346, pinned to the oracle and to the reference's goldens by the -m gpu suite) on
     # the same model outputs: every value of the merged map, not a digest.  Planned and deferred mergers are bit-identical to it.
     parity1 = None
-    if not sharded:
+    if args.full and not sharded:
         timed_out = step()
         plain = TileMerger(slicer.target_shape, CHANNELS, slicer.weight, device=dev, auto_plan=False)
         for t, c in zip(batch_tensors, batch_crops):
@@ -971,9 +985,22 @@ def main():
     elapsed, region_event_ms = runs[order[len(order) // 2]]    # the median run is the reported one
     repeat_ms = [round(r[0] / args.steps * 1e3, 4) for r in runs]
 
-    # ---- N > 1: what the exchange costs, measured (the same fields tools/shard_sim.py predicts from a one-GPU box)
+    # ---- N > 1: how the exchange ran; with --full also what it costs, measured (the same fields tools/shard_sim.py predicts from a
+    # one-GPU box)
     sharded_report = None
     if sharded and world > 1:
+        from pytorch_toolbelt_amd import parallel as _par
+
+        rccl_error = parity["rccl_error"] if parity is not None else _par.last_exchange_error()
+        sharded_report = {
+            **(parity or {}),
+            "mode": "pipelined (merge_async: image i's exchange under image i+1's kernels)" if pipelined else "latency (merge() joins the exchange inside the image)",
+            "exchange": ("ptb_halo_exchange: one ncclGroup per image on the library's own RCCL communicator" if merger.exchange is not None else
+                         "torch.distributed.batch_isend_irecv" + ("" if backend == "nccl" and os.environ.get("PTB_BENCH_EXCHANGE", "auto") == "torch" else
+                                                                 " (the library's RCCL communicator was NOT used: " + (rccl_error or f"backend {backend}") + ")")),
+            "partition": partition,
+        }
+    if sharded and world > 1 and args.full:
         def sync_step():
             merger.reset()
             for t, c in zip(batch_tensors, batch_crops):
@@ -1025,13 +1052,7 @@ def main():
         dist.all_gather_object(everyone, mine)
         ms_now = elapsed / args.steps * 1e3
         slowest_compute = max(e["compute_only_ms"] for e in everyone)
-        sharded_report = {
-            **parity,
-            "mode": "pipelined (merge_async: image i's exchange under image i+1's kernels)" if pipelined else "latency (merge() joins the exchange inside the image)",
-            "exchange": ("ptb_halo_exchange: one ncclGroup per image on the library's own RCCL communicator" if merger.exchange is not None else
-                         "torch.distributed.batch_isend_irecv" + ("" if backend == "nccl" and os.environ.get("PTB_BENCH_EXCHANGE", "auto") == "torch" else
-                                                                 " (the library's RCCL communicator was NOT used: " + (parity["rccl_error"] or f"backend {backend}") + ")")),
-            "partition": partition,
+        sharded_report.update({
             "pipelined_ms_per_image": round(ms_now if pipelined else other_ms, 4),
             "latency_mode_ms_per_image": round(other_ms if pipelined else ms_now, 4),
             "slowest_rank_compute_only_ms": round(slowest_compute, 4),
@@ -1042,7 +1063,7 @@ def main():
                     "steps with the exchange stubbed out; bytes per link = the partial-sum rectangles one rank sends to / receives from one "
                     "neighbour (each pair of GPUs has its own xGMI link, both directions at once); tools/shard_sim.py predicts the same "
                     "fields from one GPU + a link model (profiles/r04_shard_sim.txt)",
-        }
+        })
 
     if sharded_report is None and parity is not None:      # (PTB_BENCH_FORCE_SHARDED with one rank)
         sharded_report = parity
@@ -1050,7 +1071,7 @@ def main():
     # ---- secondary timings (single GPU): what each API extension of the headline configuration buys, driver-visible
     variants = None
     region_bytes_all = VIEWS * n_tiles * CHANNELS * TILE * TILE * 4 + CHANNELS * 5120 * 5120 * 4   # 12 532 580 352 B
-    if not sharded and not args.no_variants:
+    if args.full and not sharded and not args.no_variants:
         from pytorch_toolbelt_amd.inference import tta as _tta
 
         from pytorch_toolbelt_amd.inference import tiles as _tiles
@@ -1166,46 +1187,48 @@ def main():
 
     # ---- dominant-kernel roofline: ONE HIP-event pair (same stream) around the back-to-back run of full 8-tile launches
     # of a step (per-launch event pairs would insert a marker packet between kernels and inflate every launch by a few
-    # microseconds); averaged over several steps.  The trailing partial batch and the merge are outside the bracket.
-    n_full = sum(1 for c in batch_crops if len(c) == BATCH)
-    assert all(len(c) == BATCH for c in batch_crops[:n_full])
-    spans = []
-    for _ in range(max(3, min(10, args.steps))):
-        merger.reset()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for t, c in zip(batch_tensors[:n_full], batch_crops[:n_full]):
-            merger.integrate_batch_deaugment(t, c, group="d4", reduction="mean")
-        e1.record()
-        for t, c in zip(batch_tensors[n_full:], batch_crops[n_full:]):
-            merger.integrate_batch_deaugment(t, c, group="d4", reduction="mean")
-        merger.merge()
-        torch.cuda.synchronize()
-        spans.append(e0.elapsed_time(e1))
-    launch_ms = float(np.median(spans)) / max(n_full, 1) if n_full else float("nan")
-    bytes_per_tile = VIEWS * CHANNELS * TILE * TILE * 4          # 8 views x C x T x 4 B read per tile
-    bytes_per_launch = bytes_per_tile * BATCH
-    n_bands = len(merger._bands.bands) if (not sharded and deferred) else 0
-    if n_bands:
-        # deferred: the band-group launches of an image ARE the region (they read every model output once and write the merged
-        # map once) and nothing else runs on the stream: one HIP-event pair around the K timed steps / (K x launches per image)
-        launch_ms = region_event_ms / (args.steps * n_bands)
-        bytes_per_launch = (VIEWS * n_tiles * CHANNELS * TILE * TILE * 4 + CHANNELS * 5120 * 5120 * 4) // n_bands
-    elif sharded:
-        # one rank's share of the image: its tiles read once + its owned rows written once, over the whole step (kernels, the
-        # partial-sum exchange and the completion of the shared rows) -- the per-rank effective rate, not a single kernel's
-        owned = merger.owned_rows or (0, 0)
-        bytes_per_launch = bytes_per_tile * len(crops) + CHANNELS * (owned[1] - owned[0]) * 5120 * 4
-        launch_ms = elapsed / args.steps * 1e3
-    elif not sharded and planned:
-        # the planned kernel also writes the region's output (+ C x 5120 x 5120 x 4 B per image): the launch's
-        # share of the whole region's algorithmic bytes, 12 532 580 352 B x 8 / 361
-        bytes_per_launch += CHANNELS * 5120 * 5120 * 4 * BATCH // n_tiles
-    achieved = bytes_per_launch / (launch_ms * 1e-3) / 1e9
+    # microseconds); averaged over several steps.  The trailing partial batch and the merge are outside the bracket.  --full only, like
+    # the box's read ceiling and the placement search below.
+    if args.full:
+        n_full = sum(1 for c in batch_crops if len(c) == BATCH)
+        assert all(len(c) == BATCH for c in batch_crops[:n_full])
+        spans = []
+        for _ in range(max(3, min(10, args.steps))):
+            merger.reset()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for t, c in zip(batch_tensors[:n_full], batch_crops[:n_full]):
+                merger.integrate_batch_deaugment(t, c, group="d4", reduction="mean")
+            e1.record()
+            for t, c in zip(batch_tensors[n_full:], batch_crops[n_full:]):
+                merger.integrate_batch_deaugment(t, c, group="d4", reduction="mean")
+            merger.merge()
+            torch.cuda.synchronize()
+            spans.append(e0.elapsed_time(e1))
+        launch_ms = float(np.median(spans)) / max(n_full, 1) if n_full else float("nan")
+        bytes_per_tile = VIEWS * CHANNELS * TILE * TILE * 4          # 8 views x C x T x 4 B read per tile
+        bytes_per_launch = bytes_per_tile * BATCH
+        n_bands = len(merger._bands.bands) if (not sharded and deferred) else 0
+        if n_bands:
+            # deferred: the band-group launches of an image ARE the region (they read every model output once and write the merged
+            # map once) and nothing else runs on the stream: one HIP-event pair around the K timed steps / (K x launches per image)
+            launch_ms = region_event_ms / (args.steps * n_bands)
+            bytes_per_launch = (VIEWS * n_tiles * CHANNELS * TILE * TILE * 4 + CHANNELS * 5120 * 5120 * 4) // n_bands
+        elif sharded:
+            # one rank's share of the image: its tiles read once + its owned rows written once, over the whole step (kernels, the
+            # partial-sum exchange and the completion of the shared rows) -- the per-rank effective rate, not a single kernel's
+            owned = merger.owned_rows or (0, 0)
+            bytes_per_launch = bytes_per_tile * len(crops) + CHANNELS * (owned[1] - owned[0]) * 5120 * 4
+            launch_ms = elapsed / args.steps * 1e3
+        elif not sharded and planned:
+            # the planned kernel also writes the region's output (+ C x 5120 x 5120 x 4 B per image): the launch's
+            # share of the whole region's algorithmic bytes, 12 532 580 352 B x 8 / 361
+            bytes_per_launch += CHANNELS * 5120 * 5120 * 4 * BATCH // n_tiles
+        achieved = bytes_per_launch / (launch_ms * 1e-3) / 1e9
 
     # ---- what this box's memory system gives a pure read stream over the same buffers (boxes of one pool differ by ~10 %)
     box_ceiling = None
-    if not use_dist:
+    if args.full and not use_dist:
         sink = torch.zeros(4, device=dev)
         lib = N.load()
 
@@ -1238,9 +1261,9 @@ def main():
     # choosing among candidate pools at start-up (pytorch_toolbelt_amd/placement.py) is measured here, afterwards, as
     # config.best_placement: candidate pools are allocated one ~36 GB region apart, a few steps are run on each, the fastest is
     # kept and timed with the same K steps.  --placement-tries 1 skips it.
-    placement = {"max_tries": 1, "ms_per_step_by_candidate": [], "chosen": 0}
+    placement = {"max_tries": 1, "ms_per_step_by_candidate": [], "chosen": 0} if args.full else None
     best_placement = None
-    if args.placement_tries > 1 and not use_dist:
+    if args.full and args.placement_tries > 1 and not use_dist:
         search_steps = 0
 
         def run_ms(tensors, k):
@@ -1283,7 +1306,7 @@ def main():
 
     traffic, traffic_when = None, ""
     tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
+    if args.full and os.path.exists(tpath):
         try:
             tj = json.load(open(tpath))
             traffic = tj.get("band_plan_d4_bytes_per_launch" if n_bands else "view_accum_d4_bytes_per_launch")
@@ -1383,16 +1406,16 @@ def main():
                                          "outputs on THIS box, measured in this run",
                 "algorithmic_bytes_per_launch": bytes_per_launch,
                 "avg_launch_ms": round(launch_ms, 5),
-            },
+            } if args.full else None,
         }
-        if world == 1 and not use_dist and not args.no_secondary:     # (before the CPU baseline: the GPU is still at its clocks)
+        if args.full and world == 1 and not use_dist and not args.no_secondary:     # (before the CPU baseline: the GPU is still at its clocks)
             del batch_tensors, _keep
             torch.cuda.empty_cache()
             try:
                 line["config"]["secondary"] = secondary_workloads(dev, with_cpu=not args.no_cpu_baseline)
             except Exception as exc:  # noqa: BLE001  (the headline line must survive a failing side measurement)
                 line["config"]["secondary"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(slicer)
     if use_dist:
         dist.barrier()

@@ -23,7 +23,7 @@ def _line(out):
 
 
 def test_single_gpu_line():
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "1", "--no-secondary",
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--repeats", "1", "--no-secondary",
                           "--no-cpu-baseline", "--no-variants", "--placement-tries", "1", "--ramp-max-ms", "300"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert run.returncode == 0, run.stderr[-3000:]
@@ -41,6 +41,22 @@ def test_single_gpu_line():
     assert par["bit_identical"] is True and par["max_abs_diff_vs_plain_merger"] == 0.0 and par["values_checked"] == 4 * 5120 * 5120
 
 
+def test_plain_run_measures_the_headline_only():
+    """Without --full a run sets up, warms up, times its steps and prints the line; none of what --full adds after the headline
+    (parity with the plain merger, API variants, roofline and read ceiling, placement search, secondary configs, CPU baseline) runs."""
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "1", "--ramp-max-ms", "300"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert run.returncode == 0, run.stderr[-3000:]
+    d = _line(run.stdout)
+    assert all(k in d for k in CONTRACT) and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "MP/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and "cfg2" in d["config"]["workload"]
+    assert abs(d["value"] - 25.0 / d["ms_per_step"] * 1e3) / d["value"] < 0.01 and 5000.0 < d["value"] < 16000.0
+    c = d["config"]
+    assert c["first_allocation"]["ms_per_step"] == d["ms_per_step"] and len(c["repeat_ms_per_step"]) == 1
+    assert c["parity"] is None and c["variants"] is None and c["placement"] is None and c["best_placement"] is None and c["sharded"] is None
+    assert "secondary" not in c and "cpu_baseline" not in d and d["roofline"] is None
+
+
 def test_dump_outputs_is_the_same_from_run_to_run(tmp_path):
     """--dump-outputs DIR: what the timed path returned in its last timed step -- the merged 4 x 5120 x 5120 map, as the values at a
     fixed, seeded sample of its positions -- in float32, 64 MB at most.  The inputs are seeded, so another run (here with another
@@ -48,7 +64,7 @@ def test_dump_outputs_is_the_same_from_run_to_run(tmp_path):
     dumps = []
     for steps in (1, 3):
         out = tmp_path / f"steps{steps}"
-        run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--repeats", "1",
+        run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps), "--warmup", "1", "--repeats", "1",
                               "--no-secondary", "--no-cpu-baseline", "--no-variants", "--placement-tries", "1", "--ramp-max-ms", "300",
                               "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert run.returncode == 0, run.stderr[-3000:]
@@ -65,8 +81,8 @@ def test_dump_outputs_is_the_same_from_run_to_run(tmp_path):
 def test_two_ranks_on_one_gpu_take_the_sharded_pipelined_path():
     env = dict(os.environ, PTB_BENCH_SAME_GPU="1", PTB_BENCH_BACKEND="gloo")
     run = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1"],
-                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1",
+                          "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert run.returncode == 0, run.stderr[-3000:]
     d = _line(run.stdout)
     assert all(k in d for k in CONTRACT) and d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "strong"
@@ -86,8 +102,8 @@ def test_gpus_2_launches_itself_and_checks_its_band_against_the_single_device_me
     exchange (none under gloo, and the line says why)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PTB_BENCH_SAME_GPU="1", PTB_BENCH_BACKEND="gloo")
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1"],
-                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1",
+                          "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert run.returncode == 0, run.stderr[-3000:]
     assert "launching" in run.stderr and "torch.distributed.run" in run.stderr
     d = _line(run.stdout)
@@ -97,3 +113,18 @@ def test_gpus_2_launches_itself_and_checks_its_band_against_the_single_device_me
     assert sh["parity_values_checked"] == 4 * 5120 * 5120, "the two bands together are the whole merged map"
     assert sh["rccl_ranks"] == 0 and "NOT used" in sh["exchange"]
     assert len(sh["per_rank"]) == 2
+
+
+def test_plain_two_rank_run_names_its_exchange_without_the_parity_pass():
+    """`python bench.py --gpus 2` without --full: the sharded, pipelined steps are timed and config.sharded says how the exchange ran;
+    the band parity before timing and the exchange's cost measurements are --full's."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(PTB_BENCH_SAME_GPU="1", PTB_BENCH_BACKEND="gloo")
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1"],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    assert run.returncode == 0, run.stderr[-3000:]
+    d = _line(run.stdout)
+    assert all(k in d for k in CONTRACT) and d["n_gpus"] == 2 and d["steps"] == 2 and d["value"] > 0
+    sh = d["config"]["sharded"]
+    assert sh["mode"].startswith("pipelined") and "NOT used" in sh["exchange"] and sh["partition"] == "tiles"
+    assert "parity_max_abs_diff" not in sh and "per_rank" not in sh and "sharded parity" not in run.stderr

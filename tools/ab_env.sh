@@ -3,11 +3,10 @@
 VAR=$1; VALS=$2; ROUNDS=${3:-2}
 for r in $(seq $ROUNDS); do
   for v in $VALS; do
-    env $VAR=$v python bench.py --no-variants --no-cpu-baseline --repeats 3 2>/dev/null | tail -1 > /tmp/ab_line.json
-    python - "$VAR" "$v" <<'PY'
+    env $VAR=$v python bench.py --full --no-variants --no-cpu-baseline --repeats 3 2>/dev/null | tail -1 | python -c "
 import json, sys
-d = json.loads(open("/tmp/ab_line.json").read())
-print(f"{sys.argv[1]}={sys.argv[2]}: {d['ms_per_step']} ms  frac {d['roofline']['frac']}  of box read ceiling {d['roofline'].get('frac_of_box_read_ceiling')}")
-PY
+d = json.loads(sys.stdin.read())
+print(f\"{sys.argv[1]}={sys.argv[2]}: {d['ms_per_step']} ms  frac {d['roofline']['frac']}  of box read ceiling {d['roofline'].get('frac_of_box_read_ceiling')}\")
+" "$VAR" "$v"
   done
 done

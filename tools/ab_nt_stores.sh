@@ -6,7 +6,7 @@ for r in 1 2; do
 for L in default $PLAIN; do
   if [ $L = default ]; then unset PTB_HIP_LIB; else export PTB_HIP_LIB=$L; fi
   echo "=== round $r lib=$L"
-  timeout 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary < /dev/null 2>&1 | grep metric | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('headline', d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'], d['roofline']['frac'])"
+  timeout 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary < /dev/null 2>&1 | grep metric | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('headline', d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'], d['roofline']['frac'])"
   timeout 200 python tools/bench_cfg5.py < /dev/null 2>&1 | grep -E "cfg5|alone"
   timeout 200 python tools/bench_losses.py < /dev/null 2>&1 | tail -12
 done; done

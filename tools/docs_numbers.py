@@ -53,7 +53,7 @@ def block(path=DEFAULT):
     cb = d.get("cpu_baseline")
     if cb:
         rows.append((f"host CPU, the reference's op chain ({cb['cores']} threads)", "", f"{cb['value']:.1f} MP/s", ""))
-    out = [BEGIN, f"Measured by `python bench.py` on one MI355X, `{os.path.relpath(path, ROOT)}` (this table is generated: `tools/docs_numbers.py`):", "",
+    out = [BEGIN, f"Measured by `python bench.py --full` on one MI355X, `{os.path.relpath(path, ROOT)}` (this table is generated: `tools/docs_numbers.py`):", "",
            "| what | time per 5000 x 5000 image / call | rate | of 8 TB/s |", "|---|---|---|---|"]
     out += [f"| {a} | {b} | {c_} | {e} |" for a, b, c_, e in rows]
     out.append(END)

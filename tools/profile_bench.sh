@@ -7,10 +7,11 @@
 # (only gpurun_out/ travels back, and the raw databases exceed what is copied): usage  bash tools/profile_bench.sh r02
 set -u
 TAG=${1:-r03}
+R="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
 OUT=/root/repo/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
-BENCH="python /root/repo/bench.py --steps 3 --warmup 1 --repeats 1 --ramp-max-ms 600 --no-cpu-baseline --no-secondary"
+BENCH="python $R/bench.py --full --steps 3 --warmup 1 --repeats 1 --ramp-max-ms 600 --no-cpu-baseline --no-secondary"
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run -- $BENCH > $OUT/trace.log 2>&1
 # PTB_PROFILE_LIGHT=1: HBM traffic only (FETCH_SIZE, WRITE_SIZE; a --pmc pass costs ~2 minutes of box time whatever it runs)
 if [ "${PTB_PROFILE_LIGHT:-0}" = "2" ]; then      # kernel trace only (profiles/traffic.json keeps the last PMC passes and their date)

@@ -52,7 +52,7 @@ def main():
     os.makedirs(outdir, exist_ok=True)
     ks = kernels(os.path.join(PROF, "trace", "run_results.db"))
     total = sum(d for v in ks.values() for d, _ in v)
-    lines = [f"# {tag}: rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --repeats 1 --no-cpu-baseline", "",
+    lines = [f"# {tag}: rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 3 --warmup 1 --repeats 1 --no-cpu-baseline", "",
              "| kernel | calls | total ms | avg us | min us | max us | % |", "|---|---|---|---|---|---|---|"]
     for name, v in sorted(ks.items(), key=lambda kv: -sum(d for d, _ in kv[1])):
         d = [x for x, _ in v]
