@@ -69,6 +69,14 @@ typedef void* ptb_stream_t; /* hipStream_t */
  * (torch.autocast): `tta.*_image_deaugment(y)` returns a HALF tensor (inference/tta.py:442-467), `integrate_batch` widens it
  * (inference/tiles.py:334-335).  No effect on PTB_F32 sources. */
 #define PTB_ROUND_SRC 0x100
+/* or-ed into the `in_dtype` of ptb_deaug_reduce_t / ptb_deaug_accumulate_t / ptb_accumulate_planned(2) / ptb_merge_band /
+ * ptb_band_plan_submit(_rank): `in` / `batch` / the tile sources point at channels-last memory, [V*B, th, tw, C] -- element (n, c, i, j)
+ * at ((n * th + i) * tw + j) * C + c, what a model in torch.channels_last returns -- instead of the planar [V*B, C, th, tw].  The strides
+ * keep their meaning (elements between tiles / views: C*th*tw, B*C*th*tw), every output stays planar fp32, and every result has the bits
+ * the planar kernels give on the copied batch.  The layout is part of a band plan's per-image configuration (ptb_band_plan_submit_next
+ * inherits it): a batch whose layout differs from the image's first batch gets PTB_EUNSUPPORTED with nothing launched, like a dtype
+ * change.  With an unknown dtype the result is PTB_EINVAL, as without the flag. */
+#define PTB_SRC_CHANNELS_LAST 0x200
 
 int ptb_version(void);
 /* hipGetErrorString of the last failing HIP call made by this library on this thread ("" if none). */

@@ -33,11 +33,16 @@ IMAGE_DTYPE_CODES = {torch.uint8: U8, torch.uint16: U16, torch.int16: I16}   # i
 # PTB_BORDER_*: OpenCV's border codes (cv2.BORDER_CONSTANT .. cv2.BORDER_REFLECT_101)
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101 = range(5)
 ROUND_SRC = 0x100           # PTB_ROUND_SRC, or-ed into a dtype code: round the reduced value to the (half) source type before blending
+SRC_CHANNELS_LAST = 0x200   # PTB_SRC_CHANNELS_LAST, or-ed into a dtype code: the batch is [V*B, th, tw, C] memory (a model in torch.channels_last)
+DTYPE_MASK = 0xFF           # the PTB_F32 / PTB_F16 / PTB_BF16 part of a dtype code that carries flags
+LAYOUT_DENSE, LAYOUT_CHANNELS_LAST, LAYOUT_OTHER = range(3)
 
 EFRESH = -5
 PTB_EHELD = -6
 PTB_EUNSUPPORTED = -2
-_ERR = {-1: "invalid argument", -2: "unsupported configuration", -3: "HIP launch failed", -4: "tile rectangle outside the accumulator"}
+_ERR = {-1: "invalid argument", -2: "unsupported configuration", -3: "HIP launch failed", -4: "tile rectangle outside the accumulator",
+        -5: "a cell straddles written and never-written accumulator blocks (zero-fill the accumulators, then call without the first-touch bitmap)",
+        -6: "the batch overlaps memory of an earlier batch that a later launch still reads"}
 
 _c_int = ctypes.c_int
 _c_f = ctypes.c_float
@@ -189,6 +194,28 @@ def check(rc, what):
     if rc == -2:
         raise NotImplementedError(f"{what}: {msg}")
     raise RuntimeError(f"{what}: {msg}")
+
+
+def batch_layout(t):
+    """How a 4-D model output lies in memory: ``LAYOUT_DENSE`` (``[N, C, H, W]`` contiguous: what every kernel reads), ``LAYOUT_CHANNELS_LAST``
+    (not that, but contiguous in ``torch.channels_last`` -- element ``(n, c, i, j)`` at ``((n * H + i) * W + j) * C + c``; read where it lies with
+    ``SRC_CHANNELS_LAST``) or ``LAYOUT_OTHER`` (any other strides, tensors that are not 4-D: copied first).  With ``C == 1`` or a 1 x 1 plane
+    the two formats coincide and the tensor counts as dense."""
+    if t.is_contiguous():
+        return LAYOUT_DENSE
+    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
+        return LAYOUT_CHANNELS_LAST
+    return LAYOUT_OTHER
+
+
+def dense_or_channels_last(t):
+    """The batch can be handed to the kernels as it is (see ``batch_layout``)."""
+    return t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
+
+
+def layout_flag(t):
+    """``SRC_CHANNELS_LAST`` for a channels-last batch, 0 for a dense one."""
+    return 0 if t.is_contiguous() else SRC_CHANNELS_LAST
 
 
 def require_device(t, what):

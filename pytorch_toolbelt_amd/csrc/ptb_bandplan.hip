@@ -22,23 +22,7 @@
 
 namespace ptb {
 
-constexpr int PLAN_TILES = 224;   // tiles of one launch group (kernarg: 224 x 16 B + ViewArgs < 4 KiB)
-constexpr int PLAN_CH = 32;       // item rows of the 512-thread instance; plans are created with 32 or 64 rows per item (ptb_set_tunable key 11)
-
-struct BandItem {                 // 64 B = one cache line per workgroup, read with scalar loads only (never copied to registers as a
-    int ax, ay;                   // whole: run-time indexing of a by-value copy would put it in scratch memory); (ax, ay) = origin
-    int cwch;                     // extent: columns | rows << 16  (<= 64 x 64)
-    int ntiles;                   // covering tiles (0: uncovered pixels -> 0 / 0 = NaN like the reference's merge)
-    int partial;                  // 1: write the un-normalised weighted sum (multi-GPU boundary rows) instead of sum / norm
-    int pad[3];
-    unsigned long long cover[MAX_COVER];   // ascending integration order: tile slot | lx << 16 | ly << 32 (item origin in the tile)
-};
-static_assert(sizeof(BandItem) == 64, "BandItem layout");
-
-struct GroupTiles {
-    const void* src[PLAN_TILES];  // view 0, channel 0 of the tile
-    long long vs[PLAN_TILES];     // elements between consecutive views of this tile (its batch size * C * th * tw)
-};
+// (PLAN_TILES, PLAN_CH, BandItem, GroupTiles: ptb_view_device.h -- the channels-last kernels consume the same table and arguments)
 
 // PF (round 5): the loads of covering tile e + 1 are requested -- as they lie in memory: 16 registers for the eight d4 views of a half /
 // bf16 source, 32 for fp32 -- before tile e is transposed, reduced and blended.  Without it a workgroup has nothing in flight while it
@@ -544,8 +528,9 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
                                     const float* weight, ptb_stream_t stream) {
     if (!p || !batch || !merged || !norm_full || !weight || B < 1) return PTB_EINVAL;
     if (!p->dev_items) return PTB_EINVAL;
-    const int dtype_arg = in_dtype;      // (with PTB_ROUND_SRC: part of the image's configuration)
-    in_dtype &= ~PTB_ROUND_SRC;
+    const int dtype_arg = in_dtype;      // (with PTB_ROUND_SRC and PTB_SRC_CHANNELS_LAST: part of the image's configuration)
+    const bool src_cl = (in_dtype & PTB_SRC_CHANNELS_LAST) != 0;
+    in_dtype &= ~(PTB_ROUND_SRC | PTB_SRC_CHANNELS_LAST);
     if (reduction < PTB_RED_SUM || reduction > PTB_RED_LOG1P || in_dtype < PTB_F32 || in_dtype > PTB_BF16) return PTB_EINVAL;
     if (V < 1 || V > MAX_VIEWS || !views) return PTB_EINVAL;
     int nT = 0;
@@ -604,6 +589,14 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
             GroupTiles gt;
             for (size_t s = 0; s < g.tiles.size(); ++s) { gt.src[s] = p->src[g.tiles[s]]; gt.vs[s] = p->vs[g.tiles[s]]; }
             for (size_t s = g.tiles.size(); s < (size_t)PLAN_TILES; ++s) { gt.src[s] = nullptr; gt.vs[s] = 0; }
+            if (src_cl) {   // PTB_SRC_CHANNELS_LAST: the same work-item table, one workgroup per item over all channels
+                cl_launch_plan(a, p->dev_items + g.item_off, gt, g.item_cnt, (hipStream_t)stream);
+                const int rc = check_launch();
+                if (rc != PTB_OK) return rc;
+                ++p->launched;
+                ++launched;
+                continue;
+            }
             // identity view on the prefetching instances: one workgroup per item walks the channels (see band_plan_kernel, ALL)
             a.chan_loop = (V == 1 && codes == CODES_ID && g_band_chan_loop && (in_dtype != PTB_F32 ? g_band_half_pf >= 1 : g_band_half_pf >= 2)) ? 1 : 0;
             const long long blocks = (long long)g.item_cnt * (a.chan_loop ? 1 : p->C);
@@ -637,7 +630,7 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
 extern "C" int ptb_band_plan_submit_next(ptb_band_plan* p, const void* batch, int B, ptb_stream_t stream) {
     if (!p || !batch || B < 1) return PTB_EINVAL;
     if (!p->cfg_set || p->pos + B > p->n) return PTB_EUNSUPPORTED;
-    const int dt = p->cfg_dtype & ~PTB_ROUND_SRC;
+    const int dt = p->cfg_dtype & ~(PTB_ROUND_SRC | PTB_SRC_CHANNELS_LAST);
     const size_t esz = dt == PTB_F32 ? 4 : 2;
     const long long per_tile = (long long)p->C * p->th * p->tw;
     const uintptr_t p0 = reinterpret_cast<uintptr_t>(batch), p1 = p0 + (size_t)((long long)p->cfg_V * B * per_tile) * esz;

@@ -513,4 +513,47 @@ __device__ __forceinline__ void gather_widen(const typename RawOf<LD>::type (&ra
     }
 }
 
+// ------------------------------------------------------------------------------------------------ launch arguments of the band kernels
+// (defined here, not next to band_merge_kernel / band_plan_kernel, because the channels-last kernels of ptb_channels_last.hip consume them unchanged)
+constexpr int BAND_CELLS = 40, BAND_TILES = 48;
+struct BandCell {
+    int ox, oy, w, h;
+    int chunk_end;
+    int ntiles;
+    int tile[MAX_COVER];
+};
+struct BandArgs {
+    BandCell cells[BAND_CELLS];
+    int tile_x[BAND_TILES], tile_y[BAND_TILES];
+    const void* tile_src[BAND_TILES];   // view 0, channel 0 of the tile
+    long long tile_vs[BAND_TILES];      // elements between consecutive views of this tile (its batch size * C * H * W)
+};
+
+constexpr int PLAN_TILES = 224;   // tiles of one launch group (kernarg: 224 x 16 B + ViewArgs < 4 KiB)
+constexpr int PLAN_CH = 32;       // item rows of the 512-thread instance; plans are created with 32 or 64 rows per item (ptb_set_tunable key 11)
+
+struct BandItem {                 // 64 B = one cache line per workgroup, read with scalar loads only (never copied to registers as a
+    int ax, ay;                   // whole: run-time indexing of a by-value copy would put it in scratch memory); (ax, ay) = origin
+    int cwch;                     // extent: columns | rows << 16  (<= 64 x 64)
+    int ntiles;                   // covering tiles (0: uncovered pixels -> 0 / 0 = NaN like the reference's merge)
+    int partial;                  // 1: write the un-normalised weighted sum (multi-GPU boundary rows) instead of sum / norm
+    int pad[3];
+    unsigned long long cover[MAX_COVER];   // ascending integration order: tile slot | lx << 16 | ly << 32 (item origin in the tile)
+};
+static_assert(sizeof(BandItem) == 64, "BandItem layout");
+
+struct GroupTiles {
+    const void* src[PLAN_TILES];  // view 0, channel 0 of the tile
+    long long vs[PLAN_TILES];     // elements between consecutive views of this tile (its batch size * C * th * tw)
+};
+
+// ------------------------------------------------------------------------------------------------ channels-last sources
+// PTB_SRC_CHANNELS_LAST: `a.src` / the tile pointers address [.., th, tw, C] memory (a model output in torch.channels_last); everything
+// else in the arguments means what it means to the planar kernels.  One workgroup per chunk / work item over ALL channels (grid = chunks,
+// not chunks x C); `ch` = the chunk rows the host planned with.  Defined in ptb_channels_last.hip.
+void cl_launch_reduce(const ViewArgs& a, int ntiles_out, int ch, hipStream_t s);                                 // ptb_deaug_reduce_t
+void cl_launch_accum(const ViewArgs& a, const CellArgs& g, int ch, hipStream_t s);                               // ptb_deaug_accumulate_t, ptb_accumulate_planned2
+void cl_launch_band(const ViewArgs& a, const BandArgs& g, int chunks, hipStream_t s);                            // ptb_merge_band (32-row chunks)
+void cl_launch_plan(const ViewArgs& a, const BandItem* items, const GroupTiles& t, int n_items, hipStream_t s);  // ptb_band_plan_submit
+
 }  // namespace ptb

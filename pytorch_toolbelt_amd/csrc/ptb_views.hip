@@ -170,20 +170,7 @@ __global__ __launch_bounds__(CH * 16) void norm_accum_kernel(const ViewArgs a, c
 // accumulator image never exists in HBM: per 8 tiles the incremental path moves 312 MB for 268 MB of model outputs, this one
 // only the outputs and the result.  Same chunk / cover walk and the same gather_reduce as view_accum_kernel (CH = 32), so
 // the fp32 operation order per pixel -- and therefore every bit of the result -- is that of the incremental path.
-constexpr int BAND_CELLS = 40, BAND_TILES = 48;
-struct BandCell {
-    int ox, oy, w, h;
-    int chunk_end;
-    int ntiles;
-    int tile[MAX_COVER];
-};
-struct BandArgs {
-    BandCell cells[BAND_CELLS];
-    int tile_x[BAND_TILES], tile_y[BAND_TILES];
-    const void* tile_src[BAND_TILES];   // view 0, channel 0 of the tile
-    long long tile_vs[BAND_TILES];      // elements between consecutive views of this tile (its batch size * C * H * W)
-};
-
+// (BandCell / BandArgs: ptb_view_device.h -- the channels-last kernels consume the same launch arguments)
 template <int NV, int CODES, int OPK, int LD>
 __global__ __launch_bounds__(512) void band_merge_kernel(const ViewArgs a, const BandArgs g) {
     constexpr int CH = 32;
@@ -667,7 +654,7 @@ static bool aligned_elems(const void* p, int dtype) {  // 4 source elements per 
     return (reinterpret_cast<uintptr_t>(p) & (dtype == PTB_F32 ? 15u : 7u)) == 0;
 }
 
-static int run_plain(ViewArgs& a, int ntiles_out, int mode, hipStream_t s) {
+static int run_plain(ViewArgs& a, int ntiles_out, int mode, hipStream_t s, bool src_cl = false) {
     const bool nonlinear = a.op >= PTB_RED_GMEAN;
     const int nT = mode == MODE_PERVIEW ? 1 : count_transpose(a.nviews, a.codes);
     const bool tr = mode == MODE_PERVIEW ? has_transpose(a.nviews, a.codes) : nT > 0;
@@ -682,6 +669,10 @@ static int run_plain(ViewArgs& a, int ntiles_out, int mode, hipStream_t s) {
     const long long blocks = (long long)ntiles_out * a.C * a.chunks_x * a.chunks_y;
     if (blocks <= 0) return PTB_OK;
     if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
+    if (src_cl) {   // PTB_SRC_CHANNELS_LAST (MODE_REDUCE): the same chunk grid, one workgroup per chunk over all channels, any shape
+        cl_launch_reduce(a, ntiles_out, ch, s);
+        return check_launch();
+    }
     if (!fast) {
         if (mode == MODE_PERVIEW) hipLaunchKernelGGL(view_plain_scalar_kernel<MODE_PERVIEW>, dim3((unsigned)blocks), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(view_plain_scalar_kernel<MODE_REDUCE>, dim3((unsigned)blocks), dim3(256), 0, s, a);
@@ -700,7 +691,7 @@ static int run_plain(ViewArgs& a, int ntiles_out, int mode, hipStream_t s) {
 }
 
 static int launch_group(const ViewArgs& a, const CellArgs& g, const std::vector<Cell>& cells, const Fresh& fr, bool fast, int ch,
-                        hipStream_t s) {
+                        hipStream_t s, bool src_cl = false) {
     const long long blocks = (long long)a.total_chunks * a.C;
     if (blocks <= 0) return PTB_OK;
     if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
@@ -710,6 +701,8 @@ static int launch_group(const ViewArgs& a, const CellArgs& g, const std::vector<
         else if (ch == 64) hipLaunchKernelGGL(norm_accum_kernel<64>, dim3((unsigned)blocks), dim3(1024), 0, s, a, g);
         else if (ch == 32) hipLaunchKernelGGL(norm_accum_kernel<32>, dim3((unsigned)blocks), dim3(512), 0, s, a, g);
         else hipLaunchKernelGGL(norm_accum_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, a, g);
+    } else if (src_cl) {   // PTB_SRC_CHANNELS_LAST: the same cells and chunks, one workgroup per chunk over all channels, any shape
+        cl_launch_accum(a, g, ch, s);
     } else if (!fast) {
         hipLaunchKernelGGL(view_accum_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, g);
     } else if (ch == 64) {
@@ -725,7 +718,7 @@ static int launch_group(const ViewArgs& a, const CellArgs& g, const std::vector<
 }
 
 // Accumulate a run of tiles [lo, hi) of the batch; splits recursively until each launch group decomposes.
-static int run_accum(ViewArgs& a, const int* xs, const int* ys, int lo, int hi, bool fast, int ch, const Fresh& fr, hipStream_t s) {
+static int run_accum(ViewArgs& a, const int* xs, const int* ys, int lo, int hi, bool fast, int ch, const Fresh& fr, hipStream_t s, bool src_cl = false) {
     if (lo >= hi) return PTB_OK;
     CellArgs g;
     int ids[MAX_GROUP];
@@ -740,10 +733,10 @@ static int run_accum(ViewArgs& a, const int* xs, const int* ys, int lo, int hi, 
     if (st == DECOMP_SPLIT) {
         if (n == 1) return PTB_EUNSUPPORTED;  // cannot happen: one tile is one cell
         const int mid = lo + n / 2;
-        const int rc = run_accum(a, xs, ys, lo, mid, fast, ch, fr, s);
-        return rc ? rc : run_accum(a, xs, ys, mid, hi, fast, ch, fr, s);
+        const int rc = run_accum(a, xs, ys, lo, mid, fast, ch, fr, s, src_cl);
+        return rc ? rc : run_accum(a, xs, ys, mid, hi, fast, ch, fr, s, src_cl);
     }
-    return launch_group(a, g, cells, fr, fast, ch, s);
+    return launch_group(a, g, cells, fr, fast, ch, s, src_cl);
 }
 
 // Dry run of run_accum's grouping on a scratch bitmap: PTB_EFRESH if any launch group would need a zero-fill.
@@ -784,7 +777,8 @@ static int accumulate_impl(float* image, float* norm, const float* weight, const
                            int reduction, const int64_t* xs64, const int64_t* ys64, int B, int C, int th, int tw, int H, int W,
                            uint8_t* fresh, int fresh_rows, hipStream_t s, int in_dtype = PTB_F32) {
     const int round_src = (in_dtype & PTB_ROUND_SRC) ? 1 : 0;
-    in_dtype &= ~PTB_ROUND_SRC;
+    const bool src_cl = (in_dtype & PTB_SRC_CHANNELS_LAST) != 0;
+    in_dtype &= ~(PTB_ROUND_SRC | PTB_SRC_CHANNELS_LAST);
     if (in_dtype < PTB_F32 || in_dtype > PTB_BF16) return PTB_EINVAL;
     const bool norm_only = !image && !in;  // ptb_norm_accumulate
     if ((!norm_only && (!image || !in)) || (norm_only && !norm) || !weight || !xs64 || !ys64) return PTB_EINVAL;
@@ -850,11 +844,11 @@ static int accumulate_impl(float* image, float* norm, const float* weight, const
                 if (rc) return rc;
             } else {  // one group: launch it right away with the plan we already have
                 a.ncells = nc; a.total_chunks = tc;
-                return launch_group(a, g, cells, fr, fast, ch, s);
+                return launch_group(a, g, cells, fr, fast, ch, s, src_cl);
             }
         }
     }
-    return run_accum(a, xs.data(), ys.data(), 0, B, fast, ch, fr, s);
+    return run_accum(a, xs.data(), ys.data(), 0, B, fast, ch, fr, s, src_cl);
 }
 
 }  // namespace ptb
@@ -887,7 +881,8 @@ extern "C" int ptb_accumulate_planned2(float* image, const float* norm_full, flo
                                        ptb_stream_t stream) {
     if (flags & ~1) return PTB_EINVAL;
     const int round_src = (in_dtype & PTB_ROUND_SRC) ? 1 : 0;
-    in_dtype &= ~PTB_ROUND_SRC;
+    const bool src_cl = (in_dtype & PTB_SRC_CHANNELS_LAST) != 0;
+    in_dtype &= ~(PTB_ROUND_SRC | PTB_SRC_CHANNELS_LAST);
     if (!image || !norm_full || !merged || !weight || !in || !xs64 || !ys64 || !remaining || !done) return PTB_EINVAL;
     if (B < 0 || C < 1 || th < 1 || tw < 1 || H < 1 || W < 1 || fresh_rows < 1) return PTB_EINVAL;
     if (reduction < PTB_RED_SUM || reduction > PTB_RED_LOG1P || in_dtype < PTB_F32 || in_dtype > PTB_BF16) return PTB_EINVAL;
@@ -928,7 +923,7 @@ extern "C" int ptb_accumulate_planned2(float* image, const float* norm_full, flo
     const int st = decompose(xs, ys, ids, B, tw, th, ch, fr, g, a.ncells, a.total_chunks, cells, &pl);
     if (st == DECOMP_NEEDS_ZERO) return PTB_EFRESH;
     if (st != DECOMP_OK) return PTB_EUNSUPPORTED;   // several launch groups, or the batch does not fit the plan
-    const int rc = launch_group(a, g, cells, fr, fast, ch, (hipStream_t)stream);
+    const int rc = launch_group(a, g, cells, fr, fast, ch, (hipStream_t)stream, src_cl);
     if (rc == PTB_OK) commit_plan(cells, pl);
     return rc;
 }
@@ -963,7 +958,8 @@ extern "C" int ptb_merge_band(float* merged, const float* norm_full, const float
                               const int64_t* xs64, const int64_t* ys64, int n, int C, int th, int tw, int H, int W, int y0, int y1,
                               ptb_stream_t stream) {
     const int round_src = (in_dtype & PTB_ROUND_SRC) ? 1 : 0;
-    in_dtype &= ~PTB_ROUND_SRC;
+    const bool src_cl = (in_dtype & PTB_SRC_CHANNELS_LAST) != 0;
+    in_dtype &= ~(PTB_ROUND_SRC | PTB_SRC_CHANNELS_LAST);
     if (!merged || !norm_full || !weight || !tile_src || !tile_view_stride || !xs64 || !ys64) return PTB_EINVAL;
     if (n < 1 || C < 1 || th < 1 || tw < 1 || H < 1 || W < 1 || y0 < 0 || y1 <= y0 || y1 > H) return PTB_EINVAL;
     if (reduction < PTB_RED_SUM || reduction > PTB_RED_LOG1P || in_dtype < PTB_F32 || in_dtype > PTB_BF16) return PTB_EINVAL;
@@ -1028,7 +1024,8 @@ extern "C" int ptb_merge_band(float* merged, const float* norm_full, const float
     a.total_chunks = run;
     const long long blocks = (long long)run * C;
     if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
-    launch_band(a, g, (int)blocks, (hipStream_t)stream);
+    if (src_cl) cl_launch_band(a, g, run, (hipStream_t)stream);   // one workgroup per chunk over all channels
+    else launch_band(a, g, (int)blocks, (hipStream_t)stream);
     return check_launch();
 }
 
@@ -1054,7 +1051,7 @@ extern "C" int ptb_deaug_accumulate_t(float* image, float* norm, const float* we
 }
 
 static int deaug_reduce_impl(const float* in, int in_dtype, float* out, int V, const int* views, int reduction, int B, int C, int H,
-                             int W, ptb_stream_t stream);
+                             int W, ptb_stream_t stream, bool src_cl = false);
 
 extern "C" int ptb_deaug_reduce(const float* in, float* out, int V, const int* views, int reduction, int B, int C, int H, int W,
                                 ptb_stream_t stream) {
@@ -1063,12 +1060,14 @@ extern "C" int ptb_deaug_reduce(const float* in, float* out, int V, const int* v
 
 extern "C" int ptb_deaug_reduce_t(const void* in, int in_dtype, float* out, int V, const int* views, int reduction, int B, int C,
                                   int H, int W, ptb_stream_t stream) {
+    const bool src_cl = (in_dtype & PTB_SRC_CHANNELS_LAST) != 0;
+    in_dtype &= ~PTB_SRC_CHANNELS_LAST;
     if (in_dtype < PTB_F32 || in_dtype > PTB_BF16) return PTB_EINVAL;
-    return deaug_reduce_impl(static_cast<const float*>(in), in_dtype, out, V, views, reduction, B, C, H, W, stream);
+    return deaug_reduce_impl(static_cast<const float*>(in), in_dtype, out, V, views, reduction, B, C, H, W, stream, src_cl);
 }
 
 static int deaug_reduce_impl(const float* in, int in_dtype, float* out, int V, const int* views, int reduction, int B, int C, int H,
-                             int W, ptb_stream_t stream) {
+                             int W, ptb_stream_t stream, bool src_cl) {
     if (!in || !out || B < 0 || C < 1 || H < 1 || W < 1) return PTB_EINVAL;
     if (reduction < PTB_RED_SUM || reduction > PTB_RED_LOG1P) return PTB_EINVAL;
     if (int rc = validate_views(V, views, H, W)) return rc;
@@ -1086,7 +1085,7 @@ static int deaug_reduce_impl(const float* in, int in_dtype, float* out, int V, c
     a.codes = pack_runtime(V, views);
     a.scale = 1.0f;
     fill_reduction(a, reduction, V);
-    return run_plain(a, B, MODE_REDUCE, (hipStream_t)stream);
+    return run_plain(a, B, MODE_REDUCE, (hipStream_t)stream, src_cl);
 }
 
 extern "C" int ptb_view_transform(const float* in, float* out, int V, const int* views, int in_is_batch, float scale, int B,

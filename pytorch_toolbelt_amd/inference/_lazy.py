@@ -138,7 +138,7 @@ class LazyDeaugment(torch.Tensor):
         if _dlpack_orig is None:
             _guard_legacy_dlpack()         # (first handle of the process: from here on to_dlpack(handle) must evaluate it first)
         self._len = source.shape[0] // len(views)      # (len(handle) without the __torch_function__ round trip)
-        self._src = source                 # [V*B, C, H, W] contiguous float32 / float16 / bfloat16 model output (chunk-major)
+        self._src = source                 # [V*B, C, H, W] contiguous or channels-last float32 / float16 / bfloat16 model output (chunk-major)
         self._group = group                # "d4" | "d2" | "flips" | "fliplr" | "flipud"
         self._views = views                # inverse view codes, chunk order
         self._code = code                  # HIP reduction code
@@ -290,8 +290,10 @@ def maybe_lazy(source, group, views, code, compute, owned=False):
     if source.requires_grad and torch.is_grad_enabled():
         return None
     n_views = len(views)
-    if source.shape[0] % n_views != 0 or source.numel() == 0 or not source.is_contiguous():
+    if source.shape[0] % n_views != 0 or source.numel() == 0:
         return None
+    if not source.is_contiguous() and not source.is_contiguous(memory_format=torch.channels_last):
+        return None      # (a channels-last model output is read where it lies, by the fused launch and by the handle's own evaluation alike)
     if any(v & 1 for v in views) and source.shape[2] != source.shape[3]:
         return None
     if torch.jit.is_tracing() or torch.jit.is_scripting() or torch.compiler.is_compiling():

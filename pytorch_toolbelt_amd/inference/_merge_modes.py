@@ -296,10 +296,10 @@ class Bands:
 
 # ------------------------------------------------------------------------------------------------ strategies
 def _fast_call(merger, batch, crop_coords):
-    """The common call -- a contiguous model output on the merger's device that needs no autograd detach, crops as an int64 [B, 4]
-    array (a numpy slice of ``tiler.crops``): everything per call can then be validated with a handful of comparisons."""
+    """The common call -- a contiguous (or channels-last) model output on the merger's device that needs no autograd detach, crops as an
+    int64 [B, 4] array (a numpy slice of ``tiler.crops``): everything per call can then be validated with a handful of comparisons."""
     return (type(crop_coords) is np.ndarray and crop_coords.ndim == 2 and crop_coords.dtype == np.int64 and batch.is_cuda
-            and batch.is_contiguous() and not batch.requires_grad and not merger._eager_norm and not merger._window_edited())
+            and N.dense_or_channels_last(batch) and not batch.requires_grad and not merger._eager_norm and not merger._window_edited())
 
 
 class _OfMerger:
@@ -467,12 +467,14 @@ class DeferredBands(_OfMerger):
         """Every batch of an image after its first one, in ~4 us of host time (round 6; the 14-argument ``ptb_band_plan_submit`` path costs
         ~7 us a call -- 0.33 ms per 5000 x 5000 image, more than the kernels of the TTA-free loop take): the image's configuration
         (dtype, views, reduction, buffers) sits in the C plan since its first submit, custody overlap is checked there
-        (``ptb_band_plan_submit_next``), and what is left here is the contract of the call itself -- the next planned crops, a contiguous
-        batch of the image's dtype / shape on the merger's device, held batches unmodified when a launch is due.  None: not that call
+        (``ptb_band_plan_submit_next``), and what is left here is the contract of the call itself -- the next planned crops, a batch of the
+        image's dtype / shape / memory layout (contiguous, or channels-last: one dense byte range either way) on the merger's device, held
+        batches unmodified when a launch is due.  None: not that call
         (the ordinary fast path decides)."""
         s = self.slim
         if (key != s[0] or rnd != s[1] or type(crop_coords) is not np.ndarray or crop_coords.dtype.char != "l" or batch.dtype is not s[2]
-                or not batch.is_contiguous() or batch.requires_grad or not self.active):
+                or not (batch.is_contiguous() if not s[10] else N.batch_layout(batch) == N.LAYOUT_CHANNELS_LAST) or batch.requires_grad
+                or not self.active):
             return None
         m = self._m()
         plan = m._plan
@@ -539,6 +541,8 @@ class DeferredBands(_OfMerger):
             return False
         if rnd:
             dcode |= (rnd & LAZY_SRC) | (rnd & N.ROUND_SRC if dcode else 0)
+        src_cl = N.layout_flag(batch)
+        dcode |= src_cl
         varr, n_views = m._view_array(key, views)
         if batch.shape != (B * n_views, m.channels, m.weight.shape[1], m.weight.shape[2]):
             return False
@@ -554,7 +558,7 @@ class DeferredBands(_OfMerger):
             idx = dev.index if dev.index is not None else torch.cuda.current_device()
             th, tw = int(m.weight.shape[1]), int(m.weight.shape[2])
             self.slim = (key, rnd, batch.dtype, torch.Size((m.channels, th, tw)), n_views, idx, N.load().ptb_band_plan_submit_next,
-                         n_views * m.channels * th * tw * batch.element_size(), views, code)
+                         n_views * m.channels * th * tw * batch.element_size(), views, code, src_cl)
         return True
 
     def take(self, batch, coords, xy, views, reduction, dcode):
@@ -633,6 +637,8 @@ class PlannedBlocks(_OfMerger):
         dcode = N.DTYPE_CODES.get(batch.dtype)
         if dcode and rnd & N.ROUND_SRC:
             dcode |= N.ROUND_SRC
+        if dcode is not None:
+            dcode |= N.layout_flag(batch)
         B, pos = crop_coords.shape[0], plan.pos
         if (dcode is None or B == 0 or batch.device != m._image.device or pos + B > plan.xy.shape[1] or crop_coords.shape[1] != 4
                 or not plan.next_are(crop_coords, B)):
@@ -742,7 +748,7 @@ class Incremental(_OfMerger):
                 m._materialize()
                 rc = launch(None)
         N.bump()
-        if rc == -2 and dcode != N.F32:   # shape needs the scalar kernels: take the reference's route (cast, then accumulate)
+        if rc == -2 and dcode & N.DTYPE_MASK != N.F32:   # shape needs the scalar kernels: take the reference's route (cast, then accumulate)
             if dcode & N.ROUND_SRC:        # (the source of a lazy de-augmentation handle: evaluate it as the eager call would -- a half tensor -- and blend that)
                 from ._views import deaug_reduce
 

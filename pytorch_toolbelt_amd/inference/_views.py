@@ -78,7 +78,8 @@ def _raw_view_transform(x, views: Sequence[int], in_is_batch: bool, scale: float
 
 def _raw_deaug_reduce(x, views: Sequence[int], code: int):
     """out[b] = reduce_k view_k(x[k*B + b]); x contiguous [V*B, C, H, W] on the GPU, fp32 -- or fp16 / bf16, which the
-    kernel widens in registers (the fp32 copy the reference's `.float()` would write never exists).  out is fp32."""
+    kernel widens in registers (the fp32 copy the reference's `.float()` would write never exists) -- or the same in
+    torch.channels_last, read where it lies (SRC_CHANNELS_LAST).  out is fp32, contiguous NCHW."""
     V = len(views)
     n, C, H, W = x.shape
     B = n // V
@@ -88,10 +89,10 @@ def _raw_deaug_reduce(x, views: Sequence[int], code: int):
     lib = N.load()
     dcode = N.DTYPE_CODES[x.dtype]
     with N.on_device(x.device):
-        rc = lib.ptb_deaug_reduce_t(x.data_ptr(), dcode, out.data_ptr(), V, N.int_array(views), code, B, C, H, W, N.stream_ptr(x.device))
+        rc = lib.ptb_deaug_reduce_t(x.data_ptr(), dcode | N.layout_flag(x), out.data_ptr(), V, N.int_array(views), code, B, C, H, W, N.stream_ptr(x.device))
     N.bump()
     if rc == -2 and dcode != N.F32:   # shape needs the scalar kernels
-        return _raw_deaug_reduce(x.float(), views, code)
+        return _raw_deaug_reduce(x.float(), views, code)      # (.float() keeps the memory format)
     N.check(rc, "ptb_deaug_reduce")
     return out
 
@@ -133,9 +134,12 @@ class _DeaugReduce(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, views, code):
         ctx.views, ctx.code = tuple(views), code
-        x = x.contiguous()
+        nonlinear = code not in (N.RED_SUM, N.RED_MEAN)
+        # (the backward kernel of the non-linear reductions reads the saved input as dense NCHW; inference reads channels-last where it lies)
+        if (nonlinear and ctx.needs_input_grad[0]) or not N.dense_or_channels_last(x):
+            x = x.contiguous()
         out = _raw_deaug_reduce(x, views, code)
-        if code not in (N.RED_SUM, N.RED_MEAN):
+        if nonlinear:
             ctx.save_for_backward(x, out)
         return out
 
@@ -237,7 +241,7 @@ def deaug_reduce(x, views, code):
         # inference on half-precision model outputs: read them as they are
         if x.shape[0] % len(views) != 0:
             raise RuntimeError(f"Input batch size ({x.size(0)}) must be divisible by {len(views)}.")
-        return _raw_deaug_reduce(x.contiguous(), views, code).to(x.dtype)
+        return _raw_deaug_reduce(x if N.dense_or_channels_last(x) else x.contiguous(), views, code).to(x.dtype)
     x, back = _check_image(x, "de-augment")
     if x.shape[0] % len(views) != 0:
         raise RuntimeError(f"Input batch size ({x.size(0)}) must be divisible by {len(views)}.")

@@ -667,7 +667,9 @@ class TileMerger:
             batch = batch.to(device=self._image.device)
         if batch.dtype not in N.DTYPE_CODES:   # fp16 / bf16 model outputs are widened inside the kernel, not copied
             batch = batch.type_as(self._image)
-        return batch.detach().contiguous()
+        batch = batch.detach()
+        # a channels-last model output is read where it lies (N.SRC_CHANNELS_LAST); any other strides are copied, as ever
+        return batch if N.dense_or_channels_last(batch) else batch.contiguous()
 
     def _check_state(self):
         for t in (self._image, self._norm, self.weight):
@@ -697,6 +699,7 @@ class TileMerger:
         dcode = N.DTYPE_CODES[batch.dtype]
         if rnd & N.ROUND_SRC and dcode != N.F32:
             dcode |= N.ROUND_SRC
+        dcode |= N.layout_flag(batch)
         if B:
             self._selfplan.observe(batch, n_views, rnd & _LAZY_SRC)
         if B and self._deferred.active and self._deferred.take(batch, coords, xy, views, reduction, dcode | (rnd & _LAZY_SRC)):

@@ -132,6 +132,13 @@ def _image_deaugment(image: Tensor, group: str, reduction: MaybeStrOrCallable, l
 
 def _labels_deaugment(logits: Tensor, n: int, reduction: MaybeStrOrCallable, order=None) -> Tensor:
     chunks = split_into_chunks(logits, n)
+    if (order is None and logits.is_cuda and n <= 8 and N.batch_layout(logits) == N.LAYOUT_CHANNELS_LAST and logits.dtype in N.DTYPE_CODES
+            and not (logits.requires_grad and torch.is_grad_enabled())):
+        # channels-last logits maps: the reduction over the chunks is the identity-view de-augmentation, which reads them where they lie
+        # (same sums in the same order as the stack reduction below; the result is contiguous NCHW as ever)
+        code = _reduction_code(reduction)
+        if code is not None:
+            return V.deaug_reduce(logits, [N.IDENT] * n, code)
     if order is None:  # chunk-major input is already the [T, B, ...] stack
         stack = logits.reshape(n, logits.size(0) // n, *logits.shape[1:])
     else:
