@@ -398,6 +398,48 @@ int ptb_volume_split_mirror(const void* volume, int in_dtype, int D, int H, int 
                             const int64_t* xs, int B, int d, int h, int w, const float* scale, const float* bias, float pad_value,
                             int nviews, const int* masks, int out_dtype, void* out, ptb_stream_t stream);
 
+/* ---- Deferred slab merge of VolumeMerger(crops=, defer=True): the 3-D blend without accumulators (ptb_volume_bands.hip) ----------
+ * The n tile origins (zs, ys, xs; every tile d x h x w, in integration order) are known up front.  Every axis is cut at all tile
+ * starts and ends; inside a CELL (product of three intervals) the list of covering tiles is constant.  Cells with one z-interval form
+ * a SLAB; once the last tile over a slab is in, one launch reads every covering tile of its voxels, blends in integration order in
+ * registers (acc = acc + t * w from +0, n = n + w) and writes acc / n into the result window with the cast / layout / argmax of
+ * ptb_volume_merge_crop -- bit for bit ptb_volume_accumulate (or ptb_volume_mirror_accumulate) over all tiles followed by
+ * ptb_volume_merge_crop, with no [C + 1, D, H, W] accumulators in memory.
+ * ptb_volume_plan_create: HOST-side planning.  window = {z0, y0, x0, OD, OH, OW} of the padded volume, layout / kind as for
+ *   ptb_volume_merge_crop.  Work items = (cell x window) cut into boxes; voxels outside the window are never computed; a cell nobody
+ *   covers writes 0 / 0.  Returns the bytes of the device table (>= 0; *out receives the plan), PTB_EBOUNDS for a tile or a window
+ *   outside the volume, PTB_EUNSUPPORTED when more than 8 tiles cover a voxel (a step below half the tile) or a tile side exceeds 65535.
+ * ptb_volume_plan_items: the work-item table for the host, 16 int64 per item: launch group, z0, z1, y0, y1, x0, x1 (the box, in
+ *   padded-volume coordinates, inside the window), number of covering tiles, their 8 indices in integration order (-1 beyond).
+ *   rows == NULL: returns the number of items; else fills `rows` (capacity in items) and returns it.
+ * ptb_volume_plan_info: launch groups (a slab whose tile list exceeds the 224 a launch carries in its kernel arguments is cut into
+ *   several groups) in launch order = ascending completing tile; slabs; items; last_group_of_tile [n] (-1: no item reads the tile);
+ *   group_info [4 * n_groups] = z0, z1 of the slab, completing tile, items; peak_held_tiles = the most tiles in custody at once when
+ *   tiles arrive one by one (a tile is held until the tile completing its last group is in); vec_ok = 1 when w and every x origin are
+ *   multiples of 4 (the 16-byte instances serve it if the pointers are aligned too; otherwise one voxel per lane).  Any output may be NULL.
+ * ptb_volume_plan_upload: copies the item table into caller-provided device memory (16-byte aligned, the size create returned);
+ *   the library never allocates device memory.
+ * ptb_volume_plan_submit: takes the B tiles pos .. pos+B-1 -- `batch` = view 0 of the first, tile b at batch + b * tile_stride
+ *   elements, view v of a tile view_stride elements further per view; in_dtype PTB_F32 / F16 / BF16 read natively; nviews = 0: plain
+ *   tiles, else the mirror masks / reduction of ptb_volume_mirror_accumulate -- and launches every group that is now complete.
+ *   weight DEVICE [d, h, w] fp32; out DEVICE, the result window.  Returns the number of launches (>= 0); PTB_EUNSUPPORTED (nothing
+ *   recorded or launched) when `pos` is not the next planned tile, the batch runs past the plan, or dtype / views / reduction /
+ *   weight / out differ from the image's first batch.  Arguments are validated before anything touches the device.
+ * ptb_volume_plan_reset: next image.  ptb_volume_plan_state: tiles taken / groups launched for the current image. */
+typedef struct ptb_volume_plan ptb_volume_plan;
+int64_t ptb_volume_plan_create(const int64_t* zs, const int64_t* ys, const int64_t* xs, int n, int C, int d, int h, int w, int D, int H,
+                               int W, const int64_t* window, int layout, int kind, ptb_volume_plan** out);
+int64_t ptb_volume_plan_items(const ptb_volume_plan* plan, int64_t* rows, int64_t capacity);
+int ptb_volume_plan_info(const ptb_volume_plan* plan, int* n_groups, int* n_slabs, int64_t* n_items, int64_t* last_group_of_tile,
+                         int64_t* group_info, int* peak_held_tiles, int* vec_ok);
+int ptb_volume_plan_upload(ptb_volume_plan* plan, void* dev_table, ptb_stream_t stream);
+int ptb_volume_plan_reset(ptb_volume_plan* plan);
+int ptb_volume_plan_state(const ptb_volume_plan* plan, int* pos, int* launched);
+int ptb_volume_plan_submit(ptb_volume_plan* plan, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride,
+                           int in_dtype, int nviews, const int* masks, int reduction, const float* weight, void* out,
+                           ptb_stream_t stream);
+void ptb_volume_plan_destroy(ptb_volume_plan* plan);
+
 /* ---- {fliplr,flipud,flips,d2,d4}_image_deaugment (inference/tta.py:287-316,344-365,442-467,503-524) -------------
  * in [V*B, C, H, W] (chunk-major: rows [k*B,(k+1)*B) are view k), views HOST int[V] = inverse transform of each chunk.
  * out [B, C, H, W] = reduce_k view_k(in[k*B + b]).  V <= 8.  Transposing views require H == W. */

@@ -156,6 +156,14 @@ SIGNATURES = {
     "ptb_volume_mirror_accumulate": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _ip, _c_int, _i64p, _i64p, _i64p] + [_c_int] * 8 + [_vp]),
     "ptb_volume_split_mirror": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _i64p, _i64p, _i64p, _c_int, _c_int, _c_int, _c_int, _fp, _fp,
                                          _c_f, _c_int, _ip, _c_int, _vp, _vp]),
+    "ptb_volume_plan_create": (_c_i64, [_i64p, _i64p, _i64p] + [_c_int] * 8 + [_i64p, _c_int, _c_int, _vpp]),
+    "ptb_volume_plan_items": (_c_i64, [_vp, _i64p, _c_i64]),
+    "ptb_volume_plan_info": (_c_int, [_vp, _ip, _ip, _i64p, _i64p, _i64p, _ip, _ip]),
+    "ptb_volume_plan_upload": (_c_int, [_vp, _vp, _vp]),
+    "ptb_volume_plan_reset": (_c_int, [_vp]),
+    "ptb_volume_plan_state": (_c_int, [_vp, _ip, _ip]),
+    "ptb_volume_plan_submit": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_i64, _c_int, _c_int, _ip, _c_int, _vp, _vp, _vp]),
+    "ptb_volume_plan_destroy": (None, [_vp]),
 }
 
 _lib = None

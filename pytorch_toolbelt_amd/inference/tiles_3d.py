@@ -8,6 +8,7 @@ accumulate_single`` indexes with a tuple inside a tuple (:191-192).  What works 
 reproduced exactly (pinned by golden vectors); the broken parts implement the evident intent and are listed in
 DESIGN.md.
 """
+import ctypes
 from typing import Any, Iterable, List, Tuple, Union
 
 import numpy as np
@@ -15,6 +16,7 @@ import torch
 
 from .. import _native as N
 from . import _host
+from ._merge_modes import HeldBatches
 from .tta_3d import flip_view, mirror_views
 
 __all__ = ["VolumeSlicer", "VolumeMerger"]
@@ -218,11 +220,179 @@ def _roi_starts(rois, tile):
     return np.ascontiguousarray(starts)
 
 
-class VolumeMerger:
+# ------------------------------------------------------------------------------------------------ deferred slab merge
+_DEFER_HINT = "construct the merger without defer=True"
+_RESULT_KEYS = ("crop", "layout", "dtype", "argmax")
+
+
+class _ResultSpec:
+    """What a deferred merger writes: the arguments of ``merge_crop`` (``result=dict(crop=, layout=, dtype=, argmax=)``), or with
+    ``result=None`` the full padded float32 ``[C, D', H', W']`` volume that ``merge()`` returns."""
+
+    def __init__(self, result, shape):
+        self.default = result is None
+        result = dict(result or {})
+        unknown = sorted(set(result) - set(_RESULT_KEYS))
+        if unknown:
+            raise ValueError(f"result= takes the arguments of merge_crop {_RESULT_KEYS}, got {unknown}")
+        self.layout = result.get("layout", "cdhw")
+        self.window = _crop_window(result.get("crop", (0, 0, 0) + tuple(shape)), shape, self.layout)
+        self.dtype = result.get("dtype", torch.float32)
+        self.argmax = bool(result.get("argmax", False))
+        self.kind, self.out_dtype = _crop_kind(self.dtype, self.argmax)
+
+    def out_shape(self, channels):
+        od, oh, ow = self.window[3:]
+        if self.argmax:
+            return (od, oh, ow)
+        return (channels, od, oh, ow) if self.layout == "cdhw" else (od, oh, ow, channels)
+
+    def __repr__(self):
+        return f"result=dict(crop={self.window}, layout={self.layout!r}, dtype={self.dtype}, argmax={self.argmax})"
+
+
+class VolumePlan:
+    """Host-side plan of a deferred slab merge (``ptb_volume_plan_*``; needs the library, not a GPU): the crop list cut into cells of
+    constant covering-tile lists, slabs, launch groups and work items.  ``items()`` is the host-readable table ``[n_items, 16]`` int64:
+    launch group, z0, z1, y0, y1, x0, x1 of the box (padded-volume coordinates, inside the window), number of covering tiles, their 8
+    indices in integration order (-1 beyond).  ``group_info`` ``[n_groups, 4]``: z0, z1 of the slab, completing tile, items."""
+
+    def __init__(self, crops, tile, shape, channels, window=None, layout="cdhw", kind=N.CROP_F32):
+        d, h, w = (int(s) for s in tile)
+        D, H, W = (int(s) for s in shape)
+        self.starts = _roi_starts(crops, (d, h, w))
+        n = self.starts.shape[1]
+        window = (0, 0, 0, D, H, W) if window is None else tuple(int(v) for v in window)
+        lib = N.load()
+        self._lib = lib
+        self.handle = ctypes.c_void_p()
+        nbytes = lib.ptb_volume_plan_create(self.starts[0].ctypes.data_as(N._i64p), self.starts[1].ctypes.data_as(N._i64p),
+                                            self.starts[2].ctypes.data_as(N._i64p), n, int(channels), d, h, w, D, H, W, N.i64_array(window),
+                                            1 if layout == "dhwc" else 0, int(kind), ctypes.byref(self.handle))
+        if nbytes < 0:
+            self.handle = None
+            if nbytes == N.PTB_EUNSUPPORTED:
+                raise NotImplementedError("deferred slab merge: more than 8 tiles cover a voxel (a step below half the tile), or a tile side "
+                                          f"exceeds 65535; {_DEFER_HINT}")
+            N.check(int(nbytes), "VolumePlan")
+        self.table_bytes = int(nbytes)
+        self.n_tiles = n
+        n_groups, n_slabs, peak, vec = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        n_items = ctypes.c_int64()
+        last = np.zeros(n, dtype=np.int64)
+        lib.ptb_volume_plan_info(self.handle, ctypes.byref(n_groups), ctypes.byref(n_slabs), ctypes.byref(n_items), last.ctypes.data_as(N._i64p),
+                                 None, ctypes.byref(peak), ctypes.byref(vec))
+        info = np.zeros((max(1, n_groups.value), 4), dtype=np.int64)
+        lib.ptb_volume_plan_info(self.handle, None, None, None, None, info.ctypes.data_as(N._i64p), None, None)
+        self.n_groups, self.n_slabs, self.n_items = n_groups.value, n_slabs.value, int(n_items.value)
+        self.last_group_of_tile = last
+        self.group_info = info[:self.n_groups]
+        self.peak_held_tiles = peak.value
+        self.vec_ok = bool(vec.value)
+
+    def items(self):
+        rows = np.zeros((max(1, self.n_items), 16), dtype=np.int64)
+        got = self._lib.ptb_volume_plan_items(self.handle, rows.ctypes.data_as(N._i64p), self.n_items)
+        if got < 0:
+            N.check(int(got), "VolumePlan.items")
+        return rows[:self.n_items]
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ptb_volume_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DeferredVolume:
+    """What the HIP and the torch-op merger share in deferred mode: the planned sequence, the image's configuration, the result spec."""
+
+    _defer = None
+
+    def _defer_setup(self, crops, defer, result, shape, tile):
+        if not defer:
+            if crops is not None or result is not None:
+                raise ValueError(f"{type(self).__name__}: crops= and result= belong to defer=True")
+            return False
+        if crops is None:
+            raise ValueError(f"{type(self).__name__}: defer=True needs crops= (the whole crop sequence, in integration order)")
+        self._spec = _ResultSpec(result, shape)
+        self._starts = _roi_starts(list(crops), tile)
+        if self._starts.shape[1] == 0:
+            raise ValueError(f"{type(self).__name__}: crops= is empty")
+        self._pos, self._config = 0, None
+        self._defer = True
+        return True
+
+    def _next_rois(self, rois, what):
+        """``rois`` must be the next planned crops; returns their count."""
+        tile = tuple(int(s) for s in self.weight.shape[1:])
+        starts = _roi_starts(rois, tile)
+        n, pos = self._starts.shape[1], self._pos
+        if pos + len(rois) > n or not np.array_equal(starts, self._starts[:, pos:pos + len(rois)]):
+            raise RuntimeError(f"{what}: the rois are not the next {len(rois)} entries of crops= (tile {pos} of {n} is due); a deferred merger takes "
+                               f"the planned sequence in order -- {_DEFER_HINT}")
+        return len(rois)
+
+    def _same_config(self, config, what):
+        if self._pos == 0:
+            self._config = config
+        elif config != self._config:
+            raise RuntimeError(f"{what}: dtype / mirror / reduction {config} differ from the image's first batch {self._config}; one configuration "
+                               f"per image in deferred mode -- {_DEFER_HINT}")
+
+    def _finished_result(self, what):
+        n = self._starts.shape[1]
+        if self._pos != n:
+            raise RuntimeError(f"{what}: only {self._pos} of the {n} planned tiles are in; a deferred merger has no accumulators to read early -- "
+                               f"{_DEFER_HINT}")
+        return self._result
+
+    def _deferred_merge(self):
+        if not self._spec.default:
+            raise ValueError(f"merge(): this deferred merger writes {self._spec!r}; call merge_crop with these arguments, or {_DEFER_HINT}")
+        out = self._finished_result("VolumeMerger.merge")
+        return out if self.dtype == out.dtype else out.to(self.dtype)
+
+    def _deferred_merge_crop(self, crop, layout, dtype, argmax):
+        spec = self._spec
+        shape = tuple(int(s) for s in self._volume_shape)
+        window = _crop_window(crop, shape, layout)
+        kind, _ = _crop_kind(dtype, argmax)
+        if window != spec.window or layout != spec.layout or kind != spec.kind:
+            raise ValueError(f"merge_crop(crop={window}, layout={layout!r}, dtype={dtype}, argmax={argmax}): this deferred merger writes {spec!r}; "
+                             f"call it with these arguments, or {_DEFER_HINT}")
+        return self._finished_result("VolumeMerger.merge_crop")
+
+    def _no_accumulators(self, name):
+        raise RuntimeError(f"VolumeMerger.{name}: a deferred merger keeps no accumulators (the slabs write the result directly) -- {_DEFER_HINT}")
+
+
+class VolumeMerger(_DeferredVolume):
     """Blend 3-D tile predictions into a full volume that lives in HBM (reference inference/tiles_3d.py:169-211).
 
     ``volume`` ``[C, D, H, W]``, ``norm_mask`` ``[1, D, H, W]`` and ``weight`` ``[1, d, h, w]`` are public fp32 tensors
-    on the GPU.  ``integrate_batch`` adds ``tile * weight`` tile after tile (bit-identical to the reference's loop)."""
+    on the GPU.  ``integrate_batch`` adds ``tile * weight`` tile after tile (bit-identical to the reference's loop).
+
+    ``crops=, defer=True[, result=]`` (keyword-only, opt-in): the deferred slab merge.  The merger keeps references to the model
+    outputs instead of accumulating them; when the last tile over a z-slab of the plan is in, one launch reads every covering tile,
+    blends in integration order in registers and writes ``sum / norm`` straight into the result -- bit for bit what the plain
+    ``integrate_batch`` / ``integrate_batch_deaugment`` calls followed by ``merge_crop(**result)`` (``result=None``: ``merge()``)
+    give, with no ``volume`` / ``norm_mask`` in memory.  ``result``: the arguments of ``merge_crop`` as a dict (``crop``, ``layout``,
+    ``dtype``, ``argmax``); ``merge_crop`` called with the same arguments returns the tensor the slabs wrote.  The contract is
+    strict: ``rois`` must be the next entries of ``crops``; batches are CUDA float32 / float16 / bfloat16 on the merger's device, read
+    as they are, and must stay alive and unmodified until their slabs are merged (``_merge_modes.HeldBatches``); dtype / mirror /
+    reduction are fixed by an image's first batch; ``merge`` / ``merge_crop`` come after the last tile; ``volume`` / ``norm_mask``
+    do not exist.  Anything else raises and says to construct the merger without ``defer=True``.  The price of the mode is custody:
+    ``peak_held_tiles`` (from the plan) is the most tiles held at once -- with z-major crops two z-layers of tiles, plus the batch in
+    flight (98 tiles = 3.3 GB for 343 tiles of 4 x 128^3 float32; 8 x that with the 8 float32 views of ``"dhw"``).  No byte budget is
+    enforced.  More than 8 tiles over a voxel (a step below half the tile) raises ``NotImplementedError``.  ``reset()`` starts the
+    next volume of the same geometry on the same plan."""
 
     def __new__(cls, volume_shape=None, channels=None, weight=None, device="cpu", *args, **kwargs):
         # like TileMerger: the device the caller names decides -- "cpu" (the reference's default) and float64 accumulators are the
@@ -235,7 +405,7 @@ class VolumeMerger:
                 return object.__new__(HostBackedVolumeMerger)
         return object.__new__(cls)
 
-    def __init__(self, volume_shape, channels: int, weight, device="cpu", dtype=torch.float32):
+    def __init__(self, volume_shape, channels: int, weight, device="cpu", dtype=torch.float32, *, crops=None, defer=False, result=None):
         from .tiles import _resolve_device
 
         device = _resolve_device(device, "VolumeMerger")
@@ -252,8 +422,92 @@ class VolumeMerger:
         self.channels = channels
         shape = tuple(int(s) for s in volume_shape)
         self.weight = torch.from_numpy(np.expand_dims(np.asarray(weight), axis=0)).to(device=device, dtype=dtype).contiguous()
+        self._volume_shape = shape
+        if self._defer_setup(crops, defer, result, shape, tuple(int(s) for s in self.weight.shape[1:])):
+            spec = self._spec
+            self._plan = VolumePlan(list(crops), self.weight.shape[1:], shape, channels, spec.window, spec.layout, spec.kind)
+            self.peak_held_tiles = self._plan.peak_held_tiles
+            self._held = HeldBatches("VolumeMerger")
+            self._groups_done = 0
+            self._table = torch.empty(max(16, self._plan.table_bytes), device=device, dtype=torch.uint8)   # the library allocates no device memory
+            with N.on_device(self._table.device):
+                N.check(N.load().ptb_volume_plan_upload(self._plan.handle, self._table.data_ptr(), N.stream_ptr(self._table.device)), "VolumeMerger")
+            self._result = torch.empty(spec.out_shape(channels), device=device, dtype=spec.out_dtype)
+            return
         self.volume = torch.zeros((channels, *shape), device=device, dtype=dtype)
         self.norm_mask = torch.zeros((1, *shape), device=device, dtype=dtype)
+
+    # ``volume`` / ``norm_mask``: plain attributes of a plain merger; a deferred one has none to show
+    @property
+    def volume(self):
+        if self._defer:
+            self._no_accumulators("volume")
+        return self._volume
+
+    @volume.setter
+    def volume(self, value):
+        self._volume = value
+
+    @property
+    def norm_mask(self):
+        if self._defer:
+            self._no_accumulators("norm_mask")
+        return self._norm_mask
+
+    @norm_mask.setter
+    def norm_mask(self, value):
+        self._norm_mask = value
+
+    def reset(self):
+        """Start the next volume of the same geometry: a plain merger zeroes ``volume`` and ``norm_mask``; a deferred one keeps its plan
+        and device table and gets a fresh result tensor (the caller may still hold the previous one)."""
+        if not self._defer:
+            self.volume.zero_()
+            self.norm_mask.zero_()
+            return
+        N.check(N.load().ptb_volume_plan_reset(self._plan.handle), "VolumeMerger.reset")
+        self._held.clear()
+        self._pos, self._config, self._groups_done = 0, None, 0
+        self._result = torch.empty(self._spec.out_shape(self.channels), device=self.weight.device, dtype=self._spec.out_dtype)
+
+    def _submit(self, batch, rois, views, code, what):
+        """Deferred mode: take the batch into custody and launch every slab that is now complete."""
+        if not torch.is_tensor(batch) or not batch.is_cuda:
+            raise RuntimeError(f"{what}: a deferred merger reads the batches where they lie, on the GPU -- got a host batch; move it to "
+                               f"{self.weight.device}, or {_DEFER_HINT}")
+        if batch.requires_grad:
+            raise RuntimeError(f"{what}: the batch requires grad; a deferred merger holds inference outputs (use torch.no_grad() / "
+                               f".detach()), or {_DEFER_HINT}")
+        if batch.device != self.weight.device:
+            raise ValueError(f"{what}: batch is on {batch.device}, the merger on {self.weight.device}")
+        dtype = N.DTYPE_CODES.get(batch.dtype)
+        if dtype is None:
+            raise NotImplementedError(f"{what} takes float32, float16 or bfloat16 batches, got {batch.dtype}")
+        d, h, w = (int(s) for s in self.weight.shape[1:])
+        if tuple(batch.shape[1:]) != (self.channels, d, h, w):
+            raise RuntimeError(f"tile batch of shape {tuple(batch.shape)} does not match [{'V*' if views else ''}B, {self.channels}, {d}, {h}, {w}]")
+        B = self._next_rois(rois, what)
+        self._same_config((batch.dtype, tuple(views), code), what)
+        if B == 0:
+            return
+        if not batch.is_contiguous():
+            batch = batch.contiguous()          # (the copy is what is held)
+        plan, pos = self._plan, self._pos
+        due = self._groups_done < plan.n_groups and int(plan.group_info[self._groups_done, 2]) < pos + B
+        span = self._held.admit(batch, due)
+        tile_elems = self.channels * d * h * w
+        dev = self.weight.device
+        with N.on_device(dev):
+            rc = N.load().ptb_volume_plan_submit(plan.handle, pos, B, batch.data_ptr(), tile_elems, B * tile_elems, dtype, len(views),
+                                                 N.int_array(views) if views else None, code, self.weight.data_ptr(), self._result.data_ptr(),
+                                                 N.stream_ptr(dev))
+        N.bump()
+        if rc < 0:
+            N.check(rc, what)
+        self._held.keep(batch, span, last_group=int(plan.last_group_of_tile[pos:pos + B].max()))
+        self._pos = pos + B
+        self._groups_done += rc
+        self._held.rows = [row for row in self._held.rows if row[2] >= self._groups_done]   # the last launch that reads them is out
 
     def _check_accumulators(self, what):
         for t in (self.volume, self.norm_mask, self.weight):
@@ -280,12 +534,16 @@ class VolumeMerger:
 
     def accumulate_single(self, tile: torch.Tensor, roi):
         """Accumulate one ``[C, d, h, w]`` prediction at ``roi`` (3 slices)."""
+        if self._defer:
+            return self.integrate_batch(tile.unsqueeze(0), [roi])
         self._accumulate(tile.detach().to(device=self.volume.device, dtype=torch.float32).unsqueeze(0).contiguous(), [roi])
 
     def integrate_batch(self, batch: torch.Tensor, rois):
         """Accumulate ``[B, C, d, h, w]`` predictions at ``rois[b]`` (3 slices each)."""
         if len(batch) != len(rois):
             raise ValueError("Number of images in batch does not correspond to number of coordinates")
+        if self._defer:
+            return self._submit(batch, rois, (), 0, "VolumeMerger.integrate_batch")
         self._accumulate(batch.detach().to(device=self.volume.device, dtype=torch.float32).contiguous(), rois)
 
     def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean"):
@@ -304,6 +562,8 @@ class VolumeMerger:
         code = _reduction_code(reduction)
         if code is None:
             raise ValueError(f"reduction={reduction!r} cannot be fused into the tile merge")
+        if self._defer:
+            return self._submit(batch, rois, tuple(views), code, "VolumeMerger.integrate_batch_deaugment")
         self._check_accumulators("VolumeMerger")
         dtype = N.DTYPE_CODES.get(batch.dtype)
         if dtype is None:
@@ -329,6 +589,8 @@ class VolumeMerger:
 
     def merge(self) -> torch.Tensor:
         """``volume / norm_mask`` as a new tensor (no eps clamp: never-covered voxels are NaN)."""
+        if self._defer:
+            return self._deferred_merge()
         out = torch.empty_like(self.volume)
         lib = N.load()
         dev = self.volume.device
@@ -348,6 +610,8 @@ class VolumeMerger:
         bfloat16 (round to nearest even) | uint8 (truncating cast, like ``TileMerger.merge_crop``); with ``argmax=True``: torch.uint8
         or torch.int64 (the default float32 gives int64) class indices ``[D, H, W]``.
         """
+        if self._defer:
+            return self._deferred_merge_crop(crop, layout, dtype, argmax)
         shape = tuple(int(s) for s in self.volume.shape[1:])
         z0, y0, x0, od, oh, ow = _crop_window(crop, shape, layout)
         kind, out_dtype = _crop_kind(dtype, argmax)
@@ -377,34 +641,59 @@ class HostBackedVolumeMerger(VolumeMerger):
     (inference/tiles_3d.py:169-211) -- ``volume`` / ``norm_mask`` / ``weight`` in the caller's dtype, tiles blended one after the
     other (``volume[:, roi] += tile * weight``), ``merge()`` without an eps clamp."""
 
-    def __init__(self, volume_shape, channels: int, weight, device="cpu", dtype=torch.float32):
+    def __init__(self, volume_shape, channels: int, weight, device="cpu", dtype=torch.float32, *, crops=None, defer=False, result=None):
         self.dtype = dtype
         self.channels = channels
         shape = tuple(int(s) for s in volume_shape)
         self.weight = torch.from_numpy(np.expand_dims(np.asarray(weight), axis=0)).to(device=device, dtype=dtype)
         self.volume = torch.zeros((channels, *shape), device=device, dtype=dtype)
         self.norm_mask = torch.zeros((1, *shape), device=device, dtype=dtype)
+        self._volume_shape = shape
+        # deferred mode on the host: the same interface and sequence checks; the tiles are blended at once (nothing is held), and the
+        # merge_crop expression runs once, when the last tile is in
+        if self._defer_setup(crops, defer, result, shape, tuple(int(s) for s in self.weight.shape[1:])):
+            self.peak_held_tiles = 0
+            self._result = None
+
+    def reset(self):
+        self._volume.zero_()
+        self._norm_mask.zero_()
+        if self._defer:
+            self._pos, self._config, self._result = 0, None, None
+
+    def _deferred_blend(self, batch, rois, config, what):
+        self._next_rois(rois, what)
+        self._same_config(config, what)
+        self._blend(batch.to(device=self._volume.device, dtype=self._volume.dtype), rois)
+        self._pos += len(rois)
+        if self._pos == self._starts.shape[1]:
+            spec = self._spec
+            self._result = self._host_merge() if spec.default else self._host_merge_crop(spec.window, spec.layout, spec.dtype, spec.argmax)
 
     def _blend(self, tiles, rois):
         d, h, w = (int(s) for s in self.weight.shape[1:])
         if tuple(tiles.shape[1:]) != (self.channels, d, h, w):
             raise RuntimeError(f"tile batch of shape {tuple(tiles.shape)} does not match [B, {self.channels}, {d}, {h}, {w}]")
         starts = _roi_starts(rois, (d, h, w))          # (validates the ROIs like the HIP merger: 3 slices of the window's extent)
-        D, H, W = (int(s) for s in self.volume.shape[1:])
+        D, H, W = (int(s) for s in self._volume.shape[1:])
         for tile, z, y, x in zip(tiles, starts[0], starts[1], starts[2]):
             z, y, x = int(z), int(y), int(x)
             if z < 0 or y < 0 or x < 0 or z + d > D or y + h > H or x + w > W:
                 raise RuntimeError("VolumeMerger.integrate_batch: tile rectangle outside the accumulator")
             roi = (slice(None), slice(z, z + d), slice(y, y + h), slice(x, x + w))
-            self.volume[roi] += tile * self.weight
-            self.norm_mask[roi] += self.weight
+            self._volume[roi] += tile * self.weight
+            self._norm_mask[roi] += self.weight
 
     def accumulate_single(self, tile: torch.Tensor, roi):
+        if self._defer:
+            return self.integrate_batch(tile.unsqueeze(0), [roi])
         self._blend(tile.to(device=self.volume.device, dtype=self.volume.dtype).unsqueeze(0), [roi])
 
     def integrate_batch(self, batch: torch.Tensor, rois):
         if len(batch) != len(rois):
             raise ValueError("Number of images in batch does not correspond to number of coordinates")
+        if self._defer:
+            return self._deferred_blend(batch, rois, (batch.dtype, (), 0), "VolumeMerger.integrate_batch")
         self._blend(batch.to(device=self.volume.device, dtype=self.volume.dtype), rois)
 
     def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean"):
@@ -418,17 +707,29 @@ class HostBackedVolumeMerger(VolumeMerger):
         code = _reduction_code(reduction)
         if code is None:
             raise ValueError(f"reduction={reduction!r} cannot be fused into the tile merge")
-        batch = batch.to(device=self.volume.device)
+        batch = batch.to(device=self._volume.device)
         stack = torch.stack([flip_view(c, m) for c, m in zip(torch.chunk(batch, len(views)), views)])
+        if self._defer:
+            return self._deferred_blend(_host.reduce_stack(stack, code), rois, (batch.dtype, tuple(views), code), "VolumeMerger.integrate_batch_deaugment")
         self.integrate_batch(_host.reduce_stack(stack, code), rois)
 
+    def _host_merge(self):
+        return self._volume / self._norm_mask
+
     def merge(self) -> torch.Tensor:
-        return self.volume / self.norm_mask
+        if self._defer:
+            return self._deferred_merge()
+        return self._host_merge()
 
     def merge_crop(self, crop, layout: str = "cdhw", dtype=torch.float32, argmax: bool = False) -> torch.Tensor:
         """``VolumeMerger.merge_crop`` with torch ops: the cropped window of ``merge()``, moved and converted."""
-        z0, y0, x0, od, oh, ow = _crop_window(crop, tuple(int(s) for s in self.volume.shape[1:]), layout)
-        window = self.merge()[:, z0:z0 + od, y0:y0 + oh, x0:x0 + ow]
+        if self._defer:
+            return self._deferred_merge_crop(crop, layout, dtype, argmax)
+        return self._host_merge_crop(crop, layout, dtype, argmax)
+
+    def _host_merge_crop(self, crop, layout, dtype, argmax):
+        z0, y0, x0, od, oh, ow = _crop_window(crop, tuple(int(s) for s in self._volume.shape[1:]), layout)
+        window = self._host_merge()[:, z0:z0 + od, y0:y0 + oh, x0:x0 + ow]
         _, out_dtype = _crop_kind(dtype, argmax)
         if argmax:
             return window.argmax(dim=0).to(out_dtype)
