@@ -75,7 +75,14 @@ typedef void* ptb_stream_t; /* hipStream_t */
  * keep their meaning (elements between tiles / views: C*th*tw, B*C*th*tw), every output stays planar fp32, and every result has the bits
  * the planar kernels give on the copied batch.  The layout is part of a band plan's per-image configuration (ptb_band_plan_submit_next
  * inherits it): a batch whose layout differs from the image's first batch gets PTB_EUNSUPPORTED with nothing launched, like a dtype
- * change.  With an unknown dtype the result is PTB_EINVAL, as without the flag. */
+ * change.  With an unknown dtype the result is PTB_EINVAL, as without the flag.
+ * The 5-D case: or-ed into the `dtype` of ptb_volume_mirror_reduce, the `in_dtype` of ptb_volume_mirror_accumulate and the `in_dtype` of
+ * ptb_volume_plan_submit, `src` / `tiles` / `batch` address [V*B, d, h, w, C] memory -- element (n, c, z, y, x) at
+ * (((n * d + z) * h + y) * w + x) * C + c, what a model in torch.channels_last_3d returns.  tile_stride / view_stride keep their meaning (a
+ * tile is still one contiguous block of C*d*h*w elements); everything written stays as it is -- the dense result of the source type,
+ * the planar fp32 accumulators, the PTB_CROP_* results and layouts -- with the bits the planar kernels give on the copied batch; argument
+ * checks keep their order and codes.  The layout is part of a volume plan's per-image configuration, like the dtype.
+ * ptb_volume_mirror, a bit copy, refuses the flag (PTB_EINVAL). */
 #define PTB_SRC_CHANNELS_LAST 0x200
 
 int ptb_version(void);

@@ -221,6 +221,20 @@ def dense_or_channels_last(t):
     return t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
 
 
+def volume_layout(t):
+    """``batch_layout`` for a 5-D model output: ``LAYOUT_DENSE`` (``[N, C, D, H, W]`` contiguous), ``LAYOUT_CHANNELS_LAST`` (not that, but
+    contiguous in ``torch.channels_last_3d`` -- element ``(n, c, z, y, x)`` at ``(((n * D + z) * H + y) * W + x) * C + c``; read where it lies
+    with ``SRC_CHANNELS_LAST``) or ``LAYOUT_OTHER`` (any other strides, tensors that are not 5-D: copied first).  With ``C == 1`` or a
+    1 x 1 x 1 volume the two formats coincide and the tensor counts as dense."""
+    if t.dim() != 5:
+        return LAYOUT_OTHER
+    if t.is_contiguous():
+        return LAYOUT_DENSE
+    if t.is_contiguous(memory_format=torch.channels_last_3d):
+        return LAYOUT_CHANNELS_LAST
+    return LAYOUT_OTHER
+
+
 def layout_flag(t):
     """``SRC_CHANNELS_LAST`` for a channels-last batch, 0 for a dense one."""
     return 0 if t.is_contiguous() else SRC_CHANNELS_LAST

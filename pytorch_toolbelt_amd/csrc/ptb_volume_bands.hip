@@ -19,41 +19,11 @@
 
 #include "ptb_crop_device.h"
 #include "ptb_mirror_device.h"
+#include "ptb_volume_device.h"
 
 namespace ptb {
 
-constexpr int VB_COVER = 8;      // tiles covering one cell (half overlap on three axes)
-constexpr int VB_TILES = 224;    // tiles of one launch group (kernarg: 224 x 16 B + VolArgs < 4 KiB)
-constexpr int VB_BLOCK = 256;
-constexpr int VB_UNITS = 1024;   // 4-runs per work item aimed at: four per lane
-
-struct VolItem {                 // 96 B, read with scalar loads only
-    int x0, y0, z0;              // origin in the padded volume (y, z clipped to the result window; x to its 4-aligned hull)
-    int nx, ny, nz;
-    int ntiles;                  // covering tiles (0: nobody covers these voxels -> 0 / 0 like the plain merge)
-    int zero;                    // 0, as a value the compiler cannot fold (the dividend and divisor of an uncovered voxel)
-    unsigned long long cover[VB_COVER];   // integration order: group slot | lx << 16 | ly << 32 | lz << 48 (item origin in the tile);
-};                                        // entries past ntiles repeat entry 0 (a valid address for the unrolled loads)
-static_assert(sizeof(VolItem) == 96, "VolItem layout");
-
-struct VolTiles {
-    const void* src[VB_TILES];   // view 0, channel 0 of the tile
-    long long vs[VB_TILES];      // elements between consecutive views of this tile (its batch size * C * d * h * w)
-};
-
-struct VolArgs {
-    const VolItem* items;        // first item of this launch
-    const float* weight;         // [d, h, w]
-    void* out;                   // the result window
-    int C, d, h, w;
-    int wz0, wy0, wx0, OD, OH, OW;
-    int layout;                  // 0: [C, OD, OH, OW], 1: [OD, OH, OW, C] (argmax kinds: [OD, OH, OW])
-    int nv, masks, op;           // mirror TTA: views, 3 bits each, PTB_RED_*
-    float divisor;
-};
-
-template <int KIND>
-constexpr bool vb_argmax() { return KIND == PTB_CROP_ARGMAX_U8 || KIND == PTB_CROP_ARGMAX_I64; }
+// (VB_* constants, VolItem / VolTiles / VolArgs, vb_argmax and vol_pos: ptb_volume_device.h)
 
 // v[m] <- v[m + s] (s in 0..3) with compile-time register indices
 template <typename T>
@@ -61,17 +31,6 @@ __device__ __forceinline__ void shift4(T (&v)[4], int s) {
     if (s == 1) { v[0] = v[1]; v[1] = v[2]; v[2] = v[3]; }
     else if (s == 2) { v[0] = v[2]; v[1] = v[3]; }
     else if (s == 3) { v[0] = v[3]; }
-}
-
-// A lane's run of PIX voxels at padded (gz, gy, gx ..): the part of it inside the result window
-struct VolPos { long long vox; int first, cnt; };   // window-linear index of the first stored voxel, its place in the run, how many
-__device__ __forceinline__ VolPos vol_pos(const VolArgs& a, int gz, int gy, int gx, int npix) {
-    const int lo = max(gx, a.wx0), hi = min(gx + npix, a.wx0 + a.OW);
-    VolPos p;
-    p.first = lo - gx;
-    p.cnt = hi - lo;
-    p.vox = ((long long)(gz - a.wz0) * a.OH + (gy - a.wy0)) * a.OW + (lo - a.wx0);
-    return p;
 }
 
 // Channel c of a run is ready: store it (cast and layout of ptb_merge_crop.hip), or fold it into the running argmax (first maximum
@@ -565,6 +524,9 @@ extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const 
                                       int in_dtype, int nviews, const int* masks, int reduction, const float* weight, void* out,
                                       ptb_stream_t stream) {
     if (!p || !batch || !weight || !out || B < 1 || tile_stride < 1) return PTB_EINVAL;
+    const int dtype_arg = in_dtype;      // (with PTB_SRC_CHANNELS_LAST: part of the image's configuration)
+    const bool src_cl = (in_dtype & PTB_SRC_CHANNELS_LAST) != 0;
+    in_dtype &= ~PTB_SRC_CHANNELS_LAST;
     if (in_dtype < PTB_F32 || in_dtype > PTB_BF16 || nviews < 0 || nviews > MAX_VIEWS) return PTB_EINVAL;
     int packed = 0;
     if (nviews > 0) {
@@ -579,11 +541,11 @@ extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const 
     }
     if (!p->dev_items) return PTB_EINVAL;                                   // ptb_volume_plan_upload comes first
     if (pos != p->pos || (long long)pos + B > p->n) return PTB_EUNSUPPORTED;   // off the planned sequence
-    if (p->configured && (in_dtype != p->in_dtype || nviews != p->nviews || packed != p->masks || reduction != p->reduction ||
+    if (p->configured && (dtype_arg != p->in_dtype || nviews != p->nviews || packed != p->masks || reduction != p->reduction ||
                           weight != p->weight || out != p->out))
         return PTB_EUNSUPPORTED;                                            // one configuration per image
     p->configured = true;
-    p->in_dtype = in_dtype; p->nviews = nviews; p->masks = packed; p->reduction = reduction; p->weight = weight; p->out = out;
+    p->in_dtype = dtype_arg; p->nviews = nviews; p->masks = packed; p->reduction = reduction; p->weight = weight; p->out = out;
     const size_t es = in_dtype == PTB_F32 ? 4 : 2;
     for (int b = 0; b < B; ++b) {
         p->tile_src[pos + b] = static_cast<const char*>(batch) + (size_t)b * (size_t)tile_stride * es;
@@ -612,7 +574,9 @@ extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const 
         }
         a.items = p->dev_items + g.item0;
         hipStream_t s = (hipStream_t)stream;
-        switch (in_dtype) {
+        if (src_cl) {   // PTB_SRC_CHANNELS_LAST: the same work-item table, one lane per voxel over all channels
+            cl3_launch_gather(a, t, (int)g.tiles.size(), in_dtype, mode, p->kind, g.n_items, s);
+        } else switch (in_dtype) {
             case PTB_F32: launch_gather_ld<1>(a, t, mode, vec, p->kind, g.n_items, s); break;
             case PTB_F16: launch_gather_ld<2>(a, t, mode, vec, p->kind, g.n_items, s); break;
             default: launch_gather_ld<3>(a, t, mode, vec, p->kind, g.n_items, s); break;

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "ptb_mirror_device.h"
+#include "ptb_volume_device.h"
 
 namespace ptb {
 
@@ -21,15 +22,7 @@ constexpr long long MIRROR_MAX_PLANE = 0x7fffffffLL - MIRROR_GRID_X * MIRROR_BLO
 
 // (ld_dtype, mirror_src, rev4 and the per-voxel de-augmentation mirror_reduce_voxels: ptb_mirror_device.h)
 
-struct MirrorArgs {
-    const void* src;
-    void* dst;
-    long long view_stride;  // elements between consecutive views in src (B * C * D * H * W); 0: src is the [B, C, ...] batch
-    int B, C, D, H, W;
-    int nv, masks;          // views, 3 bits each
-    int op;                 // PTB_RED_* (reduce)
-    float divisor;          // 1 for sum, V otherwise (reduce)
-};
+// (MirrorArgs, MirrorAccArgs: ptb_volume_device.h)
 
 // (unit index inside one [D, H, W] plane of PIX-runs) -> (z, y, x)
 template <int PIX>
@@ -106,19 +99,6 @@ __global__ __launch_bounds__(MIRROR_BLOCK) void volume_mirror_reduce_kernel(cons
 // accumulator region and stream order gives ptb_volume_accumulate's sequential fp32 order.  volume[:, roi] += t * weight with
 // t = mirror_reduce_voxels(..) rounded to the source type (round_src1: what ptb_volume_mirror_reduce stores), product rounded, then
 // added -- the same bits as ptb_volume_mirror_reduce followed by ptb_volume_accumulate.  blockIdx.y = channel.
-struct MirrorAccArgs {
-    float* volume;        // [C, D', H', W']
-    float* norm;          // [D', H', W']
-    const float* weight;  // [d, h, w]
-    const void* tiles;    // [V * B, C, d, h, w] of the source type
-    long long view_stride;
-    long long tile_off;   // element offset of tile b, view 0
-    int C, d, h, w, D, H, W;
-    int z0, y0, x0;
-    int nv, masks, op;
-    float divisor;
-};
-
 template <int LD, int OPK, int PIX>
 __global__ __launch_bounds__(MIRROR_BLOCK) void volume_mirror_accumulate_kernel(const MirrorAccArgs a) {
     const int wq = a.w / PIX;
@@ -232,6 +212,8 @@ extern "C" int ptb_volume_mirror(const void* src, int dtype, void* dst, int nvie
 
 extern "C" int ptb_volume_mirror_reduce(const void* src, int dtype, void* dst, int nviews, const int* masks, int reduction, int B,
                                         int C, int D, int H, int W, ptb_stream_t stream) {
+    const bool src_cl = (dtype & PTB_SRC_CHANNELS_LAST) != 0;
+    dtype &= ~PTB_SRC_CHANNELS_LAST;
     if (!src || !dst || B < 0 || C < 1 || D < 1 || H < 1 || W < 1) return PTB_EINVAL;
     if (dtype < PTB_F32 || dtype > PTB_BF16 || reduction < PTB_RED_SUM || reduction > PTB_RED_LOG1P) return PTB_EINVAL;
     int packed;
@@ -245,9 +227,13 @@ extern "C" int ptb_volume_mirror_reduce(const void* src, int dtype, void* dst, i
     a.view_stride = (long long)B * C * D * H * W;
     a.op = reduction;
     a.divisor = reduction == PTB_RED_SUM ? 1.0f : (float)nviews;
+    hipStream_t s = (hipStream_t)stream;
+    if (src_cl) {   // PTB_SRC_CHANNELS_LAST: one lane per output voxel over all channels, any shape
+        cl3_launch_reduce(a, dtype, s);
+        return check_launch();
+    }
     const bool vec = !g_force_scalar && W % 4 == 0 && aligned_run(src, dtype) && aligned_run(dst, dtype);
     const bool nonlinear = reduction >= PTB_RED_GMEAN;
-    hipStream_t s = (hipStream_t)stream;
     switch (dtype) {
         case PTB_F32: return nonlinear ? launch_reduce_ld<1, 1>(a, vec, s) : launch_reduce_ld<1, 0>(a, vec, s);
         case PTB_F16: return nonlinear ? launch_reduce_ld<2, 1>(a, vec, s) : launch_reduce_ld<2, 0>(a, vec, s);
@@ -260,6 +246,8 @@ extern "C" int ptb_volume_mirror_accumulate(float* volume, float* norm, const fl
                                             int B, int C, int d, int h, int w, int D, int H, int W, ptb_stream_t stream) {
     if (!volume || !norm || !weight || !tiles || !zs || !ys || !xs) return PTB_EINVAL;
     if (B < 0 || C < 1 || d < 1 || h < 1 || w < 1 || D < 1 || H < 1 || W < 1) return PTB_EINVAL;
+    const bool src_cl = (in_dtype & PTB_SRC_CHANNELS_LAST) != 0;
+    in_dtype &= ~PTB_SRC_CHANNELS_LAST;
     if (in_dtype < PTB_F32 || in_dtype > PTB_BF16 || reduction < PTB_RED_SUM || reduction > PTB_RED_LOG1P) return PTB_EINVAL;
     int packed;
     if (int rc = pack_masks(nviews, masks, packed)) return rc;
@@ -273,6 +261,16 @@ extern "C" int ptb_volume_mirror_accumulate(float* volume, float* norm, const fl
     a.C = C; a.d = d; a.h = h; a.w = w; a.D = D; a.H = H; a.W = W;
     a.nv = nviews; a.masks = packed; a.op = reduction;
     a.divisor = reduction == PTB_RED_SUM ? 1.0f : (float)nviews;
+    if (src_cl) {   // PTB_SRC_CHANNELS_LAST: one launch per tile as below, one lane per voxel over all channels
+        const long long tile_elems = (long long)C * d * h * w;
+        for (int b = 0; b < B; ++b) {
+            a.tile_off = (long long)b * tile_elems;
+            a.z0 = (int)zs[b]; a.y0 = (int)ys[b]; a.x0 = (int)xs[b];
+            cl3_launch_accum(a, in_dtype, (hipStream_t)stream);
+            if (int rc = check_launch()) return rc;
+        }
+        return PTB_OK;
+    }
     const bool base_vec = !g_force_scalar && w % 4 == 0 && W % 4 == 0 && aligned16(volume) && aligned16(norm) && aligned16(weight) &&
                           aligned_run(tiles, in_dtype);
     const bool nonlinear = reduction >= PTB_RED_GMEAN;

@@ -343,7 +343,7 @@ class _DeferredVolume:
         if self._pos == 0:
             self._config = config
         elif config != self._config:
-            raise RuntimeError(f"{what}: dtype / mirror / reduction {config} differ from the image's first batch {self._config}; one configuration "
+            raise RuntimeError(f"{what}: dtype / mirror / reduction / layout {config} differ from the image's first batch {self._config}; one configuration "
                                f"per image in deferred mode -- {_DEFER_HINT}")
 
     def _finished_result(self, what):
@@ -377,7 +377,9 @@ class VolumeMerger(_DeferredVolume):
     """Blend 3-D tile predictions into a full volume that lives in HBM (reference inference/tiles_3d.py:169-211).
 
     ``volume`` ``[C, D, H, W]``, ``norm_mask`` ``[1, D, H, W]`` and ``weight`` ``[1, d, h, w]`` are public fp32 tensors
-    on the GPU.  ``integrate_batch`` adds ``tile * weight`` tile after tile (bit-identical to the reference's loop).
+    on the GPU.  ``integrate_batch`` adds ``tile * weight`` tile after tile (bit-identical to the reference's loop).  A model output
+    in ``torch.channels_last_3d`` (float32 / float16 / bfloat16, on the merger's device) is read where it lies by ``integrate_batch``,
+    ``integrate_batch_deaugment`` and ``accumulate_single`` -- no dense or float32 copy, the same bits.
 
     ``crops=, defer=True[, result=]`` (keyword-only, opt-in): the deferred slab merge.  The merger keeps references to the model
     outputs instead of accumulating them; when the last tile over a z-slab of the plan is in, one launch reads every covering tile,
@@ -386,8 +388,8 @@ class VolumeMerger(_DeferredVolume):
     give, with no ``volume`` / ``norm_mask`` in memory.  ``result``: the arguments of ``merge_crop`` as a dict (``crop``, ``layout``,
     ``dtype``, ``argmax``); ``merge_crop`` called with the same arguments returns the tensor the slabs wrote.  The contract is
     strict: ``rois`` must be the next entries of ``crops``; batches are CUDA float32 / float16 / bfloat16 on the merger's device, read
-    as they are, and must stay alive and unmodified until their slabs are merged (``_merge_modes.HeldBatches``); dtype / mirror /
-    reduction are fixed by an image's first batch; ``merge`` / ``merge_crop`` come after the last tile; ``volume`` / ``norm_mask``
+    as they are (dense or ``torch.channels_last_3d``: the caller's tensor itself is held; other strides are copied), and must stay alive and unmodified until their slabs are merged (``_merge_modes.HeldBatches``); dtype / mirror /
+    reduction / layout are fixed by an image's first batch; ``merge`` / ``merge_crop`` come after the last tile; ``volume`` / ``norm_mask``
     do not exist.  Anything else raises and says to construct the merger without ``defer=True``.  The price of the mode is custody:
     ``peak_held_tiles`` (from the plan) is the most tiles held at once -- with z-major crops two z-layers of tiles, plus the batch in
     flight (98 tiles = 3.3 GB for 343 tiles of 4 x 128^3 float32; 8 x that with the 8 float32 views of ``"dhw"``).  No byte budget is
@@ -487,11 +489,16 @@ class VolumeMerger(_DeferredVolume):
         if tuple(batch.shape[1:]) != (self.channels, d, h, w):
             raise RuntimeError(f"tile batch of shape {tuple(batch.shape)} does not match [{'V*' if views else ''}B, {self.channels}, {d}, {h}, {w}]")
         B = self._next_rois(rois, what)
-        self._same_config((batch.dtype, tuple(views), code), what)
+        # a channels_last_3d model output is held and read where it lies (N.SRC_CHANNELS_LAST); any other strides are copied
+        layout = N.volume_layout(batch)
+        channels_last = layout == N.LAYOUT_CHANNELS_LAST
+        self._same_config((batch.dtype, tuple(views), code, "channels_last_3d" if channels_last else "dense"), what)
         if B == 0:
             return
-        if not batch.is_contiguous():
+        if layout == N.LAYOUT_OTHER:
             batch = batch.contiguous()          # (the copy is what is held)
+        if channels_last:
+            dtype |= N.SRC_CHANNELS_LAST
         plan, pos = self._plan, self._pos
         due = self._groups_done < plan.n_groups and int(plan.group_info[self._groups_done, 2]) < pos + B
         span = self._held.admit(batch, due)
@@ -536,6 +543,8 @@ class VolumeMerger(_DeferredVolume):
         """Accumulate one ``[C, d, h, w]`` prediction at ``roi`` (3 slices)."""
         if self._defer:
             return self.integrate_batch(tile.unsqueeze(0), [roi])
+        if self._channels_last(tile.unsqueeze(0)):
+            return self.integrate_batch(tile.unsqueeze(0), [roi])
         self._accumulate(tile.detach().to(device=self.volume.device, dtype=torch.float32).unsqueeze(0).contiguous(), [roi])
 
     def integrate_batch(self, batch: torch.Tensor, rois):
@@ -544,7 +553,37 @@ class VolumeMerger(_DeferredVolume):
             raise ValueError("Number of images in batch does not correspond to number of coordinates")
         if self._defer:
             return self._submit(batch, rois, (), 0, "VolumeMerger.integrate_batch")
+        if self._channels_last(batch):       # read where it lies: the identity view summed (exact), so no float32 / dense copy exists
+            return self._mirror_accumulate(batch.detach(), rois, (0,), N.RED_SUM, "VolumeMerger.integrate_batch")
         self._accumulate(batch.detach().to(device=self.volume.device, dtype=torch.float32).contiguous(), rois)
+
+    def _channels_last(self, batch):
+        """The batch is a channels_last_3d model output the kernels of ptb_volume_channels_last.hip read as it is."""
+        return (torch.is_tensor(batch) and batch.is_cuda and batch.device == self.volume.device and batch.dtype in N.DTYPE_CODES
+                and N.volume_layout(batch) == N.LAYOUT_CHANNELS_LAST)
+
+    def _mirror_accumulate(self, batch, rois, views, code, what):
+        """``ptb_volume_mirror_accumulate`` on a dense or channels_last_3d ``[V*B, C, d, h, w]`` batch of the accumulators' device."""
+        self._check_accumulators("VolumeMerger")
+        dtype = N.DTYPE_CODES[batch.dtype]
+        d, h, w = (int(s) for s in self.weight.shape[1:])
+        if tuple(batch.shape[1:]) != (self.channels, d, h, w):
+            raise RuntimeError(f"tile batch of shape {tuple(batch.shape)} does not match [{'V*' if len(views) > 1 else ''}B, {self.channels}, {d}, {h}, {w}]")
+        if N.volume_layout(batch) == N.LAYOUT_CHANNELS_LAST:
+            dtype |= N.SRC_CHANNELS_LAST
+        else:
+            batch = batch.contiguous()
+        starts = _roi_starts(rois, (d, h, w))
+        D, H, W = (int(s) for s in self.volume.shape[1:])
+        lib = N.load()
+        dev = self.volume.device
+        with N.on_device(dev):
+            rc = lib.ptb_volume_mirror_accumulate(self.volume.data_ptr(), self.norm_mask.data_ptr(), self.weight.data_ptr(), batch.data_ptr(),
+                                                  dtype, len(views), N.int_array(views), code, starts[0].ctypes.data_as(N._i64p),
+                                                  starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), len(rois),
+                                                  self.channels, d, h, w, D, H, W, N.stream_ptr(dev))
+        N.bump()
+        N.check(rc, what)
 
     def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean"):
         """Fused ``integrate_batch(mirror_volume_deaugment(batch, mirror, reduction), rois)``, bit for bit.
@@ -574,18 +613,7 @@ class VolumeMerger(_DeferredVolume):
             raise RuntimeError(f"tile batch of shape {tuple(batch.shape)} does not match [V*B, {self.channels}, {d}, {h}, {w}]")
         if batch.device != self.volume.device:
             raise ValueError(f"integrate_batch_deaugment: batch is on {batch.device}, the accumulators on {self.volume.device}")
-        batch = batch.detach().contiguous()
-        starts = _roi_starts(rois, (d, h, w))
-        D, H, W = (int(s) for s in self.volume.shape[1:])
-        lib = N.load()
-        dev = self.volume.device
-        with N.on_device(dev):
-            rc = lib.ptb_volume_mirror_accumulate(self.volume.data_ptr(), self.norm_mask.data_ptr(), self.weight.data_ptr(), batch.data_ptr(),
-                                                  dtype, len(views), N.int_array(views), code, starts[0].ctypes.data_as(N._i64p),
-                                                  starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), len(rois),
-                                                  self.channels, d, h, w, D, H, W, N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "VolumeMerger.integrate_batch_deaugment")
+        self._mirror_accumulate(batch.detach(), rois, views, code, "VolumeMerger.integrate_batch_deaugment")
 
     def merge(self) -> torch.Tensor:
         """``volume / norm_mask`` as a new tensor (no eps clamp: never-covered voxels are NaN)."""
@@ -708,6 +736,8 @@ class HostBackedVolumeMerger(VolumeMerger):
         if code is None:
             raise ValueError(f"reduction={reduction!r} cannot be fused into the tile merge")
         batch = batch.to(device=self._volume.device)
+        if N.volume_layout(batch) == N.LAYOUT_CHANNELS_LAST:
+            batch = batch.contiguous()      # torch's sum over the stacked views follows the strides: reduce as the dense batch does
         stack = torch.stack([flip_view(c, m) for c, m in zip(torch.chunk(batch, len(views)), views)])
         if self._defer:
             return self._deferred_blend(_host.reduce_stack(stack, code), rois, (batch.dtype, tuple(views), code), "VolumeMerger.integrate_batch_deaugment")

@@ -8,7 +8,8 @@ The spec is the torch expression the functions replace::
 A view is a 3-bit mask: bit 0 flips W (dim 4), bit 1 flips H (dim 3), bit 2 flips D (dim 2).  The views of a ``mirror`` string are
 every mask made of its axes' bits, in increasing order ("dhw": masks 0..7).  Batches are chunk-major: row ``v * B + b`` holds view
 ``v`` of tile ``b``.  CUDA tensors run the HIP kernels of ``ptb_volume_tta.hip`` (one launch each); host tensors take the same
-expression in torch ops (``_host``), as everywhere in the package.  The kernels are inference only: a CUDA tensor that requires grad is
+expression in torch ops (``_host``), as everywhere in the package.  A ``torch.channels_last_3d`` model output is de-augmented where it
+lies (``ptb_volume_channels_last.hip``; fusable reductions), with the bits of its dense copy.  The kernels are inference only: a CUDA tensor that requires grad is
 refused with NotImplementedError, while a host tensor keeps torch's autograd through the torch ops.
 ``VolumeSlicer.split_device(.., mirror=)`` writes the augmented batch straight from the volume and
 ``VolumeMerger.integrate_batch_deaugment`` un-flips, reduces and blends in one pass per tile.
@@ -102,12 +103,18 @@ def mirror_volume_deaugment(y: torch.Tensor, mirror: str = "dhw",
     if code is None and not (callable(reduction) or reduction in {None, "None", "none"}):
         raise KeyError(f"Unsupported reduction mode {reduction}")
     if y.device.type != "cuda":
+        if code is not None and N.volume_layout(y) == N.LAYOUT_CHANNELS_LAST:
+            y = y.contiguous()      # torch's sum over the stacked views follows the strides (1 ulp with 8 views): reduce as the dense batch does
         stack = torch.stack([flip_view(c, m) for c, m in zip(torch.chunk(y, V), views)])
     else:
         dtype = _check_volume_batch(y, "mirror_volume_deaugment")
         B = y.shape[0] // V
         if code is not None:
-            y = y.contiguous()
+            # a channels_last_3d model output is read where it lies (N.SRC_CHANNELS_LAST); any other strides are copied, as ever
+            if N.volume_layout(y) == N.LAYOUT_CHANNELS_LAST:
+                dtype |= N.SRC_CHANNELS_LAST
+            else:
+                y = y.contiguous()
             out = torch.empty((B,) + tuple(y.shape[1:]), device=y.device, dtype=y.dtype)
             _, C, D, H, W = y.shape
             lib = N.load()
