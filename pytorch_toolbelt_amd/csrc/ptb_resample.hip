@@ -548,7 +548,10 @@ __global__ __launch_bounds__(256) void resize_nearest_kernel(const float* __rest
     }
 }
 
-// F.interpolate(mode="nearest-exact"): src = min(floor((dst + 0.5) * in / out), in - 1) (ATen nearest_neighbor_exact_compute_source_index)
+// F.interpolate(mode="nearest-exact"): src = min(floor((dst + 0.5) * in / out), in - 1) (ATen nearest_neighbor_exact_compute_source_index),
+// scale and product in fp32.  Where (dst + 0.5) * in / out is an integer k exactly (a tie: 2 -> 141 at dst 70, ...) and the fp32 scale
+// lies below in / out, the product stays below k and pixel k - 1 is taken.  ATen's device kernel selects the same pixels there (checked on
+// every such pair up to 300 x 300, tests/test_resample_sweep_gpu.py); ATen's CPU kernel differs at 32 of those pairs, where it takes pixel k.
 __device__ __forceinline__ int nearest_exact_src(int dst, float scale, int n_in) { return min((int)floorf(((float)dst + 0.5f) * scale), n_in - 1); }
 
 template <bool BWD>
