@@ -40,20 +40,10 @@ __global__ __launch_bounds__(16 * CH) void band_plan_kernel(const ViewArgs a, co
     constexpr int LDS_SET = lds_tiles(NV, CODES) * CW * CH;
     __shared__ __attribute__((aligned(16))) float lds[LDS_SET ? LDS_SET * (DB ? 2 : 1) : 4];
     const int tid = threadIdx.x;
-    unsigned bid = blockIdx.x;
-    if (a.ncells == 1) {   // XCD-aware order (A/B, ptb_set_tunable key 10): every XCD walks a contiguous eighth of the (item, channel) list
-        const unsigned per_xcd = ((unsigned)a.total_chunks + 7u) / 8u;
-        bid = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-        if (bid >= (unsigned)a.total_chunks) return;
-    }
-    int c = bid % a.C;
-    unsigned item = bid / a.C;
-    if (a.chan_loop) { c = 0; item = bid; }      // (one workgroup per item, all channels: the identity-view instances)
-    else if (a.ncells == 2) {   // channel-major: consecutive workgroups = neighbouring chunks of ONE channel plane
-        const unsigned n_items = (unsigned)a.total_chunks / (unsigned)a.C;
-        c = bid / n_items;
-        item = bid - c * n_items;
-    }
+    const unsigned bid = blockIdx.x;
+    int c = 0;
+    unsigned item = bid;                          // (a.chan_loop: one workgroup per item, all channels -- the identity-view instances)
+    if (!a.chan_loop) { c = bid % a.C; item = bid / a.C; }
     const BandItem* __restrict__ it = items + item;
     const int cwch = it->cwch, partial = it->partial;
     const int cw = cwch & 0xffff, ch = cwch >> 16;
@@ -64,7 +54,6 @@ __global__ __launch_bounds__(16 * CH) void band_plan_kernel(const ViewArgs a, co
     if (act && !partial) nfull = *reinterpret_cast<const float4*>(a.norm_full + pix);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     const int nt = it->ntiles;
-    const bool rot = PF && a.rot_views && (item & 1u);      // (wave-uniform; A/B of the view issue order, ptb_set_tunable key 22)
     // ALL (round 6): one or two row-preserving views -- the plain loop without TTA (`integrate_batch(pred, crops)`, tiles.py:321-339), the
     // flips of one axis -- bring only 16-32 bytes per lane and covering tile, so one tile ahead leaves a CU with ~32 KiB in flight and a
     // workgroup's <= 4 covering tiles a chain of exposed latencies (0.45 ms per 5000 x 5000 image: 54 % of its bytes' time).  These
@@ -134,12 +123,8 @@ __global__ __launch_bounds__(16 * CH) void band_plan_kernel(const ViewArgs a, co
             const unsigned long long cv = it->cover[0];
             const int slot = (int)(cv & 0xffff), lx = (int)((cv >> 16) & 0xffff), ly = (int)((cv >> 32) & 0xffff);
             if (act) wnxt = *reinterpret_cast<const float4*>(a.weight + (long long)(ly + r) * a.W + lx + 4 * q);
-            if (NV >= 2 && rot)
-                gather_load_raw<CH, NV, CODES, LD, NV / 2>(static_cast<const float*>(t.src[slot]), (long long)c * a.H * a.W, t.vs[slot], a.nviews, a.codes, a.H,
-                                                           a.W, lx, ly, cw, ch, tid, nxt);
-            else
-                gather_load_raw<CH, NV, CODES, LD>(static_cast<const float*>(t.src[slot]), (long long)c * a.H * a.W, t.vs[slot], a.nviews, a.codes, a.H, a.W, lx,
-                                                   ly, cw, ch, tid, nxt);
+            gather_load_raw<CH, NV, CODES, LD>(static_cast<const float*>(t.src[slot]), (long long)c * a.H * a.W, t.vs[slot], a.nviews, a.codes, a.H, a.W, lx,
+                                               ly, cw, ch, tid, nxt);
         }
     }
     for (int e = 0; e < nt; ++e) {
@@ -155,12 +140,8 @@ __global__ __launch_bounds__(16 * CH) void band_plan_kernel(const ViewArgs a, co
                 const unsigned long long cn = it->cover[e + 1];
                 const int sn = (int)(cn & 0xffff), nlx = (int)((cn >> 16) & 0xffff), nly = (int)((cn >> 32) & 0xffff);
                 if (act) wnxt = *reinterpret_cast<const float4*>(a.weight + (long long)(nly + r) * a.W + nlx + 4 * q);
-                if (NV >= 2 && rot)
-                    gather_load_raw<CH, NV, CODES, LD, NV / 2>(static_cast<const float*>(t.src[sn]), (long long)c * a.H * a.W, t.vs[sn], a.nviews, a.codes, a.H,
-                                                               a.W, nlx, nly, cw, ch, tid, nxt);
-                else
-                    gather_load_raw<CH, NV, CODES, LD>(static_cast<const float*>(t.src[sn]), (long long)c * a.H * a.W, t.vs[sn], a.nviews, a.codes, a.H, a.W,
-                                                       nlx, nly, cw, ch, tid, nxt);
+                gather_load_raw<CH, NV, CODES, LD>(static_cast<const float*>(t.src[sn]), (long long)c * a.H * a.W, t.vs[sn], a.nviews, a.codes, a.H, a.W,
+                                                   nlx, nly, cw, ch, tid, nxt);
             }
             const bool db = DB && a.lds_db;      // (wave-uniform; ptb_set_tunable key 25 for same-process A/B runs)
             val = gather_tail<CH, NV, CODES, OPK>(v, a.nviews, a.codes, cw, ch, a.op, a.divisor, db ? lds + (e & 1) * LDS_SET : lds, tid, db ? false : e + 1 < nt);
@@ -570,7 +551,6 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
     a.weight = weight; a.merged = merged; a.norm_full = norm_full;
     a.in_dtype = in_dtype;
     a.round_src = (dtype_arg & PTB_ROUND_SRC) ? 1 : 0;
-    a.rot_views = g_band_rot_views;
     a.lds_db = g_band_lds_db;
     a.H = p->th; a.W = p->tw; a.C = p->C;
     a.dst_chan_stride = (long long)p->H * p->W;
@@ -601,8 +581,7 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
             a.chan_loop = (V == 1 && codes == CODES_ID && g_band_chan_loop && (in_dtype != PTB_F32 ? g_band_half_pf >= 1 : g_band_half_pf >= 2)) ? 1 : 0;
             const long long blocks = (long long)g.item_cnt * (a.chan_loop ? 1 : p->C);
             if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
-            a.ncells = a.chan_loop ? 0 : g_band_xcd; a.total_chunks = (int)blocks;
-            launch_plan(a, p->dev_items + g.item_off, gt, a.ncells == 1 ? (int)(8 * ((blocks + 7) / 8)) : (int)blocks, p->ch, (hipStream_t)stream);   // (rounded up only where the kernel's XCD order guards the surplus)
+            launch_plan(a, p->dev_items + g.item_off, gt, (int)blocks, p->ch, (hipStream_t)stream);
             const int rc = check_launch();
             if (rc != PTB_OK) return rc;
             ++p->launched;
@@ -716,7 +695,6 @@ extern "C" int ptb_band_plan_submit_rank(ptb_band_plan* p, int pos, int B, const
 
 int ptb::g_band_chan_loop = 1;     // ptb_set_tunable key 27: identity-view band launches run one workgroup per item over all channels (window / normaliser loaded once per pixel)
 int ptb::g_band_lds_db = 1;        // ptb_set_tunable key 25: the prefetching band instances alternate between two sets of LDS tiles (one barrier per covering tile instead of two)
-int ptb::g_band_rot_views = 0;     // ptb_set_tunable key 22 (A/B): odd work items of the band plan kernel issue their view loads starting at view NV / 2
 int ptb::g_band_half_pf = 2;       // ptb_set_tunable key 21: the band plan kernel requests covering tile e + 1 before it finishes tile e -- 0: never (round 4's
                                    // instances), 1: for half / bf16 sources, 2: for fp32 sources as well
 int ptb::g_rank_finish_fused = 1;   // ptb_set_tunable key 18: 0 = ptb_rect_add + ptb_merge_div_ex launches (A/B, bit-identity test)

@@ -43,31 +43,24 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// tunables (ptb_set_tunable)
-extern int g_chunk_rows;    // 16 | 32 | 64
-extern int g_force_scalar;  // 0 | 1
-extern int g_loss_grid_cap;  // workgroups per loss-kernel launch
-extern int g_ms_tiled;       // 0 | 1: LDS-staged multiscale kernel
-extern int g_ms_tile_w;      // 64 | 128: output tile width of the fused multiscale kernel
-extern int g_rank_finish_fused;  // 0 | 1: one-launch finish of a rank's image (ShardedTileMerger, deferred bands)
-extern int g_rs_xcd_map;     // 0 | 1: XCD-contiguous tile order in the Lovasz radix scatter
-extern int g_lovasz_rankdot;     // 0 | 1: last level of the key-only Lovasz forward without a scatter
-extern int g_lovasz_fused_dot;   // 0 | 1: the binning scatter of the Lovasz training path also evaluates the loss
-extern int g_nt_grad_stores; // 0 | 1: non-temporal gradient stores in the fused loss backward
-extern int g_stats_pk;       // 0 | 1: statistics-only / focal-only instances of the packed streaming loss kernel
-extern int g_focal_pk_grid;  // workgroups of the packed-fp32 fused loss forward
-extern int g_focal_pk;       // 0 | 1: A/B of the packed-fp32 instance of the fused loss forward
-extern int g_fused_pix2;     // 0 | 1: A/B of the fused loss forward with 2 pixels per lane
-extern int g_loss_prefetch;   // 0 | 1: the fused loss forward fetches the next pixel group while it computes the current one
-extern int g_smf_bwd_stash;  // 0 | 2 | 4: softmax focal backward with the per-class terms kept in registers, pixels per lane
-extern int g_band_rows;     // 32 | 64: rows per work item of band plans created from now on (A/B)
-extern int g_band_half_pf;  // 0 | 1 | 2: the band plan kernel prefetches the next covering tile (1: half / bf16 sources only, 2: fp32 too)
-extern int g_band_chan_loop; // 0 | 1: identity-view band launches, one workgroup per item over all channels
-extern int g_band_lds_db;   // 0 | 1: double-buffered LDS tiles in the prefetching band plan instances
-extern int g_band_rot_views;  // 0 | 1: odd work items of the band plan kernel issue their view loads starting at view NV / 2 (A/B)
-extern int g_band_xcd;      // 0 | 1: XCD-aware workgroup order in the band plan kernel (A/B)
-extern int g_ms_strip;       // 0 | 1..64: XCD-aware tile order of the fused multiscale kernel, strip width in tile columns
-extern int g_ms_tile_rows;   // 64 | 32: output tile height of the fused multiscale kernel
-extern int g_nt_loads;      // 0 | 1: non-temporal streaming loads in the linear view kernels
+// tunables: ptb_set_tunable(key, value) -- the key, the values it takes, what it selects
+extern int g_chunk_rows;         //  0: 16 | 32 | 64, chunk rows of the view / accumulate kernels
+extern int g_force_scalar;       //  1: 0 | 1, element-wise kernels instead of the 16-byte ones
+extern int g_ms_tiled;           //  3: 0 | 1, LDS-staged multiscale kernel
+extern int g_loss_grid_cap;      //  4: >= 0, workgroups per loss-kernel launch (0: the per-kernel default)
+extern int g_ms_tile_rows;       //  6: 16 | 32 | 64, output tile height of the fused multiscale kernel
+extern int g_smf_bwd_stash;      //  7: 0 | 2 | 4, softmax focal backward with the per-class terms kept in registers, pixels per lane
+extern int g_ms_strip;           //  9: 0 | 1..64, XCD-aware tile order of the fused multiscale kernel, strip width in tile columns
+extern int g_band_rows;          // 11: 32 | 64, rows per work item of band plans created from now on
+extern int g_ms_tile_w;          // 15: 64 | 128, output tile width of the fused multiscale kernel
+extern int g_nt_grad_stores;     // 16: 0 | 1, non-temporal gradient stores in the fused loss backward
+extern int g_rs_xcd_map;         // 17: 0 | 1 (bit 0 of the value), XCD-contiguous tile order in the Lovasz radix scatter
+extern int g_rank_finish_fused;  // 18: 0 | 1, one-launch finish of a rank's image (ShardedTileMerger, deferred bands)
+extern int g_lovasz_fused_dot;   // 19: 0 | 1, the binning scatter of the Lovasz training path also evaluates the loss
+extern int g_stats_pk;           // 20: 0 | 1, statistics-only / focal-only instances of the packed streaming loss kernel
+extern int g_band_half_pf;       // 21: clamped to 0..2, the band plan kernel prefetches the next covering tile (1: half / bf16 sources only, 2: fp32 too)
+extern int g_lovasz_rankdot;     // 23: 0 | 1, last level of the key-only Lovasz forward without a scatter
+extern int g_band_lds_db;        // 25: 0 | 1, double-buffered LDS tiles in the prefetching band plan instances
+extern int g_band_chan_loop;     // 27: 0 | 1, identity-view band launches, one workgroup per item over all channels
 
 }  // namespace ptb

@@ -9,8 +9,6 @@ namespace ptb {
 static thread_local std::string g_last_error;
 int g_chunk_rows = 32;  // 32x64 chunks (512-thread workgroups) measured best on MI355X (profiles/)
 int g_force_scalar = 0;
-int g_nt_loads = 1;
-int g_band_xcd = 0;   // ptb_set_tunable key 10
 int g_band_rows = 64; // ptb_set_tunable key 11: 64-row work items (1024-thread workgroups, 256-byte segments for the transposing views too)
                       // measured 0.8-1 % faster than 32 rows on every memory region of the device (2.046 vs 2.058, 2.270 vs 2.290 ms)
 int g_ms_tiled = 1;
@@ -33,7 +31,6 @@ __global__ __launch_bounds__(256) void merge_div_kernel(const float* __restrict_
     const v4f* ex4 = reinterpret_cast<const v4f*>(extra);
     v4f* o4 = reinterpret_cast<v4f*>(out);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < hw4; i += stride) {
-        // everything here is touched exactly once: non-temporal loads (g_nt_loads) keep the streams out of L2 / MALL
         const v4f n = NT ? __builtin_nontemporal_load(&n4[i]) : n4[i];
         for (int c = 0; c < C; ++c) {
             v4f v = NT ? __builtin_nontemporal_load(&im4[c * ics4 + i]) : im4[c * ics4 + i];
@@ -194,118 +191,52 @@ extern "C" int ptb_version(void) { return 102; }
 
 extern "C" const char* ptb_last_hip_error(void) { return g_last_error.c_str(); }
 
+// ptb_set_tunable: one row per key -- the variable (described at its extern in ptb_common.h) and the values it takes.
+namespace {
+enum Check {
+    BOOL,    // stores value ? 1 : 0
+    BIT0,    // stores value & 1
+    RANGE,   // accepts lo <= value <= hi
+    CLAMP,   // stores value clamped to lo .. hi
+    SET,     // accepts the values listed (a repeated entry fills the row)
+};
+struct Tunable { int key; int* var; Check check; int v[3]; };
+const Tunable kTunables[] = {
+    {0, &g_chunk_rows, SET, {16, 32, 64}},
+    {1, &g_force_scalar, BOOL, {}},
+    {3, &g_ms_tiled, BOOL, {}},
+    {4, &g_loss_grid_cap, RANGE, {0, 0x7fffffff}},
+    {6, &g_ms_tile_rows, SET, {16, 32, 64}},
+    {7, &g_smf_bwd_stash, SET, {0, 2, 4}},
+    {9, &g_ms_strip, RANGE, {0, 64}},
+    {11, &g_band_rows, SET, {32, 64, 64}},
+    {15, &g_ms_tile_w, SET, {64, 128, 128}},
+    {16, &g_nt_grad_stores, BOOL, {}},
+    {17, &g_rs_xcd_map, BIT0, {}},
+    {18, &g_rank_finish_fused, BOOL, {}},
+    {19, &g_lovasz_fused_dot, BOOL, {}},
+    {20, &g_stats_pk, BOOL, {}},
+    {21, &g_band_half_pf, CLAMP, {0, 2}},
+    {23, &g_lovasz_rankdot, BOOL, {}},
+    {25, &g_band_lds_db, BOOL, {}},
+    {27, &g_band_chan_loop, BOOL, {}},
+};
+}  // namespace
+
 extern "C" int ptb_set_tunable(int key, int value) {
-    if (key == 0) {
-        if (value != 16 && value != 32 && value != 64) return PTB_EINVAL;
-        g_chunk_rows = value;
+    for (const Tunable& t : kTunables) {
+        if (t.key != key) continue;
+        switch (t.check) {
+            case BOOL: value = value ? 1 : 0; break;
+            case BIT0: value &= 1; break;
+            case RANGE: if (value < t.v[0] || value > t.v[1]) return PTB_EINVAL; break;
+            case CLAMP: value = std::min(std::max(value, t.v[0]), t.v[1]); break;
+            case SET: if (value != t.v[0] && value != t.v[1] && value != t.v[2]) return PTB_EINVAL; break;
+        }
+        *t.var = value;
         return PTB_OK;
     }
-    if (key == 1) {
-        g_force_scalar = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 2) {
-        g_nt_loads = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 3) {
-        g_ms_tiled = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 4) {
-        if (value < 0) return PTB_EINVAL;
-        g_loss_grid_cap = value;
-        return PTB_OK;
-    }
-    if (key == 5) {
-        g_fused_pix2 = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 12) {
-        if (value < 0 || value > 2) return PTB_EINVAL;
-        g_focal_pk = value;
-        return PTB_OK;
-    }
-    if (key == 15) {
-        if (value != 64 && value != 128) return PTB_EINVAL;
-        g_ms_tile_w = value;
-        return PTB_OK;
-    }
-    if (key == 16) {
-        g_nt_grad_stores = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 17) {
-        g_rs_xcd_map = value & 7;       // bit 0: XCD-contiguous tile order; bit 1 (A/B only): histogram loads behind the ranking
-        return PTB_OK;
-    }
-    if (key == 18) {
-        g_rank_finish_fused = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 19) {
-        g_lovasz_fused_dot = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 20) {
-        g_stats_pk = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 21) {
-        g_band_half_pf = value < 0 ? 0 : (value > 2 ? 2 : value);
-        return PTB_OK;
-    }
-    if (key == 22) {
-        g_band_rot_views = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 27) {
-        g_band_chan_loop = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 25) {
-        g_band_lds_db = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 23) {
-        g_lovasz_rankdot = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 13) {
-        if (value < 1) return PTB_EINVAL;
-        g_focal_pk_grid = value;
-        return PTB_OK;
-    }
-    if (key == 6) {
-        if (value != 16 && value != 32 && value != 64) return PTB_EINVAL;
-        g_ms_tile_rows = value;
-        return PTB_OK;
-    }
-    if (key == 11) {
-        if (value != 32 && value != 64) return PTB_EINVAL;
-        g_band_rows = value;
-        return PTB_OK;
-    }
-    if (key == 10) {
-        if (value < 0 || value > 2) return PTB_EINVAL;
-        g_band_xcd = value;
-        return PTB_OK;
-    }
-    if (key == 9) {
-        if (value < 0 || value > 64) return PTB_EINVAL;
-        g_ms_strip = value;
-        return PTB_OK;
-    }
-    if (key == 8) {
-        g_loss_prefetch = value ? 1 : 0;
-        return PTB_OK;
-    }
-    if (key == 7) {
-        if (value != 0 && value != 2 && value != 4) return PTB_EINVAL;
-        g_smf_bwd_stash = value;
-        return PTB_OK;
-    }
-    return PTB_EINVAL;
+    return PTB_EINVAL;      // (unknown key)
 }
 
 extern "C" int ptb_merge_div_ex(const float* image, const float* norm, float* out, int C, int64_t HW, int64_t image_cs,

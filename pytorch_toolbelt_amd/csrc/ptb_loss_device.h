@@ -380,7 +380,9 @@ static inline int zero_sums(double* sums, int row, int* error_flag, hipStream_t 
 // Measured on MI355X (tools/ab_losses.py): the streaming kernels (focal fwd/bwd, softmax focal) gain ~10 % from an
 // oversubscribed grid (32 workgroups per CU, one pixel group per wave), the statistics kernels lose from it (more
 // per-workgroup LDS reductions + atomics), so they keep 8 per CU.
-constexpr int kGridStream = 256 * 32, kGridStats = 256 * 8;
+// The packed fused forward (seg_focal_pk_kernel) pays a per-workgroup prologue / epilogue / slot atomics: 2 workgroups per CU
+// (512 / 768 / 1024 / 2048 workgroups: 112.6 / 120.9 / 122.8 / 121.5 us at cfg4).
+constexpr int kGridStream = 256 * 32, kGridStats = 256 * 8, kGridFocalPk = 512;
 static inline int grid_for_groups(long long groups, int dflt) {
     const long long want = (groups + 3) / 4;
     const long long cap = g_loss_grid_cap > 0 ? g_loss_grid_cap : dflt;

@@ -200,17 +200,16 @@ __global__ __launch_bounds__(256, SHARE ? 3 : 1) void seg_loss_fwd_reg_kernel(co
     if (a.tail_counter) region_tail(a, lds);
 }
 
-// Straight-line variant for the common case -- hard labels, C <= CREG, HW % 256 == 0 (every lane of every wave holds 4 valid
-// pixels), softmax or given probabilities, and for FOCAL the default focal configuration (gamma 2, nothing else).  rocprof on
-// the generic kernel above: 1 630 vector instructions per wave and pixel group (25 per element) and 71 % VALU busy -- the
-// run-time switches (prob, c < C, ok, ignore) cut the unrolled class loop into hundreds of basic blocks.  Here everything
-// that varies is a template parameter, classes beyond C are padded with -inf / 0 (they contribute exact zeros, so only
-// their loads are guarded), and no control flow diverges: about 8 (statistics) / 20 (+ focal) vector instructions per
-// element (2 pixels per lane, 98 VGPRs, measured the same as 4: 105 vs 106 us).  T_c is a label count: taken per WAVE from the compare mask the class loop needs anyway (s_bcnt1 on the scalar
-// unit).  FOCAL shares the exp with the softmax as described at `share` above, with the same exact redo of extreme elements.
-template <int CREG, int PROB, bool FOCAL, bool IGN, int PIX = 4, bool TERM = true, bool FULL = false, bool PF = false>   // FULL: C == CREG
-__global__ __launch_bounds__(256, FOCAL ? 3 : 1) void seg_fwd_lean_kernel(const SegArgs a) {
-    static_assert(!FOCAL || PROB == PROB_SOFTMAX, "the shared exp needs the softmax numerators");
+// Straight-line statistics kernel for the common case -- hard labels, C <= CREG, HW % 256 == 0 (every lane of every wave holds 4
+// valid pixels), softmax or given probabilities.  rocprof on the generic kernel above: 1 630 vector instructions per wave and pixel
+// group (25 per element) and 71 % VALU busy -- the run-time switches (prob, c < C, ok, ignore) cut the unrolled class loop into
+// hundreds of basic blocks.  Here everything that varies is a template parameter, classes beyond C are padded with -inf / 0 (they
+// contribute exact zeros, so only their loads are guarded), and no control flow diverges: about 8 vector instructions per element.
+// T_c is a label count: taken per WAVE from the compare mask the class loop needs anyway (s_bcnt1 on the scalar unit).
+// (The fused focal + statistics forward and the ignore-free softmax statistics run seg_focal_pk_kernel below.)
+template <int CREG, int PROB, bool IGN>
+__global__ __launch_bounds__(256, 1) void seg_fwd_lean_kernel(const SegArgs a) {
+    constexpr int PIX = 4;
     extern __shared__ float lds[];  // [4 waves][3][C]
     const int lane = threadIdx.x & 63, wave = wave_id();
     const int C = a.C;
@@ -219,15 +218,14 @@ __global__ __launch_bounds__(256, FOCAL ? 3 : 1) void seg_fwd_lean_kernel(const 
     int nT[CREG];
 #pragma unroll
     for (int c = 0; c < CREG; ++c) { aI[c] = 0.f; aP[c] = 0.f; nT[c] = 0; }
-    double f_loss = 0.0, f_term = 0.0;
     const long long per_img = a.HW / (64 * PIX);
     const long long groups = per_img * a.B;
     const long long stride = (long long)gridDim.x * 4;
     // one pixel group = 64 * PIX pixels of one image: its CREG class planes and labels are fetched as one batch of loads
-    auto fetch = [&](long long g, float (&xv)[CREG][PIX], long long (&l64)[PIX], long long& base) {
+    auto fetch = [&](long long g, float (&xv)[CREG][PIX], long long (&l64)[PIX]) {
         const int b = (int)(g / per_img);
         const long long i0 = (g - (long long)b * per_img) * (64 * PIX) + (long long)lane * PIX;
-        base = (long long)b * C * a.HW + i0;
+        const long long base = (long long)b * C * a.HW + i0;
         const long long* lp = a.labels + (long long)b * a.HW + i0;
 #pragma unroll
         for (int k = 0; k < PIX; k += 2) {
@@ -239,10 +237,10 @@ __global__ __launch_bounds__(256, FOCAL ? 3 : 1) void seg_fwd_lean_kernel(const 
             const float pad = PROB == PROB_SOFTMAX ? -INFINITY : 0.f;
 #pragma unroll
             for (int k = 0; k < PIX; ++k) xv[c][k] = pad;
-            if (FULL || c < C) load_px<PIX>(a.logits + base + (long long)c * a.HW, xv[c], true);
+            if (c < C) load_px<PIX>(a.logits + base + (long long)c * a.HW, xv[c], true);
         }
     };
-    auto process = [&](float (&xv)[CREG][PIX], const long long (&l64)[PIX], const long long base) {
+    auto process = [&](float (&xv)[CREG][PIX], const long long (&l64)[PIX]) {
         int lab[PIX];
         bool valid[PIX];
         {
@@ -255,22 +253,14 @@ __global__ __launch_bounds__(256, FOCAL ? 3 : 1) void seg_fwd_lean_kernel(const 
             }
             if (bad) raise_label_error(a.error_flag);
         }
-        float inv[PIX], em[PIX];
-        // FOCAL: the class loop below is exact only while every sigmoid and its complement stay normal fp32 numbers when formed
-        // as u / (u + em), em / (u + em): all logits of the lane's pixels in [-80, 60] (then u = exp(x - m) >= e^-140 / e^-80 ... is
-        // covered by x - m >= -80 as well).  A wave holding anything else redoes its focal sums from the re-read logits with the
-        // generic formula (never on sane logits); the region statistics need no such care.
-        bool tame = true;
+        float inv[PIX];
 #pragma unroll
         for (int k = 0; k < PIX; ++k) {
-            inv[k] = 1.0f; em[k] = 1.0f;
+            inv[k] = 1.0f;
             if (PROB == PROB_SOFTMAX) {
-                float m = xv[0][k], lo = xv[0][k];
+                float m = xv[0][k];
 #pragma unroll
-                for (int c = 1; c < CREG; ++c) {
-                    m = fmaxf(m, xv[c][k]);
-                    if (FOCAL) lo = fminf(lo, (FULL || c < C) ? xv[c][k] : lo);   // (the padding is -inf)
-                }
+                for (int c = 1; c < CREG; ++c) m = fmaxf(m, xv[c][k]);
                 const float M = m * kLog2e;
                 float d = 0.f;
 #pragma unroll
@@ -280,71 +270,28 @@ __global__ __launch_bounds__(256, FOCAL ? 3 : 1) void seg_fwd_lean_kernel(const 
                     d += u;
                 }
                 inv[k] = rcp(d);
-                if (FOCAL) {
-                    em[k] = ex2(-M);
-                    tame = tame && (m <= 60.f) && (lo >= -80.f) && (lo - m >= -80.f);
-                }
             }
         }
-        float lsum = 0.f, fsum = 0.f;    // lsum: sum of f * log2(p_t), scaled by -ln 2 once per group
 #pragma unroll
         for (int c = 0; c < CREG; ++c) {
 #pragma unroll
             for (int k = 0; k < PIX; ++k) {
                 const float u = xv[c][k];
                 const bool hit = lab[k] == c;
-                if (FOCAL) {
-                    const float r = rcp(u + em[k]);
-                    const float ps = u * r, qs = em[k] * r;                  // sigmoid(x), 1 - sigmoid(x)
-                    const float pt = hit ? ps : qs, omp = hit ? qs : ps;
-                    const float f = omp * omp;
-                    lsum = __builtin_fmaf(f, lg2(pt), lsum);
-                    if (TERM) fsum += f;
-                }
                 const float pm = (IGN && !valid[k]) ? 0.f : u;
                 aP[c] = __builtin_fmaf(pm, inv[k], aP[c]);
                 aI[c] = __builtin_fmaf(hit ? u : 0.f, inv[k], aI[c]);
                 nT[c] += __popcll(__ballot(hit));
             }
         }
-        if (FOCAL) {
-            lsum *= -kLn2;
-            if (__any(!tame)) {   // the whole wave: exact sums from the re-read logits
-                const FocalCfg cfg = focal_cfg(a);
-                lsum = 0.f; fsum = 0.f;
-#pragma unroll
-                for (int k = 0; k < PIX; ++k)
-                    for (int c = 0; c < C; ++c)
-                        lsum += focal_one<true>(a.logits[base + (long long)c * a.HW + k], lab[k] == c ? 1.f : 0.f, false, 1.0f, cfg, fsum);
-            }
-            f_loss += (double)lsum;
-            f_term += (double)fsum;
-        }
     };
-    const long long g0 = (long long)blockIdx.x * 4 + wave;
-    if constexpr (PF) {
-        // two register buffers: the loads of the NEXT group are in flight while this one is computed (the compute phase of a
-        // group is ~1 us of VALU time during which the wave would otherwise have nothing outstanding)
-        float xa[CREG][PIX], xb[CREG][PIX];
-        long long la[PIX], lb[PIX], ba = 0, bb = 0;
-        if (g0 < groups) fetch(g0, xa, la, ba);
-        for (long long g = g0; g < groups; g += 2 * stride) {
-            const bool hb = g + stride < groups;
-            if (hb) fetch(g + stride, xb, lb, bb);
-            process(xa, la, ba);
-            if (g + 2 * stride < groups) fetch(g + 2 * stride, xa, la, ba);
-            if (hb) process(xb, lb, bb);
-        }
-    } else {
-        for (long long g = g0; g < groups; g += stride) {
-            float xv[CREG][PIX];
-            long long l64[PIX], base;
-            fetch(g, xv, l64, base);
-            process(xv, l64, base);
-        }
+    for (long long g = (long long)blockIdx.x * 4 + wave; g < groups; g += stride) {
+        float xv[CREG][PIX];
+        long long l64[PIX];
+        fetch(g, xv, l64);
+        process(xv, l64);
     }
     double* slot = a.sums + (size_t)(blockIdx.x % SUM_SLOTS) * (2 + 3 * C);
-    if (FOCAL) block_add2(f_loss, f_term, slot, lane, wave);
 #pragma unroll
     for (int c = 0; c < CREG; ++c) {
         if (c < C) {
@@ -361,8 +308,8 @@ __global__ __launch_bounds__(256, FOCAL ? 3 : 1) void seg_fwd_lean_kernel(const 
 }
 
 
-// The cfg4 instance of the fused forward (hard labels, softmax statistics + default focal, 2 pixels per lane) with the vector
-// instruction count cut by a quarter (rocprofv3 on seg_fwd_lean_kernel<.., FOCAL>: VALU 71 % busy, the kernel is co-bound by issue):
+// The fused forward (hard labels, softmax statistics + default focal: gamma 2, nothing else; 2 pixels per lane), written so that the
+// vector instruction count stays low (rocprofv3 on its select-per-element predecessor: VALU 71 % busy, co-bound by issue):
 //  * everything per element is written on PAIRS (the lane's two pixels) so that the plain arithmetic issues as packed fp32
 //    (v_pk_add / v_pk_mul / v_pk_fma_f32: two elements per full-rate slot); only v_exp / v_rcp / v_log stay per element;
 //  * no per-element select on "is this the label's class": every element is summed with the t = 0 formula
@@ -371,7 +318,9 @@ __global__ __launch_bounds__(256, FOCAL ? 3 : 1) void seg_fwd_lean_kernel(const 
 //    (its u picked from the registers by a 4-level select tree on the label's bits: 15 selects per pixel instead of 3 per element);
 //  * I_c and T_c get one LDS add per pixel each into the lane's own column of a per-wave [class][lane] table (ds_add_f32, no
 //    bank conflicts, no cross-lane traffic) instead of a select + fma and a compare + ballot per element.
-// Results agree with seg_fwd_lean_kernel to rounding (same exp / rcp / log instructions, another association of the sums).
+// The class loop is exact only while every sigmoid and its complement stay normal fp32 numbers when formed as u / (u + em),
+// em / (u + em): all logits of the lane's pixels in [-80, 60] and x - m >= -80.  A wave holding anything else redoes its focal sums
+// from the re-read logits with the generic formula (never on sane logits); the region statistics need no such care.
 typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f rcp2(v2f x) { return v2f{rcp(x.x), rcp(x.y)}; }
 __device__ __forceinline__ v2f lg22(v2f x) { return v2f{lg2(x.x), lg2(x.y)}; }
@@ -381,8 +330,8 @@ __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elem
 // FOCAL = false: the same streaming skeleton for the region statistics alone (DiceLoss / JaccardLoss on logits + hard labels): one
 // exp per element, one rcp per pixel, P in packed registers, I and T through the per-lane LDS columns.
 // STATS = false: the focal sums alone (BinaryFocalLoss in its default configuration on label maps): no softmax denominator, no P / I / T.
-template <int CREG, bool TERM, bool FULL, bool PF = false, bool FOCAL = true, bool STATS = true>   // PF: the next pixel group's loads are in flight while this one is computed
-__global__ __launch_bounds__(256, PF ? 2 : 4) void seg_focal_pk_kernel(const SegArgs a) {
+template <int CREG, bool TERM, bool FULL, bool FOCAL = true, bool STATS = true>   // FULL: C == CREG
+__global__ __launch_bounds__(256, 4) void seg_focal_pk_kernel(const SegArgs a) {
     static_assert(FOCAL || STATS, "nothing to compute");
     extern __shared__ float lds[];  // [4 waves][2][CREG][64] per-lane columns of I and T; afterwards [4][3][C] wave sums + the tail's scratch
     const int lane = threadIdx.x & 63, wave = wave_id();
@@ -498,27 +447,12 @@ __global__ __launch_bounds__(256, PF ? 2 : 4) void seg_focal_pk_kernel(const Seg
         f_loss += (double)lsum;
         f_term += (double)fsum;
     };
-    const long long g0 = (long long)blockIdx.x * 4 + wave;
-    if constexpr (PF) {
-        v2f xa[CREG], xb[CREG];
-        longlong2 la{}, lb{};
-        long long ba = 0, bb = 0;
-        if (g0 < groups) fetch(g0, xa, la, ba);
-        for (long long g = g0; g < groups; g += 2 * stride) {
-            const bool hb = g + stride < groups;
-            if (hb) fetch(g + stride, xb, lb, bb);
-            process(xa, la, ba);
-            if (g + 2 * stride < groups) fetch(g + 2 * stride, xa, la, ba);
-            if (hb) process(xb, lb, bb);
-        }
-    } else {
-        for (long long g = g0; g < groups; g += stride) {
-            v2f xv[CREG];
-            longlong2 l2;
-            long long base;
-            fetch(g, xv, l2, base);
-            process(xv, l2, base);
-        }
+    for (long long g = (long long)blockIdx.x * 4 + wave; g < groups; g += stride) {
+        v2f xv[CREG];
+        longlong2 l2;
+        long long base;
+        fetch(g, xv, l2, base);
+        process(xv, l2, base);
     }
     double* slot = a.sums + (size_t)(blockIdx.x % SUM_SLOTS) * (2 + 3 * C);
     if constexpr (FOCAL) block_add2(f_loss, f_term, slot, lane, wave);
@@ -1230,7 +1164,7 @@ __global__ __launch_bounds__(256, 3) void seg_fused_bwd_shared_kernel(const SegA
 }
 
 // Straight-line instance of the fused backward for the common case (hard labels, C <= CREG padded with -inf, HW % 256 == 0,
-// default focal configuration; see seg_fwd_lean_kernel): no divergent control flow, only the loads and the stores of the
+// default focal configuration; see seg_focal_pk_kernel): no divergent control flow, only the loads and the stores of the
 // classes beyond C are guarded.
 template <int CREG>
 __global__ __launch_bounds__(256, 3) void seg_fused_bwd_lean_kernel(const SegArgs a, const float* __restrict__ coef, const float* __restrict__ gI,
@@ -1720,7 +1654,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIX == 2 ? 
 }
 
 // Straight-line instances of the softmax focal loss for the common case (C <= CREG padded with -inf, HW % 256 == 0, gamma = 2,
-// no class weights, no reduced threshold; see seg_fwd_lean_kernel).  u = exp(x - m) stays in the registers; the BCE term's
+// no class weights, no reduced threshold; see seg_focal_pk_kernel).  u = exp(x - m) stays in the registers; the BCE term's
 // sigmoid comes from u and em = exp(-m) like in the wave-uniform fast path of softmax_focal_kernel, and a wave that holds a
 // pixel with |m| > 60 or a logit 80 below its maximum falls back to that kernel's exact formulas for the whole group.
 template <int CREG, int MODE>
@@ -1981,14 +1915,9 @@ __global__ __launch_bounds__(256) void region_epilogue_kernel(const EpiArgs a) {
 
 // ------------------------------------------------------------------------------------------------ host side
 int g_loss_grid_cap = 0;  // 0 = per-kernel default; otherwise workgroups per launch (ptb_set_tunable key 4)
-int g_loss_prefetch = 0;   // ptb_set_tunable key 8: register double buffering in the fused loss forward (measured: no gain, 0.146 vs 0.141-0.145 ms)
 int g_smf_bwd_stash = 4;  // ptb_set_tunable key 7: 4 pixels per lane (251 VGPRs, 2 waves per SIMD) measured 0.372 ms fwd+bwd at cfg4, 2 pixels 0.54, the two-pass kernel 0.41-0.48
 int g_nt_grad_stores = 1;    // ptb_set_tunable key 16: non-temporal stores of the gradient in the fused backward (A/B: 333 -> 315 us fwd+bwd at cfg4; the other backward kernels always use them)
-int g_focal_pk_grid = 512;   // ptb_set_tunable key 13: workgroups of seg_focal_pk_kernel (2 per CU measured best: per-workgroup prologue / epilogue / slot atomics)
 int g_stats_pk = 1;       // ptb_set_tunable key 20: Dice / Jaccard statistics and the default BinaryFocalLoss on label maps take the packed streaming kernel (0: the lean kernels)
-int g_focal_pk = 1;       // ptb_set_tunable key 12 (2 = with register prefetch of the next pixel group): packed-fp32 / per-pixel-correction instance of the fused forward (seg_focal_pk_kernel); 0 = seg_fwd_lean_kernel
-int g_fused_pix2 = 1;     // ptb_set_tunable key 5: fused focal + statistics forward with 2 pixels per lane (120 VGPRs, 4 waves per SIMD,
-                          // instead of 4 pixels: 163 VGPRs, 3 waves): 0.164-0.171 vs 0.173-0.186 ms per FocalDiceJaccardLoss forward at cfg4
 }  // namespace ptb
 
 using namespace ptb;
@@ -2083,7 +2012,7 @@ static int seg_loss_fwd_launch(SegArgs& a, hipStream_t s) {
                else hipLaunchKernelGGL((seg_stats_dense_lean_kernel<PROB_IDENTITY, false>), dgrid, block, shmem, s, a); }
         return check_launch();
     }
-    // straight-line kernels for the common case (see seg_fwd_lean_kernel)
+    // straight-line kernels for the common case (see seg_fwd_lean_kernel, seg_focal_pk_kernel)
     if (!g_force_scalar && labels && !dense && vec && HW % 256 == 0 && C <= 16 && (what & SEG_STATS) && !(flags & SEG_ELEMWISE) &&
         (prob == PROB_SOFTMAX || prob == PROB_IDENTITY)) {
         const bool ign = flags & SEG_HAS_IGNORE;
@@ -2092,27 +2021,21 @@ static int seg_loss_fwd_launch(SegArgs& a, hipStream_t s) {
         const dim3 lgrid(grid_for_groups(HW / 256 * B, kGridStats));
         const bool no_term = flags & SEG_NO_TERM;
 #define PTB_LEAN(CR) do { \
-            if (plain_focal) { const dim3 g2(grid_for_groups(HW / 128 * B, kGridStats)); \
+            if (plain_focal) { \
                                const size_t pk_lds = std::max(shmem, (size_t)4 * 2 * CR * 64 * sizeof(float)); \
-                               const dim3 gpk(grid_for_groups(HW / 128 * B, g_focal_pk_grid)); \
-                               if (g_fused_pix2 && g_focal_pk == 2 && no_term && C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true, true>), gpk, block, pk_lds, s, a); \
-                               else if (g_fused_pix2 && g_focal_pk && no_term && C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true>), gpk, block, pk_lds, s, a); \
-                               else if (g_fused_pix2 && g_focal_pk && no_term) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, false>), gpk, block, pk_lds, s, a); \
-                               else if (g_fused_pix2 && g_focal_pk) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, true, false>), gpk, block, pk_lds, s, a); \
-                               else if (!g_fused_pix2) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, true, false, 4, true, false>), lgrid, block, shmem, s, a); \
-                               else if (no_term && C == CR && g_loss_prefetch) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, true, false, 2, false, true, true>), g2, block, shmem, s, a); \
-                               else if (no_term && C == CR) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, true, false, 2, false, true>), g2, block, shmem, s, a); \
-                               else if (no_term) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, true, false, 2, false, false>), g2, block, shmem, s, a); \
-                               else hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, true, false, 2, true, false>), g2, block, shmem, s, a); } \
+                               const dim3 gpk(grid_for_groups(HW / 128 * B, kGridFocalPk)); \
+                               if (no_term && C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true>), gpk, block, pk_lds, s, a); \
+                               else if (no_term) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, false>), gpk, block, pk_lds, s, a); \
+                               else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, true, false>), gpk, block, pk_lds, s, a); } \
             else if (prob == PROB_SOFTMAX && !ign && g_stats_pk && HW % 128 == 0) { \
                                const size_t pk_lds = std::max(shmem, (size_t)4 * 2 * CR * 64 * sizeof(float)); \
-                               const dim3 gpk(grid_for_groups(HW / 128 * B, g_focal_pk_grid)); \
-                               if (C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true, false, false>), gpk, block, pk_lds, s, a); \
-                               else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, false, false, false>), gpk, block, pk_lds, s, a); } \
-            else if (prob == PROB_SOFTMAX) { if (ign) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, false, true>), lgrid, block, shmem, s, a); \
-                                             else hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, false, false>), lgrid, block, shmem, s, a); } \
-            else { if (ign) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_IDENTITY, false, true>), lgrid, block, shmem, s, a); \
-                   else hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_IDENTITY, false, false>), lgrid, block, shmem, s, a); } } while (0)
+                               const dim3 gpk(grid_for_groups(HW / 128 * B, kGridFocalPk)); \
+                               if (C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true, false>), gpk, block, pk_lds, s, a); \
+                               else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, false, false>), gpk, block, pk_lds, s, a); } \
+            else if (prob == PROB_SOFTMAX) { if (ign) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, true>), lgrid, block, shmem, s, a); \
+                                             else hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, false>), lgrid, block, shmem, s, a); } \
+            else { if (ign) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_IDENTITY, true>), lgrid, block, shmem, s, a); \
+                   else hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_IDENTITY, false>), lgrid, block, shmem, s, a); } } while (0)
         if (what == SEG_STATS || plain_focal) {
             if (C <= 4) PTB_LEAN(4); else if (C <= 8) PTB_LEAN(8); else PTB_LEAN(16);
             return check_launch();
@@ -2123,12 +2046,12 @@ static int seg_loss_fwd_launch(SegArgs& a, hipStream_t s) {
         // BinaryFocalLoss() on label maps in its default configuration: the packed streaming kernel of the fused loss without its
         // statistics half (the shared exponent shift max_c x keeps one exp per element for sigmoid and its complement)
         const bool term = !(flags & SEG_NO_TERM);
-        const dim3 gpk(grid_for_groups(HW / 128 * B, g_focal_pk_grid));
+        const dim3 gpk(grid_for_groups(HW / 128 * B, kGridFocalPk));
 #define PTB_FPK(CR) do { const size_t pk_lds = std::max(shmem, (size_t)4 * 2 * CR * 64 * sizeof(float)); \
-                         if (term) { if (C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, true, true, false, true, false>), gpk, block, pk_lds, s, a); \
-                                     else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, true, false, false, true, false>), gpk, block, pk_lds, s, a); } \
-                         else { if (C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true, false, true, false>), gpk, block, pk_lds, s, a); \
-                                else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, false, false, true, false>), gpk, block, pk_lds, s, a); } } while (0)
+                         if (term) { if (C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, true, true, true, false>), gpk, block, pk_lds, s, a); \
+                                     else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, true, false, true, false>), gpk, block, pk_lds, s, a); } \
+                         else { if (C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true, true, false>), gpk, block, pk_lds, s, a); \
+                                else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, false, true, false>), gpk, block, pk_lds, s, a); } } while (0)
         if (C <= 4) PTB_FPK(4); else if (C <= 8) PTB_FPK(8); else PTB_FPK(16);
 #undef PTB_FPK
         return check_launch();

@@ -365,8 +365,7 @@ __global__ __launch_bounds__(NW * 64) void rs_scatter_kernel(const unsigned* __r
     static_assert(!(GRAD && KEYONLY), "the gradient variant carries a value");
     static_assert(!IOTA || (!GRAD && !KEYONLY), "IOTA is the pair sort's first pass");
     __shared__ unsigned skey[RS_TILE], sval[KEYONLY ? 1 : RS_TILE];
-    const unsigned lin = tile_of_block(xcd_map & 1);
-    const bool late = (xcd_map & 2) != 0;     // (A/B: ptb_set_tunable(17, 3) puts the histogram loads back behind the ranking)
+    const unsigned lin = tile_of_block(xcd_map);
     const int seg = lin / T, tile = lin % T;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long t0 = (long long)tile * RS_TILE;
@@ -380,7 +379,7 @@ __global__ __launch_bounds__(NW * 64) void rs_scatter_kernel(const unsigned* __r
     // what the digit threads need from the scanned histograms does not depend on the keys: requested first, consumed after the
     // ranking (issued behind the barrier these loads were ~2 us of exposed latency per tile)
     unsigned rs = 0, before = 0, tile_before = 0;
-    if (threadIdx.x < 256 && !late) {
+    if (threadIdx.x < 256) {
         // this digit's elements in earlier spans of the segment, and in the whole segment
         const int my_span = tile / RS_SPAN;
         for (int sp = 0; sp < spans; ++sp) {
@@ -446,14 +445,8 @@ __global__ __launch_bounds__(NW * 64) void rs_scatter_kernel(const unsigned* __r
             const float jk = jaccard_at(G, kf, (float)(before_u + fg));
             // the left neighbour's J_k: one DPP move (wave_shr:1) and a v_readlane for the carry -- as ds_bpermute shuffles these were two
             // more trips through the LDS pipeline per item, next to the ranking's own
-            float left_j, last_j;
-            if (xcd_map & 4) {       // (A/B: ptb_set_tunable(17, 5) = the ds_bpermute shuffles)
-                left_j = __shfl_up(jk, 1);
-                last_j = __shfl(jk, 63);
-            } else {
-                left_j = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(jk), __float_as_int(jk), 0x138, 0xF, 0xF, false));
-                last_j = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(jk), 63));
-            }
+            const float left_j = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(jk), __float_as_int(jk), 0x138, 0xF, 0xF, false));
+            const float last_j = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(jk), 63));
             const float jprev = lane == 0 ? carry : left_j;
             carry = last_j;
             v[j] = __float_as_uint(jk - jprev);                  // lovasz.py:32-33
@@ -511,15 +504,6 @@ __global__ __launch_bounds__(NW * 64) void rs_scatter_kernel(const unsigned* __r
             const unsigned c = wave_hist[w][threadIdx.x];
             wave_hist[w][threadIdx.x] = tot;
             tot += c;
-        }
-        if (late) {
-            const int my_span = tile / RS_SPAN;
-            for (int sp = 0; sp < spans; ++sp) {
-                const unsigned c = span_tot[((long long)seg * spans + sp) * 256 + threadIdx.x];
-                before += sp < my_span ? c : 0u;
-                rs += c;
-            }
-            tile_before = hist[((long long)seg * T + tile) * 256 + threadIdx.x];
         }
     }
     const unsigned excl = block_inclusive_scan_n<NW>(tot, wave_tot) - tot;
@@ -585,7 +569,7 @@ __global__ __launch_bounds__(NW * 64) void lovasz_rankdot_kernel(const unsigned*
     __shared__ unsigned base_all[256], base_fg[256];            // position / foreground count in front of the tile's first key of digit d
     __shared__ unsigned wave_tot[4];
     __shared__ double wacc[NW];
-    const unsigned lin = tile_of_block(xcd_map & 1);
+    const unsigned lin = tile_of_block(xcd_map);
     const int seg = lin / T, tile = lin % T;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long t0 = (long long)tile * RS_TILE;

@@ -66,7 +66,6 @@ struct ViewArgs {
     int round_src;       // PTB_ROUND_SRC: the reduced value is rounded to the (half / bf16) source type before it is blended
     int chan_loop;       // band plan kernel, identity view: one workgroup per work item walks all channels (ptb_set_tunable key 27)
     int lds_db;          // band plan kernel, prefetching instances: alternate between two sets of LDS tiles (ptb_set_tunable key 25)
-    int rot_views;       // band plan kernel (A/B, ptb_set_tunable key 22): odd work items issue their view loads starting at view NV / 2
 };
 
 enum { MODE_REDUCE = 0, MODE_PERVIEW = 1, MODE_ACCUM = 2 };
@@ -453,9 +452,7 @@ __device__ __forceinline__ float4 gather_reduce(const float* __restrict__ src, l
 // gather_reduce in two steps: the loads of one covering tile as raw values (8 bytes per view for half / bf16 -- 16 registers for the
 // eight d4 views -- 16 bytes for fp32), held while the PREVIOUS tile is still being transposed, reduced and blended, and their
 // widening into gather_tail's input.  band_plan_kernel<.., PF> requests tile e + 1 before it finishes tile e.
-// ROT: the loads are ISSUED starting at view ROT (then ROT + 1, ..., wrapping) -- which register receives which view, and so every bit of
-// the result, is unchanged; an A/B on whether workgroups that all walk the views in one order collide in DRAM (ptb_set_tunable key 22).
-template <int CH, int NV, int CODES, int LD, int ROT = 0>
+template <int CH, int NV, int CODES, int LD>
 __device__ __forceinline__ void gather_load_raw(const float* __restrict__ src, long long plane, long long view_stride, int nv_rt, int codes_rt, int H,
                                                 int W, int lx, int ly, int cw, int ch, int tid, typename RawOf<LD>::type (&raw)[NV]) {
     constexpr int QPR = CH / 4;
@@ -466,8 +463,7 @@ __device__ __forceinline__ void gather_load_raw(const float* __restrict__ src, l
     const int nv = CODES >= 0 ? NV : nv_rt;
     const int codes = CODES >= 0 ? CODES : codes_rt;
 #pragma unroll
-    for (int kk = 0; kk < NV; ++kk) {
-        const int k = (kk + ROT) % NV;
+    for (int k = 0; k < NV; ++k) {
         raw[k] = typename RawOf<LD>::type{};
         if (k < nv) {
             const int code = (codes >> (3 * k)) & 7;

@@ -577,9 +577,7 @@ static void launch_plain_ch(const ViewArgs& a, int blocks, hipStream_t s, bool n
             if (a.in_dtype == PTB_F16) { PTB_PLAIN_LD(NV, CODES, 2); break; }                                     \
             if (a.in_dtype == PTB_BF16) { PTB_PLAIN_LD(NV, CODES, 3); break; }                                    \
         }                                                                                                         \
-        if (nonlinear) hipLaunchKernelGGL((view_plain_kernel<CH, NV, CODES, 1, MODE, 1>), grid, block, 0, s, a);  \
-        else if (g_nt_loads) hipLaunchKernelGGL((view_plain_kernel<CH, NV, CODES, 0, MODE, 1>), grid, block, 0, s, a); \
-        else hipLaunchKernelGGL((view_plain_kernel<CH, NV, CODES, 0, MODE, 0>), grid, block, 0, s, a);            \
+        PTB_PLAIN_LD(NV, CODES, 1);                                                                               \
     } while (0)
     if constexpr (MODE == MODE_PERVIEW) {
         hipLaunchKernelGGL((view_plain_kernel<CH, 1, -1, 0, MODE_PERVIEW, 1>), grid, block, 0, s, a);
@@ -609,9 +607,7 @@ static void launch_accum_ch(const ViewArgs& a, const CellArgs& g, int blocks, hi
             if (a.in_dtype == PTB_F16) { PTB_ACCUM_LD(NV, CODES, 2); break; }                                     \
             if (a.in_dtype == PTB_BF16) { PTB_ACCUM_LD(NV, CODES, 3); break; }                                    \
         }                                                                                                         \
-        if (nonlinear) hipLaunchKernelGGL((view_accum_kernel<CH, NV, CODES, 1, 1>), grid, block, 0, s, a, g);     \
-        else if (g_nt_loads) hipLaunchKernelGGL((view_accum_kernel<CH, NV, CODES, 0, 1>), grid, block, 0, s, a, g); \
-        else hipLaunchKernelGGL((view_accum_kernel<CH, NV, CODES, 0, 0>), grid, block, 0, s, a, g);               \
+        PTB_ACCUM_LD(NV, CODES, 1);                                                                               \
     } while (0)
     if (a.nviews == 1 && a.codes == CODES_ID) PTB_ACCUM(1, CODES_ID);
     else if (a.nviews == 2 && a.codes == CODES_FLIPLR) PTB_ACCUM(2, CODES_FLIPLR);

@@ -62,6 +62,34 @@ def test_argument_validation_without_gpu():
     assert lib.ptb_resize_bilinear(None, None, 1, 4, 4, 8, 8, 0, None) == -1
 
 
+def test_tunable_table_without_gpu():
+    """ptb_set_tunable is one table of the surviving keys: the retired A/B switches (2, 5, 8, 10, 12, 13, 22) are unknown keys now --
+    even their former defaults are refused --, key 17 keeps bit 0 of its value only, and every validated key accepts and refuses what
+    it did before.  Host-only: the setter touches no device."""
+    from pytorch_toolbelt_amd import _native as N
+
+    lib = N.load()
+    defaults = {0: 32, 6: 32, 7: 4, 9: 64, 11: 64, 15: 128, 17: 1, 21: 2}
+    try:
+        for key, former_default in ((2, 1), (5, 1), (8, 0), (10, 0), (12, 1), (13, 512), (22, 0)):
+            assert lib.ptb_set_tunable(key, former_default) == -1, key
+        assert lib.ptb_set_tunable(24, 1) == -1 and lib.ptb_set_tunable(-1, 0) == -1      # (never known)
+        assert lib.ptb_set_tunable(17, 0) == 0 and lib.ptb_set_tunable(17, 1) == 0
+        assert lib.ptb_set_tunable(17, 7) == 0 and lib.ptb_set_tunable(17, 1) == 0          # (nothing depends on bits 1-2)
+        for key, accepted, rejected in ((0, (16, 32, 64), (48, 0)), (6, (16, 32, 64), (48,)), (7, (0, 2, 4), (1, 3)), (9, (0, 1, 64), (65, -1)),
+                                        (11, (32, 64), (48, 16)), (15, (64, 128), (96,)), (4, (0, 2048), (-1,))):
+            for v in accepted:
+                assert lib.ptb_set_tunable(key, v) == 0, (key, v)
+            for v in rejected:
+                assert lib.ptb_set_tunable(key, v) == -1, (key, v)
+        for v in (-5, 0, 1, 2, 9):           # key 21 clamps to 0..2, the boolean keys normalise: no value is refused
+            assert lib.ptb_set_tunable(21, v) == 0 and lib.ptb_set_tunable(1, v) == 0, v
+    finally:
+        for key, v in defaults.items():
+            assert lib.ptb_set_tunable(key, v) == 0, key
+        assert lib.ptb_set_tunable(1, 0) == 0 and lib.ptb_set_tunable(4, 0) == 0
+
+
 def test_device_decides_and_the_hip_path_never_falls_back():
     """The contract of the two implementations: the DEVICE the caller names decides.  CPU tensors / device="cpu" take the host
     (torch-op) path like the reference does; anything CUDA takes the HIP kernels and fails LOUDLY when they cannot run -- a missing

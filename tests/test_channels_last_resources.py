@@ -33,10 +33,12 @@ def test_no_other_kernels_in_the_translation_unit(report):
 
 @pytest.mark.parametrize("unit, kernel, count", [
     ("ptb_bandplan.hip.txt", "band_plan_kernel", 156),
-    ("ptb_views.hip.txt", "view_accum_kernel", 91),
-    ("ptb_views.hip.txt", "view_plain_kernel", 81),
+    ("ptb_views.hip.txt", "view_accum_kernel", 91 - 3 * 7),
+    ("ptb_views.hip.txt", "view_plain_kernel", 81 - 3 * 6),
 ])
 def test_planar_kernels_keep_the_parent_commits_instances(forced_build, unit, kernel, count):
-    """Instance counts of the planar kernels as compiled from the parent commit (they read dense batches exactly as before)."""
+    """Instance counts of the planar kernels as compiled when the channels-last kernels arrived (they read dense batches exactly as before);
+    the two view kernels less their linear fp32 instances with temporal loads, which nothing selects any more: 3 chunk heights x 7 view
+    groups of view_accum_kernel, 3 x 6 of view_plain_kernel."""
     hits = {k: v for k, v in _report(Path(forced_build["remarks_dir"]) / unit).items() if ("%d%s" % (len(kernel), kernel)) in k}
     assert len(hits) == count

@@ -70,10 +70,8 @@ def main():
         "d4": list(DEAUGMENT_VIEWS["d4"]),
         "transposing x4 + id x4": [N.TRANSPOSE, N.ROT90_CW, N.ROT90_CCW, N.ANTITRANSPOSE, N.IDENT, N.IDENT, N.IDENT, N.IDENT],
     }
-    for ch, nt in ((64, 0), (64, 1), (32, 0), (32, 1), (16, 0), (16, 1)):
+    for ch in (64, 32, 16):
         lib.ptb_set_tunable(0, ch)
-        lib.ptb_set_tunable(2, nt)
-        ch = f"{ch} nt={nt}"
         for name, views in view_sets.items():
             t = timeit(lambda i: V._raw_deaug_reduce(bufs[i], views, N.RED_MEAN), args.reps, nbuf)
             rows.append((f"CH={ch} deaug_reduce {name} -> [8,4,512,512]", nbytes / t / 1e9, t))
@@ -84,10 +82,8 @@ def main():
         t = timeit(lambda i: merger.integrate_batch(bufs[i][:8], crops_row), args.reps, nbuf)
         rows.append((f"CH={ch} integrate_batch (1 view) row of 8", nbytes / 8 / t / 1e9, t))
     lib.ptb_set_tunable(0, 32)
-    for nt in (0, 1):
-        lib.ptb_set_tunable(2, nt)
-        t = timeit(lambda i: merger.merge(), args.reps, nbuf)
-        rows.append((f"merge 4x5120x5120 (r image+norm, w out) nt={nt}", (2 * merger.image.numel() + merger.norm_mask.numel()) * 4 / t / 1e9, t))
+    t = timeit(lambda i: merger.merge(), args.reps, nbuf)
+    rows.append(("merge 4x5120x5120 (r image+norm, w out)", (2 * merger.image.numel() + merger.norm_mask.numel()) * 4 / t / 1e9, t))
     # d4 augment [8,3,512,512] -> [64,3,512,512]: read 25 MB, write 201 MB
     from pytorch_toolbelt_amd.inference import tta
     xa = [torch.randn((8, 3, T, T), device=dev) for _ in range(nbuf)]
