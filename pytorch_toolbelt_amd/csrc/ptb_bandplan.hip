@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "ptb_dispatch.h"
 #include "ptb_view_device.h"
 
 namespace ptb {
@@ -169,47 +170,17 @@ __global__ __launch_bounds__(16 * CH) void band_plan_kernel(const ViewArgs a, co
 
 static void launch_plan(const ViewArgs& a, const BandItem* items, const GroupTiles& t, int blocks, int ch, hipStream_t s) {
     const dim3 grid(blocks), block(16 * ch);
-    const bool nonlinear = a.op >= PTB_RED_GMEAN;
-#define PTB_PLAN_PF(NV, CODES, LD)                                                                                  \
-    do {                                                                                                            \
-        if (ch == 64) {                                                                                             \
-            if (nonlinear) hipLaunchKernelGGL((band_plan_kernel<NV, CODES, 1, LD, 64, true>), grid, block, 0, s, a, items, t); \
-            else hipLaunchKernelGGL((band_plan_kernel<NV, CODES, 0, LD, 64, true>), grid, block, 0, s, a, items, t);       \
-        } else if (nonlinear) hipLaunchKernelGGL((band_plan_kernel<NV, CODES, 1, LD, PLAN_CH, true>), grid, block, 0, s, a, items, t);    \
-        else hipLaunchKernelGGL((band_plan_kernel<NV, CODES, 0, LD, PLAN_CH, true>), grid, block, 0, s, a, items, t);              \
-    } while (0)
-#define PTB_PLAN_LD(NV, CODES, LD)                                                                                  \
-    do {                                                                                                            \
-        if (ch == 64) {                                                                                             \
-            if (nonlinear) hipLaunchKernelGGL((band_plan_kernel<NV, CODES, 1, LD, 64>), grid, block, 0, s, a, items, t); \
-            else hipLaunchKernelGGL((band_plan_kernel<NV, CODES, 0, LD, 64>), grid, block, 0, s, a, items, t);       \
-        } else if (nonlinear) hipLaunchKernelGGL((band_plan_kernel<NV, CODES, 1, LD>), grid, block, 0, s, a, items, t);    \
-        else hipLaunchKernelGGL((band_plan_kernel<NV, CODES, 0, LD>), grid, block, 0, s, a, items, t);              \
-    } while (0)
-#define PTB_PLAN(NV, CODES)                                                                                         \
-    do {                                                                                                            \
-        if (a.in_dtype == PTB_F16) { if (g_band_half_pf) PTB_PLAN_PF(NV, CODES, 2); else PTB_PLAN_LD(NV, CODES, 2); }      \
-        else if (a.in_dtype == PTB_BF16) { if (g_band_half_pf) PTB_PLAN_PF(NV, CODES, 3); else PTB_PLAN_LD(NV, CODES, 3); } \
-        else if (g_band_half_pf >= 2) PTB_PLAN_PF(NV, CODES, 1);                                                    \
-        else PTB_PLAN_LD(NV, CODES, 1);                                                                             \
-    } while (0)
-#define PTB_PLAN_RT(NV, CODES) /* view codes read at run time: no prefetching instance (it would spill) */          \
-    do {                                                                                                            \
-        if (a.in_dtype == PTB_F16) PTB_PLAN_LD(NV, CODES, 2);                                                       \
-        else if (a.in_dtype == PTB_BF16) PTB_PLAN_LD(NV, CODES, 3);                                                 \
-        else PTB_PLAN_LD(NV, CODES, 1);                                                                             \
-    } while (0)
-    if (a.nviews == 1 && a.codes == CODES_ID) PTB_PLAN(1, CODES_ID);
-    else if (a.nviews == 2 && a.codes == CODES_FLIPLR) PTB_PLAN(2, CODES_FLIPLR);
-    else if (a.nviews == 2 && a.codes == CODES_FLIPUD) PTB_PLAN(2, CODES_FLIPUD);
-    else if (a.nviews == 3 && a.codes == CODES_FLIPS) PTB_PLAN(3, CODES_FLIPS);
-    else if (a.nviews == 4 && a.codes == CODES_D2) PTB_PLAN(4, CODES_D2);
-    else if (a.nviews == 8 && a.codes == CODES_D4) PTB_PLAN(8, CODES_D4);
-    else PTB_PLAN_RT(8, -1);
-#undef PTB_PLAN
-#undef PTB_PLAN_RT
-#undef PTB_PLAN_LD
-#undef PTB_PLAN_PF
+    // the prefetching instances (tunable 21): 1 = half / bf16 sources only, 2 = fp32 sources too
+    const bool prefetch = a.in_dtype == PTB_F16 || a.in_dtype == PTB_BF16 ? g_band_half_pf != 0 : g_band_half_pf >= 2;
+    with_view_set(a.nviews, a.codes, [&](auto nv, auto codes) { with_src_dtype(a.in_dtype, [&](auto ld) {
+        with_reduction(a.op, [&](auto opk) { with_value<64, PLAN_CH>(ch, [&](auto chv) {
+            // view codes read at run time (CODES = -1): no prefetching instance (it would spill)
+            with_bool(prefetch && codes() >= 0, [&](auto pf) {
+                if constexpr (codes() >= 0 || !pf())
+                    hipLaunchKernelGGL((band_plan_kernel<nv(), codes(), opk(), ld(), chv(), pf()>), grid, block, 0, s, a, items, t);
+                else no_instance("band_plan_kernel");
+            });
+        }); }); }); });
 }
 
 struct Group {
@@ -653,8 +624,8 @@ extern "C" int ptb_halo_pack(const float* src, int64_t chan_stride, int64_t row_
     const bool vec = !g_force_scalar && cols % 4 == 0 && chan_stride % 4 == 0 && row_stride % 4 == 0 && aligned16(src) && aligned16(dst);
     const long long total = (long long)C * rows * (vec ? cols / 4 : cols);
     const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 16);
-    if (vec) hipLaunchKernelGGL(halo_pack_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, C, rows, cols, (long long)chan_stride, (long long)row_stride);
-    else hipLaunchKernelGGL(halo_pack_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, C, rows, cols, (long long)chan_stride, (long long)row_stride);
+    with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL(halo_pack_kernel<(v() ? 4 : 1)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, C, rows, cols, (long long)chan_stride, (long long)row_stride); });
     return check_launch();
 }
 

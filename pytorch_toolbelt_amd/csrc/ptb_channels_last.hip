@@ -16,6 +16,7 @@
 //
 // Per pixel and channel the arithmetic is the planar kernels': views summed in view order with __fadd_rn, red_pre / red_post /
 // div_views, PTB_ROUND_SRC, then tile * window rounded and added in integration order (no contraction) -- bit-identical results.
+#include "ptb_dispatch.h"
 #include "ptb_view_device.h"
 
 namespace ptb {
@@ -275,25 +276,14 @@ __global__ __launch_bounds__(CL_THREADS) void cl_plan_kernel(const ViewArgs a, c
 
 // ------------------------------------------------------------------------------------------------ dispatch
 // (linear | non-linear reduction) x source dtype x (vector | element loads): 12 instances per kernel, view codes and C at run time
-#define PTB_CL_LAUNCH(KERNEL, vec, ...)                                                                                  \
-    do {                                                                                                                 \
-        const bool nonlinear_ = a.op >= PTB_RED_GMEAN;                                                                   \
-        if (a.in_dtype == PTB_F16) PTB_CL_LAUNCH_IN(KERNEL, PTB_F16, vec, __VA_ARGS__);                                  \
-        else if (a.in_dtype == PTB_BF16) PTB_CL_LAUNCH_IN(KERNEL, PTB_BF16, vec, __VA_ARGS__);                           \
-        else PTB_CL_LAUNCH_IN(KERNEL, PTB_F32, vec, __VA_ARGS__);                                                        \
-    } while (0)
-#define PTB_CL_LAUNCH_IN(KERNEL, IN, vec, ...)                                                                           \
-    do {                                                                                                                 \
-        if (nonlinear_) {                                                                                                \
-            if (vec) hipLaunchKernelGGL((KERNEL<1, IN, true>), grid, dim3(CL_THREADS), 0, s, __VA_ARGS__);               \
-            else hipLaunchKernelGGL((KERNEL<1, IN, false>), grid, dim3(CL_THREADS), 0, s, __VA_ARGS__);                  \
-        } else {                                                                                                         \
-            if (vec) hipLaunchKernelGGL((KERNEL<0, IN, true>), grid, dim3(CL_THREADS), 0, s, __VA_ARGS__);               \
-            else hipLaunchKernelGGL((KERNEL<0, IN, false>), grid, dim3(CL_THREADS), 0, s, __VA_ARGS__);                  \
-        }                                                                                                                \
-    } while (0)
+template <class F>
+static void with_cl_instance(const ViewArgs& a, bool vec, F&& f) {
+    with_reduction(a.op, [&](auto opk) { with_src_dtype(a.in_dtype, [&](auto ld) { with_bool(vec, [&](auto v) {
+        f(opk, int_c<ld_dtype<ld()>()>{}, v); }); }); });
+}
 
-// four channels per load: C a multiple of 4 (then every pixel of an aligned tile is aligned) and 16- / 8-byte aligned tiles
+// four channels per load: C a multiple of 4 (then every pixel of an aligned tile is aligned) and 16- / 8-byte aligned tiles.
+// (Unlike cl3_vec_ok of the 3-D unit this does not look at g_force_scalar: known, and left as it is.)
 static bool cl_vec_ok(const ViewArgs& a, const void* p, long long stride0, long long stride1) {
     const uintptr_t mask = a.in_dtype == PTB_F32 ? 15u : 7u;
     return a.C % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & mask) == 0 && stride0 % 4 == 0 && stride1 % 4 == 0;
@@ -302,13 +292,15 @@ static bool cl_vec_ok(const ViewArgs& a, const void* p, long long stride0, long 
 void cl_launch_reduce(const ViewArgs& a, int ntiles_out, int ch, hipStream_t s) {
     const dim3 grid((unsigned)ntiles_out * a.chunks_x * a.chunks_y);
     const bool vec = cl_vec_ok(a, a.src, a.src_tile_stride, a.src_view_stride);
-    PTB_CL_LAUNCH(cl_reduce_kernel, vec, a, ch);
+    with_cl_instance(a, vec, [&](auto opk, auto in, auto v) {
+        hipLaunchKernelGGL((cl_reduce_kernel<opk(), in(), v()>), grid, dim3(CL_THREADS), 0, s, a, ch); });
 }
 
 void cl_launch_accum(const ViewArgs& a, const CellArgs& g, int ch, hipStream_t s) {
     const dim3 grid((unsigned)a.total_chunks);
     const bool vec = cl_vec_ok(a, a.src, a.src_tile_stride, a.src_view_stride);
-    PTB_CL_LAUNCH(cl_accum_kernel, vec, a, g, ch);
+    with_cl_instance(a, vec, [&](auto opk, auto in, auto v) {
+        hipLaunchKernelGGL((cl_accum_kernel<opk(), in(), v()>), grid, dim3(CL_THREADS), 0, s, a, g, ch); });
 }
 
 void cl_launch_band(const ViewArgs& a, const BandArgs& g, int chunks, hipStream_t s) {
@@ -316,7 +308,8 @@ void cl_launch_band(const ViewArgs& a, const BandArgs& g, int chunks, hipStream_
     bool vec = true;
     for (int ci = 0; ci < a.ncells; ++ci)
         for (int e = 0; e < g.cells[ci].ntiles; ++e) vec = vec && cl_vec_ok(a, g.tile_src[g.cells[ci].tile[e]], g.tile_vs[g.cells[ci].tile[e]], 0);
-    PTB_CL_LAUNCH(cl_band_kernel, vec, a, g);
+    with_cl_instance(a, vec, [&](auto opk, auto in, auto v) {
+        hipLaunchKernelGGL((cl_band_kernel<opk(), in(), v()>), grid, dim3(CL_THREADS), 0, s, a, g); });
 }
 
 void cl_launch_plan(const ViewArgs& a, const BandItem* items, const GroupTiles& t, int n_items, hipStream_t s) {
@@ -324,10 +317,8 @@ void cl_launch_plan(const ViewArgs& a, const BandItem* items, const GroupTiles& 
     bool vec = true;
     for (int k = 0; k < PLAN_TILES; ++k)
         if (t.src[k]) vec = vec && cl_vec_ok(a, t.src[k], t.vs[k], 0);
-    PTB_CL_LAUNCH(cl_plan_kernel, vec, a, items, t);
+    with_cl_instance(a, vec, [&](auto opk, auto in, auto v) {
+        hipLaunchKernelGGL((cl_plan_kernel<opk(), in(), v()>), grid, dim3(CL_THREADS), 0, s, a, items, t); });
 }
-
-#undef PTB_CL_LAUNCH
-#undef PTB_CL_LAUNCH_IN
 
 }  // namespace ptb

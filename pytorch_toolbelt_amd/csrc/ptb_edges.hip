@@ -10,6 +10,7 @@
 // The other end, merge + crop, is in ptb_merge_crop.hip.  The split is an HBM-bound streaming kernel (no MFMA), write-bound (V*4
 // output bytes per input byte); it reuses the augment scatter of the view kernels: one 64 x CH pixel chunk per workgroup, 16 B
 // stores per lane, transposing views through the XOR-swizzled LDS tile.
+#include "ptb_dispatch.h"
 #include "ptb_view_device.h"
 
 namespace ptb {
@@ -114,8 +115,8 @@ __global__ __launch_bounds__(256) void edge_split_scalar_kernel(const ViewArgs a
 
 // one launch per group of MAX_GROUP tiles: the LDS-scatter kernel (CH rows per chunk, ptb_set_tunable key 0) or, for any other
 // shape / ptb_set_tunable(1, 1), the scalar kernel
-template <int IN, int OUT>
-int launch_split_tiles(ViewArgs& a, SplitArgs& g, const int64_t* xs, const int64_t* ys, int B, int V, bool fast, hipStream_t s) {
+static int launch_split_tiles(int in_dtype, int out_dtype, ViewArgs& a, SplitArgs& g, const int64_t* xs, const int64_t* ys, int B, int V, bool fast,
+                              hipStream_t s) {
     const int ch = g_chunk_rows;
     for (int b0 = 0; b0 < B; b0 += MAX_GROUP) {
         const int n = B - b0 < MAX_GROUP ? B - b0 : MAX_GROUP;
@@ -124,24 +125,20 @@ int launch_split_tiles(ViewArgs& a, SplitArgs& g, const int64_t* xs, const int64
         if (fast) {
             const long long blocks = (long long)n * g.IC * a.chunks_x * a.chunks_y;
             if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
-            if (ch == 64) hipLaunchKernelGGL((edge_split_kernel<64, IN, OUT>), dim3((unsigned)blocks), dim3(1024), 0, s, a, g, B);
-            else if (ch == 32) hipLaunchKernelGGL((edge_split_kernel<32, IN, OUT>), dim3((unsigned)blocks), dim3(512), 0, s, a, g, B);
-            else hipLaunchKernelGGL((edge_split_kernel<16, IN, OUT>), dim3((unsigned)blocks), dim3(256), 0, s, a, g, B);
+            with_value<64, 32, 16>(ch, [&](auto chv) { with_value<PTB_U8, PTB_U16, PTB_I16>(in_dtype, [&](auto in) {
+                with_value<PTB_F32, PTB_F16, PTB_BF16>(out_dtype, [&](auto out) {
+                    hipLaunchKernelGGL((edge_split_kernel<chv(), in(), out()>), dim3((unsigned)blocks), dim3(chv() * 16), 0, s, a, g, B);
+                }); }); });
         } else {
             const long long total = (long long)V * n * g.IC * a.H * a.W;
             const long long want = (total + 255) / 256;
-            hipLaunchKernelGGL((edge_split_scalar_kernel<IN, OUT>), dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, s, a, g, B, n);
+            with_value<PTB_U8, PTB_U16, PTB_I16>(in_dtype, [&](auto in) { with_value<PTB_F32, PTB_F16, PTB_BF16>(out_dtype, [&](auto out) {
+                hipLaunchKernelGGL((edge_split_scalar_kernel<in(), out()>), dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, s, a, g, B, n);
+            }); });
         }
         if (int rc = check_launch()) return rc;
     }
     return PTB_OK;
-}
-
-template <int IN>
-int launch_split_tiles_in(int out_dtype, ViewArgs& a, SplitArgs& g, const int64_t* xs, const int64_t* ys, int B, int V, bool fast, hipStream_t s) {
-    if (out_dtype == PTB_F32) return launch_split_tiles<IN, PTB_F32>(a, g, xs, ys, B, V, fast, s);
-    if (out_dtype == PTB_F16) return launch_split_tiles<IN, PTB_F16>(a, g, xs, ys, B, V, fast, s);
-    return launch_split_tiles<IN, PTB_BF16>(a, g, xs, ys, B, V, fast, s);
 }
 
 }  // namespace ptb
@@ -192,9 +189,7 @@ extern "C" int ptb_split_tiles(const void* image, int in_dtype, int IH, int IW, 
     for (int c = 0; c < IC; ++c) { g.scale[c] = scale ? scale[c] : 1.0f; g.bias[c] = bias ? bias[c] : 0.0f; }
     const bool fast = !g_force_scalar && tw % 4 == 0 && (nt == 0 || th % 4 == 0) && aligned16(out);
     hipStream_t s = (hipStream_t)stream;
-    if (in_dtype == PTB_U8) return launch_split_tiles_in<PTB_U8>(out_dtype, a, g, xs, ys, B, V, fast, s);
-    if (in_dtype == PTB_U16) return launch_split_tiles_in<PTB_U16>(out_dtype, a, g, xs, ys, B, V, fast, s);
-    return launch_split_tiles_in<PTB_I16>(out_dtype, a, g, xs, ys, B, V, fast, s);
+    return launch_split_tiles(in_dtype, out_dtype, a, g, xs, ys, B, V, fast, s);
 }
 
 // The uint8 / constant border / fp32 contract of the first device split, kept as it was (the same checks in the same order).

@@ -9,6 +9,7 @@
 // T reads + 1 write per element instead of the reference's (2 passes per activation) + stack (T reads + T writes) +
 // reduce (T reads + temporaries).  HBM-bound streaming: 16 B per lane, non-temporal loads, no MFMA.
 // The softmax variant keeps the C channel values of 4 pixels in registers (C <= 16) so every logit is read once.
+#include "ptb_dispatch.h"
 #include "ptb_view_device.h"
 
 namespace ptb {
@@ -251,22 +252,13 @@ extern "C" int ptb_ensemble_reduce(const float* const* inputs, int T, int reduct
     a.act = activation; a.temperature = temperature;
     a.B = B; a.C = C;
     hipStream_t s = (hipStream_t)stream;
-    const bool nonlinear = reduction >= PTB_RED_GMEAN;
     if (activation == 2) {
         if (!g_force_scalar && aligned && HW % 4 == 0 && C <= 16) {
             a.hw4 = HW / 4;
             const int pix = C <= 8 ? 4 : 2;
             const dim3 grid(grid_for((long long)B * a.hw4 * (4 / pix))), block(256);
-#define PTB_SM(CREG, PIX)                                                                                     \
-    do {                                                                                                      \
-        if (reduction == PTB_RED_GMEAN) hipLaunchKernelGGL((ensemble_softmax_kernel<2, CREG, PIX>), grid, block, 0, s, a); \
-        else if (nonlinear) hipLaunchKernelGGL((ensemble_softmax_kernel<1, CREG, PIX>), grid, block, 0, s, a); \
-        else hipLaunchKernelGGL((ensemble_softmax_kernel<0, CREG, PIX>), grid, block, 0, s, a);               \
-    } while (0)
-            if (C <= 4) PTB_SM(4, 4);
-            else if (C <= 8) PTB_SM(8, 4);
-            else PTB_SM(16, 2);
-#undef PTB_SM
+            with_reduction3(reduction, [&](auto opk) { with_at_most<4, 8, 16>(C, [&](auto cr) {
+                hipLaunchKernelGGL((ensemble_softmax_kernel<opk(), cr(), (cr() <= 8 ? 4 : 2)>), grid, block, 0, s, a); }); });
         } else {
             hipLaunchKernelGGL(ensemble_softmax_generic_kernel, dim3(grid_for((long long)B * HW)), dim3(256), 0, s, a, (long long)HW);
         }
@@ -275,19 +267,11 @@ extern "C" int ptb_ensemble_reduce(const float* const* inputs, int T, int reduct
     if (!g_force_scalar && aligned && n % 4 == 0) {
         a.n4 = n / 4;
         const dim3 grid(grid_for(a.n4)), block(256);
-        if (activation == 1) {
-            if (reduction == PTB_RED_GMEAN) hipLaunchKernelGGL((ensemble_kernel<2, 1>), grid, block, 0, s, a);
-            else if (nonlinear) hipLaunchKernelGGL((ensemble_kernel<1, 1>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((ensemble_kernel<0, 1>), grid, block, 0, s, a);
-        } else {
-            if (reduction == PTB_RED_GMEAN) hipLaunchKernelGGL((ensemble_kernel<2, 0>), grid, block, 0, s, a);
-            else if (nonlinear) hipLaunchKernelGGL((ensemble_kernel<1, 0>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((ensemble_kernel<0, 0>), grid, block, 0, s, a);
-        }
+        with_reduction3(reduction, [&](auto opk) { with_value<1, 0>(activation, [&](auto act) {
+            hipLaunchKernelGGL((ensemble_kernel<opk(), act()>), grid, block, 0, s, a); }); });
     } else {
         const dim3 grid(grid_for(n)), block(256);
-        if (activation == 1) hipLaunchKernelGGL(ensemble_scalar_kernel<1>, grid, block, 0, s, a, n);
-        else hipLaunchKernelGGL(ensemble_scalar_kernel<0>, grid, block, 0, s, a, n);
+        with_value<1, 0>(activation, [&](auto act) { hipLaunchKernelGGL(ensemble_scalar_kernel<act()>, grid, block, 0, s, a, n); });
     }
     return check_launch();
 }

@@ -11,6 +11,7 @@
 //
 // class_weights follow dim 1 of the ORIGINAL tensor (functional.py:83-88), which need not be the softmax dimension: cw_mode
 // 1 = indexed by the softmax channel, 2 = by (b / cw_div) % cw_n, 3 = by (position / cw_div) % cw_n.
+#include "ptb_dispatch.h"
 #include "ptb_loss_device.h"
 
 namespace ptb {
@@ -163,10 +164,8 @@ extern "C" int ptb_focal_softmax_fwd(const float* logits, const int64_t* labels,
     const bool vec = vec_ok(HW, {logits, dense, elem_out, labels});
     const dim3 grid(vec ? grid_for_groups((HW + 255) / 256 * B, kGridStream) : grid_for_groups((HW + 63) / 64 * B, kGridStream)), block(256);
     const bool g2 = gamma == 2.0f;
-    if (vec) { if (g2) hipLaunchKernelGGL((focal_softmax_kernel<4, 0, true>), grid, block, 0, s, fa, nullptr, nullptr, nullptr);
-               else hipLaunchKernelGGL((focal_softmax_kernel<4, 0, false>), grid, block, 0, s, fa, nullptr, nullptr, nullptr); }
-    else { if (g2) hipLaunchKernelGGL((focal_softmax_kernel<1, 0, true>), grid, block, 0, s, fa, nullptr, nullptr, nullptr);
-           else hipLaunchKernelGGL((focal_softmax_kernel<1, 0, false>), grid, block, 0, s, fa, nullptr, nullptr, nullptr); }
+    with_bool(vec, [&](auto v) { with_bool(g2, [&](auto g) {
+        hipLaunchKernelGGL((focal_softmax_kernel<(v() ? 4 : 1), 0, g()>), grid, block, 0, s, fa, nullptr, nullptr, nullptr); }); });
     return check_launch();
 }
 
@@ -182,9 +181,7 @@ extern "C" int ptb_focal_softmax_bwd(const float* logits, const int64_t* labels,
     const bool vec = vec_ok(HW, {logits, dense, grad_elem, grad, labels});
     const dim3 grid(vec ? grid_for_groups((HW + 255) / 256 * B, kGridStream) : grid_for_groups((HW + 63) / 64 * B, kGridStream)), block(256);
     const bool g2 = gamma == 2.0f;
-    if (vec) { if (g2) hipLaunchKernelGGL((focal_softmax_kernel<4, 1, true>), grid, block, 0, s, fa, coef, grad_elem, grad);
-               else hipLaunchKernelGGL((focal_softmax_kernel<4, 1, false>), grid, block, 0, s, fa, coef, grad_elem, grad); }
-    else { if (g2) hipLaunchKernelGGL((focal_softmax_kernel<1, 1, true>), grid, block, 0, s, fa, coef, grad_elem, grad);
-           else hipLaunchKernelGGL((focal_softmax_kernel<1, 1, false>), grid, block, 0, s, fa, coef, grad_elem, grad); }
+    with_bool(vec, [&](auto v) { with_bool(g2, [&](auto g) {
+        hipLaunchKernelGGL((focal_softmax_kernel<(v() ? 4 : 1), 1, g()>), grid, block, 0, s, fa, coef, grad_elem, grad); }); });
     return check_launch();
 }

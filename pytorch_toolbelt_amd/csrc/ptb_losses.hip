@@ -18,6 +18,7 @@
 
 #include <type_traits>
 
+#include "ptb_dispatch.h"
 #include "ptb_loss_device.h"
 
 // the losses are tolerance-checked (1e-5), not bit-exact: let the compiler fuse multiply-adds in this file
@@ -1981,6 +1982,21 @@ extern "C" int ptb_region_loss_fwd(const float* logits, const int64_t* labels, c
     return seg_loss_fwd_launch(a, (hipStream_t)stream);
 }
 
+// The packed streaming kernel, seg_focal_pk_kernel<CREG, TERM, FULL, FOCAL, STATS> (FULL: C == CREG).  Compiled: focal + statistics
+// (without a FULL form where it writes the terms), statistics alone (never writes them), focal alone.
+static void launch_focal_pk(const SegArgs& a, size_t shmem, bool term, bool focal, bool stats, hipStream_t s) {
+    const dim3 gpk(grid_for_groups(a.HW / 128 * a.B, kGridFocalPk)), block(256);
+    with_at_most<4, 8, 16>(a.C, [&](auto cr) {
+        const size_t pk_lds = std::max(shmem, (size_t)4 * 2 * cr() * 64 * sizeof(float));
+        const bool full = a.C == cr() && !(term && focal && stats);
+        with_bool(term, [&](auto tm) { with_bool(full, [&](auto fu) { with_bool(focal, [&](auto fo) { with_bool(stats, [&](auto st) {
+            if constexpr ((fo() || st()) && !(tm() && !fo()) && !(tm() && fu() && fo() && st()))
+                hipLaunchKernelGGL((seg_focal_pk_kernel<cr(), tm(), fu(), fo(), st()>), gpk, block, pk_lds, s, a);
+            else no_instance("seg_focal_pk_kernel");
+        }); }); }); });
+    });
+}
+
 static int seg_loss_fwd_launch(SegArgs& a, hipStream_t s) {
     const float *logits = a.logits, *dense = a.dense, *class_weights = a.class_weights;
     const long long* labels = a.labels;
@@ -1999,17 +2015,15 @@ static int seg_loss_fwd_launch(SegArgs& a, hipStream_t s) {
     if (!g_force_scalar && dense && !labels && what == (SEG_FOCAL | SEG_STATS) && vec && HW % 1024 == 0 && prob == PROB_SIGMOID && g2 &&
         !class_weights && !(flags & (SEG_HAS_ALPHA | SEG_REDUCED | SEG_ELEMWISE))) {
         const dim3 dgrid(grid_for_groups(HW / 1024 * C * B, kGridStream));
-        if (flags & SEG_HAS_IGNORE) hipLaunchKernelGGL((seg_stats_dense_lean_kernel<PROB_SIGMOID, true, true>), dgrid, block, shmem, s, a);
-        else hipLaunchKernelGGL((seg_stats_dense_lean_kernel<PROB_SIGMOID, false, true>), dgrid, block, shmem, s, a);
+        with_bool(flags & SEG_HAS_IGNORE, [&](auto ig) {
+            hipLaunchKernelGGL((seg_stats_dense_lean_kernel<PROB_SIGMOID, ig(), true>), dgrid, block, shmem, s, a); });
         return check_launch();
     }
     if (!g_force_scalar && dense && !labels && what == SEG_STATS && vec && HW % 1024 == 0 && (prob == PROB_SIGMOID || prob == PROB_IDENTITY)) {
         const bool ign = flags & SEG_HAS_IGNORE;
         const dim3 dgrid(grid_for_groups(HW / 1024 * C * B, kGridStream));
-        if (prob == PROB_SIGMOID) { if (ign) hipLaunchKernelGGL((seg_stats_dense_lean_kernel<PROB_SIGMOID, true>), dgrid, block, shmem, s, a);
-                                    else hipLaunchKernelGGL((seg_stats_dense_lean_kernel<PROB_SIGMOID, false>), dgrid, block, shmem, s, a); }
-        else { if (ign) hipLaunchKernelGGL((seg_stats_dense_lean_kernel<PROB_IDENTITY, true>), dgrid, block, shmem, s, a);
-               else hipLaunchKernelGGL((seg_stats_dense_lean_kernel<PROB_IDENTITY, false>), dgrid, block, shmem, s, a); }
+        with_value<PROB_SIGMOID, PROB_IDENTITY>(prob, [&](auto pr) { with_bool(ign, [&](auto ig) {
+            hipLaunchKernelGGL((seg_stats_dense_lean_kernel<pr(), ig()>), dgrid, block, shmem, s, a); }); });
         return check_launch();
     }
     // straight-line kernels for the common case (see seg_fwd_lean_kernel, seg_focal_pk_kernel)
@@ -2020,73 +2034,55 @@ static int seg_loss_fwd_launch(SegArgs& a, hipStream_t s) {
                                  !(flags & (SEG_HAS_IGNORE | SEG_HAS_ALPHA | SEG_REDUCED));
         const dim3 lgrid(grid_for_groups(HW / 256 * B, kGridStats));
         const bool no_term = flags & SEG_NO_TERM;
-#define PTB_LEAN(CR) do { \
-            if (plain_focal) { \
-                               const size_t pk_lds = std::max(shmem, (size_t)4 * 2 * CR * 64 * sizeof(float)); \
-                               const dim3 gpk(grid_for_groups(HW / 128 * B, kGridFocalPk)); \
-                               if (no_term && C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true>), gpk, block, pk_lds, s, a); \
-                               else if (no_term) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, false>), gpk, block, pk_lds, s, a); \
-                               else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, true, false>), gpk, block, pk_lds, s, a); } \
-            else if (prob == PROB_SOFTMAX && !ign && g_stats_pk && HW % 128 == 0) { \
-                               const size_t pk_lds = std::max(shmem, (size_t)4 * 2 * CR * 64 * sizeof(float)); \
-                               const dim3 gpk(grid_for_groups(HW / 128 * B, kGridFocalPk)); \
-                               if (C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true, false>), gpk, block, pk_lds, s, a); \
-                               else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, false, false>), gpk, block, pk_lds, s, a); } \
-            else if (prob == PROB_SOFTMAX) { if (ign) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, true>), lgrid, block, shmem, s, a); \
-                                             else hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_SOFTMAX, false>), lgrid, block, shmem, s, a); } \
-            else { if (ign) hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_IDENTITY, true>), lgrid, block, shmem, s, a); \
-                   else hipLaunchKernelGGL((seg_fwd_lean_kernel<CR, PROB_IDENTITY, false>), lgrid, block, shmem, s, a); } } while (0)
+        // statistics alone from the packed kernel (tunable 20)
+        const bool stats_pk = prob == PROB_SOFTMAX && !ign && g_stats_pk && HW % 128 == 0;
         if (what == SEG_STATS || plain_focal) {
-            if (C <= 4) PTB_LEAN(4); else if (C <= 8) PTB_LEAN(8); else PTB_LEAN(16);
+            if (plain_focal) launch_focal_pk(a, shmem, !no_term, true, true, s);
+            else if (stats_pk) launch_focal_pk(a, shmem, false, false, true, s);
+            else with_at_most<4, 8, 16>(C, [&](auto cr) { with_value<PROB_SOFTMAX, PROB_IDENTITY>(prob, [&](auto pr) { with_bool(ign, [&](auto ig) {
+                hipLaunchKernelGGL((seg_fwd_lean_kernel<cr(), pr(), ig()>), lgrid, block, shmem, s, a); }); }); });
             return check_launch();
         }
-#undef PTB_LEAN
     }
     if (focal_only_pk(a)) {
         // BinaryFocalLoss() on label maps in its default configuration: the packed streaming kernel of the fused loss without its
         // statistics half (the shared exponent shift max_c x keeps one exp per element for sigmoid and its complement)
         const bool term = !(flags & SEG_NO_TERM);
-        const dim3 gpk(grid_for_groups(HW / 128 * B, kGridFocalPk));
-#define PTB_FPK(CR) do { const size_t pk_lds = std::max(shmem, (size_t)4 * 2 * CR * 64 * sizeof(float)); \
-                         if (term) { if (C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, true, true, true, false>), gpk, block, pk_lds, s, a); \
-                                     else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, true, false, true, false>), gpk, block, pk_lds, s, a); } \
-                         else { if (C == CR) hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, true, true, false>), gpk, block, pk_lds, s, a); \
-                                else hipLaunchKernelGGL((seg_focal_pk_kernel<CR, false, false, true, false>), gpk, block, pk_lds, s, a); } } while (0)
-        if (C <= 4) PTB_FPK(4); else if (C <= 8) PTB_FPK(8); else PTB_FPK(16);
-#undef PTB_FPK
+        launch_focal_pk(a, shmem, term, true, false, s);
         return check_launch();
     }
     if (what == SEG_FOCAL && !g_force_scalar && labels && !dense && vec && HW % 256 == 0 && g2 && !class_weights &&
         !(flags & (SEG_HAS_ALPHA | SEG_REDUCED | SEG_ELEMWISE))) {
         const bool ign = flags & SEG_HAS_IGNORE;
         const dim3 lgrid(grid_for_groups(HW / 256 * B, kGridStream));
-#define PTB_FL(CH) do { if (ign) hipLaunchKernelGGL((focal_fwd_lean_kernel<CH, true>), lgrid, block, 0, s, a); \
-                        else hipLaunchKernelGGL((focal_fwd_lean_kernel<CH, false>), lgrid, block, 0, s, a); } while (0)
-        if (C <= 4) PTB_FL(4); else PTB_FL(8);   // 16 at once (139 VGPRs, 3 waves / SIMD) measured 119 us vs 108 us for 2 x 8 at C = 16
-#undef PTB_FL
+        // no 16: 16 at once (139 VGPRs, 3 waves / SIMD) measured 119 us vs 108 us for 2 x 8 at C = 16
+        with_at_most<4, 8>(C, [&](auto cch) { with_bool(ign, [&](auto ig) {
+            hipLaunchKernelGGL((focal_fwd_lean_kernel<cch(), ig()>), lgrid, block, 0, s, a); }); });
         return check_launch();
     }
     if (what == SEG_FOCAL) {
-#define PTB_FF(P, D) do { if (g2) hipLaunchKernelGGL((focal_fwd_kernel<P, D, true>), grid, block, 0, s, a); \
-                          else hipLaunchKernelGGL((focal_fwd_kernel<P, D, false>), grid, block, 0, s, a); } while (0)
-        if (vec) { if (labels) PTB_FF(4, false); else PTB_FF(4, true); }
-        else { if (labels) PTB_FF(1, false); else PTB_FF(1, true); }
-#undef PTB_FF
+        with_bool(vec, [&](auto v) { with_bool(!labels, [&](auto dn) { with_bool(g2, [&](auto g) {
+            hipLaunchKernelGGL((focal_fwd_kernel<(v() ? 4 : 1), dn(), g()>), grid, block, 0, s, a); }); }); });
     } else if (vec && C <= 16) {
-#define PTB_FWD(W, D) do { if (g2) hipLaunchKernelGGL((seg_loss_fwd_reg_kernel<4, 16, W, D, true>), grid, block, shmem, s, a); \
-                           else hipLaunchKernelGGL((seg_loss_fwd_reg_kernel<4, 16, W, D, false>), grid, block, shmem, s, a); } while (0)
-        const bool plain = g2 && !class_weights && !(flags & (SEG_HAS_IGNORE | SEG_HAS_ALPHA | SEG_REDUCED));
-        if (labels && what != SEG_STATS && prob == PROB_SOFTMAX && !(flags & SEG_ELEMWISE)) {
-            if (plain) hipLaunchKernelGGL((seg_loss_fwd_reg_kernel<4, 16, 3, false, true, true, true>), grid, block, shmem, s, a);
-            else if (g2) hipLaunchKernelGGL((seg_loss_fwd_reg_kernel<4, 16, 3, false, true, true>), grid, block, shmem, s, a);
-            else hipLaunchKernelGGL((seg_loss_fwd_reg_kernel<4, 16, 3, false, false, true>), grid, block, shmem, s, a);
-        } else if (labels) { if (what == SEG_STATS) hipLaunchKernelGGL((seg_loss_fwd_reg_kernel<4, 16, 2, false, true>), grid, block, shmem, s, a); else PTB_FWD(3, false); }
-        else { if (what == SEG_STATS) hipLaunchKernelGGL((seg_loss_fwd_reg_kernel<4, 16, 2, true, true>), grid, block, shmem, s, a); else PTB_FWD(3, true); }
-#undef PTB_FWD
-    } else if (vec) {
-        hipLaunchKernelGGL((seg_loss_fwd_kernel<4>), grid, block, shmem, s, a);
+        // seg_loss_fwd_reg_kernel<4, 16, WHAT, DENSE, G2, SHARE, PLAIN>, its nine forms and when each runs:
+        //   WHAT DENSE G2  SHARE PLAIN
+        //    3   no    yes yes   yes    labels, focal + statistics of a softmax, no element-wise output (= share), plain
+        //    3   no    yes yes   no     share, gamma == 2, not plain (class weights, ignore, alpha or reduced threshold)
+        //    3   no    no  yes   no     share, any other gamma
+        //    2   no    yes no    no     statistics alone from labels (compiled as G2 only: gamma is not read)
+        //    2   yes   yes no    no     statistics alone from dense targets
+        //    3   no    y/n no    no     labels, not share (sigmoid / given probabilities, or element-wise output), gamma == 2 or not
+        //    3   yes   y/n no    no     dense targets, gamma == 2 or not
+        const bool share = labels && what != SEG_STATS && prob == PROB_SOFTMAX && !(flags & SEG_ELEMWISE);
+        const bool plain = share && g2 && !class_weights && !(flags & (SEG_HAS_IGNORE | SEG_HAS_ALPHA | SEG_REDUCED));
+        with_bool(what == SEG_STATS, [&](auto so) { with_bool(!labels, [&](auto dn) { with_bool(g2 || so(), [&](auto g) {
+            with_bool(share, [&](auto sh) { with_bool(plain, [&](auto pl) {
+                if constexpr (!(sh() && (so() || dn())) && !(so() && !g()) && !(pl() && !(sh() && g())))
+                    hipLaunchKernelGGL((seg_loss_fwd_reg_kernel<4, 16, (so() ? 2 : 3), dn(), g(), sh(), pl()>), grid, block, shmem, s, a);
+                else no_instance("seg_loss_fwd_reg_kernel");
+            }); }); }); }); });
     } else {
-        hipLaunchKernelGGL((seg_loss_fwd_kernel<1>), grid, block, shmem, s, a);
+        with_bool(vec, [&](auto v) { hipLaunchKernelGGL((seg_loss_fwd_kernel<(v() ? 4 : 1)>), grid, block, shmem, s, a); });
     }
     return check_launch();
 }
@@ -2103,16 +2099,8 @@ extern "C" int ptb_focal_bwd(const float* logits, const int64_t* labels, const f
     const bool vec = vec_ok(HW, {logits, dense, grad_elem, grad, labels});
     const dim3 grid(vec ? grid_for_groups((HW + 255) / 256 * B, kGridStream) : grid_for_groups((HW + 63) / 64 * B, kGridStream)), block(256);
     const bool g2 = gamma == 2.0f;
-#define PTB_FBWD(P, D, G) do { if (g2) hipLaunchKernelGGL((focal_bwd_kernel<P, D, G, true>), grid, block, 0, s, a, coef, grad_elem, grad); \
-                               else hipLaunchKernelGGL((focal_bwd_kernel<P, D, G, false>), grid, block, 0, s, a, coef, grad_elem, grad); } while (0)
-    if (vec) {
-        if (labels) { if (grad_elem) PTB_FBWD(4, false, true); else PTB_FBWD(4, false, false); }
-        else { if (grad_elem) PTB_FBWD(4, true, true); else PTB_FBWD(4, true, false); }
-    } else {
-        if (labels) { if (grad_elem) PTB_FBWD(1, false, true); else PTB_FBWD(1, false, false); }
-        else { if (grad_elem) PTB_FBWD(1, true, true); else PTB_FBWD(1, true, false); }
-    }
-#undef PTB_FBWD
+    with_bool(vec, [&](auto v) { with_bool(!labels, [&](auto dn) { with_bool(grad_elem != nullptr, [&](auto ge) { with_bool(g2, [&](auto g) {
+        hipLaunchKernelGGL((focal_bwd_kernel<(v() ? 4 : 1), dn(), ge(), g()>), grid, block, 0, s, a, coef, grad_elem, grad); }); }); }); });
     return check_launch();
 }
 
@@ -2127,10 +2115,8 @@ extern "C" int ptb_seg_stats_bwd(const float* logits, const int64_t* labels, con
     if (!g_force_scalar && dense && !labels && HW % 1024 == 0 && (prob == PROB_SIGMOID || prob == PROB_IDENTITY) && vec_ok(HW, {logits, dense, grad})) {
         const dim3 dgrid(grid_for_groups(HW / 1024 * C * B, kGridStream)), block(256);
         const bool ign = flags & SEG_HAS_IGNORE;
-        if (prob == PROB_SIGMOID) { if (ign) hipLaunchKernelGGL((seg_dense_bwd_lean_kernel<PROB_SIGMOID, true, false>), dgrid, block, 0, s, a, gI, gI, gP, grad);
-                                    else hipLaunchKernelGGL((seg_dense_bwd_lean_kernel<PROB_SIGMOID, false, false>), dgrid, block, 0, s, a, gI, gI, gP, grad); }
-        else { if (ign) hipLaunchKernelGGL((seg_dense_bwd_lean_kernel<PROB_IDENTITY, true, false>), dgrid, block, 0, s, a, gI, gI, gP, grad);
-               else hipLaunchKernelGGL((seg_dense_bwd_lean_kernel<PROB_IDENTITY, false, false>), dgrid, block, 0, s, a, gI, gI, gP, grad); }
+        with_value<PROB_SIGMOID, PROB_IDENTITY>(prob, [&](auto pr) { with_bool(ign, [&](auto ig) {
+            hipLaunchKernelGGL((seg_dense_bwd_lean_kernel<pr(), ig(), false>), dgrid, block, 0, s, a, gI, gI, gP, grad); }); });
         return check_launch();
     }
     if (vec_ok(HW, {logits, dense, grad, labels})) {
@@ -2150,9 +2136,8 @@ static int launch_smf(const SmfArgs& a, const float* coef, const float* grad_pix
     if (MODE == 0 && !g_force_scalar && a.HW % 256 == 0 && a.C <= 16 && a.gamma == 2.0f && !a.class_weights && !a.reduced &&
         vec_ok(a.HW, {a.logits, a.pixel_out, grad_pix, grad, a.labels})) {
         const dim3 lgrid(grid_for_groups(a.HW / 256 * a.B, kGridStream)), block(256);
-        if (a.C <= 4) hipLaunchKernelGGL((softmax_focal_lean_kernel<4, 0>), lgrid, block, 0, s, a, coef, grad_pix, grad);
-        else if (a.C <= 8) hipLaunchKernelGGL((softmax_focal_lean_kernel<8, 0>), lgrid, block, 0, s, a, coef, grad_pix, grad);
-        else hipLaunchKernelGGL((softmax_focal_lean_kernel<16, 0>), lgrid, block, 0, s, a, coef, grad_pix, grad);
+        with_at_most<4, 8, 16>(a.C, [&](auto cr) {
+            hipLaunchKernelGGL((softmax_focal_lean_kernel<cr(), 0>), lgrid, block, 0, s, a, coef, grad_pix, grad); });
         return check_launch();
     }
     if (vec_ok(a.HW, {a.logits, a.pixel_out, grad_pix, grad, a.labels})) {
@@ -2161,17 +2146,16 @@ static int launch_smf(const SmfArgs& a, const float* coef, const float* grad_pix
         if (MODE == 1 && a.C <= 16 && !g_force_scalar && g_smf_bwd_stash) {   // one transcendental pass, T_c kept in registers
             const int pix = g_smf_bwd_stash;
             const int g2 = grid_for_groups((a.HW + 64 * pix - 1) / (64 * pix) * a.B, kGridStream);
-#define PTB_SMF_BWD(P, G, F) hipLaunchKernelGGL((softmax_focal_bwd_kernel<P, 16, G, F>), dim3(g2), dim3(256), 0, s, a, coef, grad_pix, grad)
-            const bool gm2 = a.gamma == 2.0f;
             // (FULL = true, all 16 loads unconditional, lets the scheduler hoist everything: 256 VGPRs + scratch against 184 -- not used)
-            if (pix == 2) { if (gm2) PTB_SMF_BWD(2, true, false); else PTB_SMF_BWD(2, false, false); }
-            else { if (gm2) PTB_SMF_BWD(4, true, false); else PTB_SMF_BWD(4, false, false); }
-#undef PTB_SMF_BWD
+            with_value<2, 4>(pix, [&](auto p) { with_bool(a.gamma == 2.0f, [&](auto g) {
+                hipLaunchKernelGGL((softmax_focal_bwd_kernel<p(), 16, g(), false>), dim3(g2), dim3(256), 0, s, a, coef, grad_pix, grad); }); });
             return check_launch();
         }
-        if (a.C <= 16 && a.gamma == 2.0f) hipLaunchKernelGGL((softmax_focal_kernel<4, 16, MODE, true>), dim3(grid), dim3(256), 0, s, a, coef, grad_pix, grad);
-        else if (a.C <= 16) hipLaunchKernelGGL((softmax_focal_kernel<4, 16, MODE, false>), dim3(grid), dim3(256), 0, s, a, coef, grad_pix, grad);
-        else hipLaunchKernelGGL((softmax_focal_kernel<4, 0, MODE, false>), dim3(grid), dim3(256), 0, s, a, coef, grad_pix, grad);
+        with_bool(a.C <= 16, [&](auto reg) { with_bool(a.C <= 16 && a.gamma == 2.0f, [&](auto g) {   // G2 only with the classes in registers
+            if constexpr (reg() || !g())
+                hipLaunchKernelGGL((softmax_focal_kernel<4, (reg() ? 16 : 0), MODE, g()>), dim3(grid), dim3(256), 0, s, a, coef, grad_pix, grad);
+            else no_instance("softmax_focal_kernel");
+        }); });
     } else {
         hipLaunchKernelGGL((softmax_focal_kernel<1, 0, MODE, false>), dim3(grid_for_groups((a.HW + 63) / 64 * a.B, kGridStream)), dim3(256), 0, s, a, coef, grad_pix, grad);
     }
@@ -2210,29 +2194,27 @@ extern "C" int ptb_seg_fused_bwd(const float* logits, const int64_t* labels, con
     if (!g_force_scalar && dense && !labels && HW % 1024 == 0 && prob == PROB_SIGMOID && gamma == 2.0f && !class_weights &&
         !(flags & (SEG_HAS_ALPHA | SEG_REDUCED)) && vec_ok(HW, {logits, dense, grad})) {
         const dim3 dgrid(grid_for_groups(HW / 1024 * C * B, kGridStream)), dblock(256);
-        if (flags & SEG_HAS_IGNORE) hipLaunchKernelGGL((seg_dense_bwd_lean_kernel<PROB_SIGMOID, true, true>), dgrid, dblock, 0, (hipStream_t)stream, a, coef, gI, gP, grad);
-        else hipLaunchKernelGGL((seg_dense_bwd_lean_kernel<PROB_SIGMOID, false, true>), dgrid, dblock, 0, (hipStream_t)stream, a, coef, gI, gP, grad);
+        with_bool(flags & SEG_HAS_IGNORE, [&](auto ig) {
+            hipLaunchKernelGGL((seg_dense_bwd_lean_kernel<PROB_SIGMOID, ig(), true>), dgrid, dblock, 0, (hipStream_t)stream, a, coef, gI, gP, grad); });
         return check_launch();
     }
     if (C > 16 || !vec_ok(HW, {logits, dense, grad, labels}) || (dense && prob == PROB_SOFTMAX)) return PTB_EUNSUPPORTED;
     const dim3 grid(grid_for_groups((HW + 255) / 256 * B, kGridStats)), block(256);
     hipStream_t s = (hipStream_t)stream;
     const bool g2 = gamma == 2.0f;
-#define PTB_FUSED(D) do { if (g2) hipLaunchKernelGGL((seg_fused_bwd_kernel<4, 16, D, true>), grid, block, 0, s, a, coef, gI, gP, grad); \
-                          else hipLaunchKernelGGL((seg_fused_bwd_kernel<4, 16, D, false>), grid, block, 0, s, a, coef, gI, gP, grad); } while (0)
     if (labels && prob == PROB_SOFTMAX) {
         const bool plain = g2 && !class_weights && !(flags & (SEG_HAS_IGNORE | SEG_HAS_ALPHA | SEG_REDUCED));
         if (plain && !g_force_scalar && HW % 256 == 0) {
             if (g_nt_grad_stores) a.flags |= SEG_NT_STORES;
             const dim3 lgrid(grid_for_groups(HW / 256 * B, kGridStats));
-            if (C <= 4) hipLaunchKernelGGL((seg_fused_bwd_lean_kernel<4>), lgrid, block, 0, s, a, coef, gI, gP, grad);
-            else if (C <= 8) hipLaunchKernelGGL((seg_fused_bwd_lean_kernel<8>), lgrid, block, 0, s, a, coef, gI, gP, grad);
-            else hipLaunchKernelGGL((seg_fused_bwd_lean_kernel<16>), lgrid, block, 0, s, a, coef, gI, gP, grad);
-        } else if (plain) hipLaunchKernelGGL((seg_fused_bwd_shared_kernel<4, 16, true, true>), grid, block, 0, s, a, coef, gI, gP, grad);
-        else if (g2) hipLaunchKernelGGL((seg_fused_bwd_shared_kernel<4, 16, true>), grid, block, 0, s, a, coef, gI, gP, grad);
-        else hipLaunchKernelGGL((seg_fused_bwd_shared_kernel<4, 16, false>), grid, block, 0, s, a, coef, gI, gP, grad);
-    } else if (labels) PTB_FUSED(false); else PTB_FUSED(true);
-#undef PTB_FUSED
+            with_at_most<4, 8, 16>(C, [&](auto cr) {
+                hipLaunchKernelGGL((seg_fused_bwd_lean_kernel<cr()>), lgrid, block, 0, s, a, coef, gI, gP, grad); });
+        } else with_bool(g2, [&](auto g) { with_bool(plain, [&](auto pl) {   // (plain implies gamma == 2)
+            if constexpr (g() || !pl())
+                hipLaunchKernelGGL((seg_fused_bwd_shared_kernel<4, 16, g(), pl()>), grid, block, 0, s, a, coef, gI, gP, grad);
+            else no_instance("seg_fused_bwd_shared_kernel"); }); });
+    } else with_bool(!labels, [&](auto dn) { with_bool(g2, [&](auto g) {
+        hipLaunchKernelGGL((seg_fused_bwd_kernel<4, 16, dn(), g()>), grid, block, 0, s, a, coef, gI, gP, grad); }); });
     return check_launch();
 }
 

@@ -26,6 +26,7 @@
 #include <cstring>
 
 #include "ptb_common.h"
+#include "ptb_dispatch.h"
 
 namespace ptb {
 
@@ -1114,10 +1115,8 @@ static int lovasz_fwd_impl(const float* pred, const int64_t* labels, const float
         if (nch > 65535) return PTB_EUNSUPPORTED;
         const dim3 grid((unsigned)gt, (unsigned)nch);
         // kappa keys (keyonly_key), no values written: the first scatter pass makes them (IOTA)
-        if (a.mode == LOVASZ_SOFTMAX)
-            hipLaunchKernelGGL(lovasz_error_hist_kernel<LOVASZ_SOFTMAX>, grid, dim3(256), 0, s, a, T, cchunk, keys_a, hist);
-        else
-            hipLaunchKernelGGL(lovasz_error_hist_kernel<LOVASZ_HINGE>, grid, dim3(256), 0, s, a, T, cchunk, keys_a, hist);
+        with_value<LOVASZ_SOFTMAX, LOVASZ_HINGE>(a.mode, [&](auto mode) {
+            hipLaunchKernelGGL(lovasz_error_hist_kernel<mode()>, grid, dim3(256), 0, s, a, T, cchunk, keys_a, hist); });
         if (int rc = check_launch()) return rc;
     }
     // four stable 8-bit passes, ping-ponging a -> b -> a -> b -> a
@@ -1208,10 +1207,8 @@ extern "C" int ptb_lovasz_fwd_keys(const float* pred, const int64_t* labels, con
         nch = (a.C + cchunk - 1) / cchunk;
         if (nch > 65535) return PTB_EUNSUPPORTED;
         const dim3 grid((unsigned)gt, (unsigned)nch);
-        if (a.mode == LOVASZ_SOFTMAX)
-            hipLaunchKernelGGL(lovasz_error_hist_kernel<LOVASZ_SOFTMAX>, grid, dim3(256), 0, s, a, T, cchunk, keys_a, hist);
-        else
-            hipLaunchKernelGGL(lovasz_error_hist_kernel<LOVASZ_HINGE>, grid, dim3(256), 0, s, a, T, cchunk, keys_a, hist);
+        with_value<LOVASZ_SOFTMAX, LOVASZ_HINGE>(a.mode, [&](auto mode) {
+            hipLaunchKernelGGL(lovasz_error_hist_kernel<mode()>, grid, dim3(256), 0, s, a, T, cchunk, keys_a, hist); });
         if (int rc = check_launch()) return rc;
     }
     unsigned *kin = keys_a, *kout = keys_b;
@@ -1275,12 +1272,9 @@ static int lovasz_bwd_binned_impl(const float* pred, const int64_t* labels, cons
     if (gx > 0x7fffffffLL || nch > 65535) return PTB_EUNSUPPORTED;
     const size_t lds = sizeof(float) << block_log2;
     const dim3 grid((unsigned)gx, (unsigned)nch);
-    if (a.mode == LOVASZ_SOFTMAX)
-        hipLaunchKernelGGL(lovasz_bwd_binned_kernel<LOVASZ_SOFTMAX>, grid, dim3(256), lds, (hipStream_t)stream, a, coef, gscale, binned_vals, binned_grad, grad,
-                           block_log2, (int)nblocks, cchunk);
-    else
-        hipLaunchKernelGGL(lovasz_bwd_binned_kernel<LOVASZ_HINGE>, grid, dim3(256), lds, (hipStream_t)stream, a, coef, gscale, binned_vals, binned_grad, grad,
-                           block_log2, (int)nblocks, cchunk);
+    with_value<LOVASZ_SOFTMAX, LOVASZ_HINGE>(a.mode, [&](auto mode) {
+        hipLaunchKernelGGL(lovasz_bwd_binned_kernel<mode()>, grid, dim3(256), lds, (hipStream_t)stream, a, coef, gscale, binned_vals, binned_grad, grad,
+                           block_log2, (int)nblocks, cchunk); });
     return check_launch();
 }
 
@@ -1310,10 +1304,8 @@ extern "C" int ptb_lovasz_bwd(const float* pred, const int64_t* labels, const fl
     const long long n = a.P * a.S;
     if (n == 0) return PTB_OK;
     const int blocks = blocks_for((long long)a.B * a.HW);
-    if (a.mode == LOVASZ_SOFTMAX)
-        hipLaunchKernelGGL(lovasz_bwd_kernel<LOVASZ_SOFTMAX>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, coef, grad_at_pixel, grad);
-    else
-        hipLaunchKernelGGL(lovasz_bwd_kernel<LOVASZ_HINGE>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, coef, grad_at_pixel, grad);
+    with_value<LOVASZ_SOFTMAX, LOVASZ_HINGE>(a.mode, [&](auto mode) {
+        hipLaunchKernelGGL(lovasz_bwd_kernel<mode()>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, coef, grad_at_pixel, grad); });
     return check_launch();
 }
 

@@ -9,6 +9,7 @@
 // One kernel family serves both: a 2-D call is a 3-D one with D = OD = 1 and z0 = 0.  HBM-bound streaming kernels (no MFMA);
 // each lane owns 4 consecutive output voxels of one row and reads them with 16-byte loads when the window is aligned.
 #include "ptb_crop_device.h"
+#include "ptb_dispatch.h"
 
 namespace ptb {
 
@@ -164,19 +165,6 @@ __global__ __launch_bounds__(256) void crop_last_kernel(const CropArgs a, bool v
     }
 }
 
-template <int KIND>
-void launch_kind(const CropArgs& a, int layout, bool vec, bool repack, dim3 grid, hipStream_t s) {
-    constexpr bool argmax = KIND == PTB_CROP_ARGMAX_U8 || KIND == PTB_CROP_ARGMAX_I64;
-    if (argmax || layout == 0 || a.C == 1) {
-        hipLaunchKernelGGL(crop_planar_kernel<KIND>, grid, dim3(256), 0, s, a, vec);
-    } else if constexpr (!argmax) {
-        if (a.C == 2) hipLaunchKernelGGL((crop_last_kernel<KIND, 2>), grid, dim3(256), 0, s, a, vec, repack);
-        else if (a.C == 3) hipLaunchKernelGGL((crop_last_kernel<KIND, 3>), grid, dim3(256), 0, s, a, vec, repack);
-        else if (a.C == 4) hipLaunchKernelGGL((crop_last_kernel<KIND, 4>), grid, dim3(256), 0, s, a, vec, repack);
-        else hipLaunchKernelGGL((crop_last_kernel<KIND, 0>), grid, dim3(256), 0, s, a, vec, repack);
-    }
-}
-
 // Both entry points, after their own argument checks: a non-empty window inside the accumulator, layout 0 | 1, kind PTB_CROP_*.
 int launch_crop(const CropArgs& a, int layout, int kind, hipStream_t s) {
     const long long total = (long long)a.OD * a.OH * ((a.OW + 3) / 4);
@@ -185,14 +173,15 @@ int launch_crop(const CropArgs& a, int layout, int kind, hipStream_t s) {
     const bool vec = !g_force_scalar && a.W % 4 == 0 && a.x0 % 4 == 0 && aligned16(a.vol) && aligned16(a.norm);
     // fp32 channel-last: exchange the lanes' runs through LDS so that the stores are lane-contiguous (C == 1 already is)
     const bool repack = !g_force_scalar && kind == PTB_CROP_F32 && a.C > 1 && a.OW % 4 == 0 && aligned16(a.out);
-    switch (kind) {
-        case PTB_CROP_F32: launch_kind<PTB_CROP_F32>(a, layout, vec, repack, grid, s); break;
-        case PTB_CROP_U8: launch_kind<PTB_CROP_U8>(a, layout, vec, repack, grid, s); break;
-        case PTB_CROP_ARGMAX_U8: launch_kind<PTB_CROP_ARGMAX_U8>(a, layout, vec, repack, grid, s); break;
-        case PTB_CROP_ARGMAX_I64: launch_kind<PTB_CROP_ARGMAX_I64>(a, layout, vec, repack, grid, s); break;
-        case PTB_CROP_F16: launch_kind<PTB_CROP_F16>(a, layout, vec, repack, grid, s); break;
-        default: launch_kind<PTB_CROP_BF16>(a, layout, vec, repack, grid, s); break;
-    }
+    with_crop_kind(kind, [&](auto k) {
+        constexpr bool argmax = k() == PTB_CROP_ARGMAX_U8 || k() == PTB_CROP_ARGMAX_I64;
+        if (argmax || layout == 0 || a.C == 1) {
+            hipLaunchKernelGGL(crop_planar_kernel<k()>, grid, dim3(256), 0, s, a, vec);
+        } else if constexpr (!argmax) {
+            with_value<2, 3, 4, 0>(a.C, [&](auto c) {   // 0: C at run time
+                hipLaunchKernelGGL((crop_last_kernel<k(), c()>), grid, dim3(256), 0, s, a, vec, repack); });
+        }
+    });
     return check_launch();
 }
 

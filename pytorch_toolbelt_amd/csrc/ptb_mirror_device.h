@@ -5,10 +5,6 @@
 
 namespace ptb {
 
-// LD (ptb_view_device.h's ld4 codes: 1 = fp32 non-temporal, 2 = fp16, 3 = bf16) -> the PTB_* element type widen<> reads
-template <int LD>
-constexpr int ld_dtype() { return LD == 2 ? PTB_F16 : (LD == 3 ? PTB_BF16 : PTB_F32); }
-
 // Element offset, inside one [D, H, W] plane, of the PIX source elements view `m` puts at output (z, y, x .. x + PIX - 1): the
 // first of them in memory order (a W-flipped run is read from there and reversed).
 template <int PIX>

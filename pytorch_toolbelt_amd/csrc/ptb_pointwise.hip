@@ -13,6 +13,7 @@
 // backward is one read + one write.  All HBM-bound streaming: 16 B per lane, no MFMA.  Scalar epilogues (means,
 // normalisation, class-balance weights) stay on the device in the caller's autograd graph, so nothing synchronises.
 #include "ptb_common.h"
+#include "ptb_dispatch.h"
 
 namespace ptb {
 
@@ -672,15 +673,11 @@ static int pw_zero(double* sums, int* error_flag, hipStream_t s) {   // slot sum
 
 using namespace ptb;
 
-#define PTB_PW_DISPATCH(KERNEL, VECFLAG, ...)                                                       \
-    switch (kind) {                                                                                 \
-        case PW_SOFT_BCE: if (VECFLAG) KERNEL(PW_SOFT_BCE, true, __VA_ARGS__); else KERNEL(PW_SOFT_BCE, false, __VA_ARGS__); break;             \
-        case PW_BALANCED_BCE: if (VECFLAG) KERNEL(PW_BALANCED_BCE, true, __VA_ARGS__); else KERNEL(PW_BALANCED_BCE, false, __VA_ARGS__); break; \
-        case PW_QFL: if (VECFLAG) KERNEL(PW_QFL, true, __VA_ARGS__); else KERNEL(PW_QFL, false, __VA_ARGS__); break;                           \
-        case PW_WING: if (VECFLAG) KERNEL(PW_WING, true, __VA_ARGS__); else KERNEL(PW_WING, false, __VA_ARGS__); break;                       \
-        case PW_SOFT_F1: if (VECFLAG) KERNEL(PW_SOFT_F1, true, __VA_ARGS__); else KERNEL(PW_SOFT_F1, false, __VA_ARGS__); break;              \
-        default: if (VECFLAG) KERNEL(PW_LOGCOSH, true, __VA_ARGS__); else KERNEL(PW_LOGCOSH, false, __VA_ARGS__); break;                      \
-    }
+// the PW_* kind of a point-wise loss (fill_pw has validated it)
+template <class F>
+static void with_pw_kind(int kind, F&& f) {
+    with_value<PW_SOFT_BCE, PW_BALANCED_BCE, PW_QFL, PW_WING, PW_SOFT_F1, PW_LOGCOSH>(kind, f);
+}
 
 extern "C" int ptb_pointwise_loss_fwd(int kind, const float* x, const float* t, const float* chan_w, const float* chan_pw, double* sums,
                                       float* elem_out, int64_t n, int C, int64_t HW, int flags, float p0, float p1, float p2,
@@ -694,9 +691,8 @@ extern "C" int ptb_pointwise_loss_fwd(int kind, const float* x, const float* t, 
     a.sums = sums; a.out = elem_out;
     const bool vec = pw_vec(a, nullptr);
     const dim3 grid(pw_grid(vec ? n / 4 : n)), block(256);
-#define PTB_PW_FWD(K, V, dummy) hipLaunchKernelGGL((pw_fwd_kernel<K, V>), grid, block, 0, s, a)
-    PTB_PW_DISPATCH(PTB_PW_FWD, vec, 0)
-#undef PTB_PW_FWD
+    with_pw_kind(kind, [&](auto k) { with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((pw_fwd_kernel<k(), v()>), grid, block, 0, s, a); }); });
     return check_launch();
 }
 
@@ -713,41 +709,27 @@ extern "C" int ptb_pointwise_loss_apply(int kind, int emit_loss, const float* x,
     const bool vec = pw_vec(a, grad_elem);
     const dim3 grid(pw_grid(vec ? n / 4 : n)), block(256);
     if (emit_loss) {
-        if (vec) hipLaunchKernelGGL((pw_apply_kernel<PW_BALANCED_BCE, true, true>), grid, block, 0, s, a, coef, grad_elem);
-        else hipLaunchKernelGGL((pw_apply_kernel<PW_BALANCED_BCE, false, true>), grid, block, 0, s, a, coef, grad_elem);
+        with_bool(vec, [&](auto v) {
+            hipLaunchKernelGGL((pw_apply_kernel<PW_BALANCED_BCE, v(), true>), grid, block, 0, s, a, coef, grad_elem); });
         return check_launch();
     }
-#define PTB_PW_BWD(K, V, dummy) hipLaunchKernelGGL((pw_apply_kernel<K, V, false>), grid, block, 0, s, a, coef, grad_elem)
-    PTB_PW_DISPATCH(PTB_PW_BWD, vec, 0)
-#undef PTB_PW_BWD
+    with_pw_kind(kind, [&](auto k) { with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((pw_apply_kernel<k(), v(), false>), grid, block, 0, s, a, coef, grad_elem); }); });
     return check_launch();
 }
 
 static int launch_sce(const SceArgs& a, int mode, const float* coef, const float* grad_pix, float* grad, hipStream_t s) {
     const bool vec = !g_force_scalar && a.HW % 4 == 0 && aligned16(a.x) && aligned16(a.labels) && (!a.pix_out || aligned16(a.pix_out)) &&
                      (!grad || aligned16(grad)) && (!grad_pix || aligned16(grad_pix));
-#define PTB_SCE(PIX, CREG)                                                                                              \
-    do {                                                                                                                \
-        const dim3 grid(pw_grid((long long)a.B * ((a.HW + PIX - 1) / PIX))), block(256);                                \
-        if (mode == 0) hipLaunchKernelGGL((soft_ce_kernel<PIX, CREG, 0>), grid, block, 0, s, a, coef, grad_pix, grad);  \
-        else hipLaunchKernelGGL((soft_ce_kernel<PIX, CREG, 1>), grid, block, 0, s, a, coef, grad_pix, grad);            \
-    } while (0)
     if (a.C <= 16) {
-        if (vec) {
-            if (a.C <= 4) PTB_SCE(4, 4);
-            else if (a.C <= 8) PTB_SCE(4, 8);
-            else PTB_SCE(4, 16);
-        } else {
-            if (a.C <= 4) PTB_SCE(1, 4);
-            else if (a.C <= 8) PTB_SCE(1, 8);
-            else PTB_SCE(1, 16);
-        }
+        with_bool(vec, [&](auto v) { with_at_most<4, 8, 16>(a.C, [&](auto cr) { with_value<0, 1>(mode, [&](auto m) {
+            constexpr int PIX = v() ? 4 : 1;
+            const dim3 grid(pw_grid((long long)a.B * ((a.HW + PIX - 1) / PIX))), block(256);
+            hipLaunchKernelGGL((soft_ce_kernel<PIX, cr(), m()>), grid, block, 0, s, a, coef, grad_pix, grad); }); }); });
     } else {
         const dim3 grid(pw_grid((long long)a.B * a.HW)), block(256);
-        if (mode == 0) hipLaunchKernelGGL(soft_ce_generic_kernel<0>, grid, block, 0, s, a, coef, grad_pix, grad);
-        else hipLaunchKernelGGL(soft_ce_generic_kernel<1>, grid, block, 0, s, a, coef, grad_pix, grad);
+        with_value<0, 1>(mode, [&](auto m) { hipLaunchKernelGGL(soft_ce_generic_kernel<m()>, grid, block, 0, s, a, coef, grad_pix, grad); });
     }
-#undef PTB_SCE
     return check_launch();
 }
 
@@ -798,7 +780,6 @@ extern "C" int ptb_bitempered_rows(const float* activations, const float* onehot
     BtRowArgs a{activations, onehot, grad_loss, out, (long long)R, K, t1, t2, smoothing, iters};
     const long long blocks = (R + 3) / 4;
     const dim3 grid((unsigned)(blocks < 256 * 8 ? blocks : 256 * 8)), block(256);
-    if (backward) hipLaunchKernelGGL(bitempered_rows_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(bitempered_rows_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+    with_bool(backward, [&](auto bw) { hipLaunchKernelGGL(bitempered_rows_kernel<bw()>, grid, block, 0, (hipStream_t)stream, a); });
     return check_launch();
 }

@@ -4,6 +4,7 @@
 // reference's torch kernels to rounding.
 #include <algorithm>
 
+#include "ptb_dispatch.h"
 #include "ptb_view_device.h"
 
 namespace ptb {
@@ -754,12 +755,8 @@ static int ms_reduce_impl(const float* const* inputs, const int* hs_full, const 
     if (g_ms_tiled && tiles <= 0x7fffffffLL) {
         const dim3 grid((unsigned)tiles), block(256);
         hipStream_t st = (hipStream_t)stream;
-#define PTB_MS(OPK) do { if (align_corners) hipLaunchKernelGGL((ms_reduce_tiled_kernel<OPK, 1>), grid, block, 0, st, a, out); \
-                        else hipLaunchKernelGGL((ms_reduce_tiled_kernel<OPK, 0>), grid, block, 0, st, a, out); } while (0)
-        if (reduction == PTB_RED_GMEAN) PTB_MS(2);
-        else if (reduction >= PTB_RED_GMEAN) PTB_MS(1);
-        else PTB_MS(0);
-#undef PTB_MS
+        with_reduction3(reduction, [&](auto opk) { with_bool(align_corners, [&](auto al) {
+            hipLaunchKernelGGL((ms_reduce_tiled_kernel<opk(), (al() ? 1 : 0)>), grid, block, 0, st, a, out); }); });
         return check_launch();
     }
     const long long total = planes * hout * ((wout + 3) / 4);
@@ -792,42 +789,21 @@ extern "C" int ptb_ms_deaug_reduce_strip(const float* const* inputs, const int* 
 // Keeping neighbours on one L2 pays; narrow strips cost more in DRAM page locality than the vertical halo reuse returns.
 namespace ptb { int g_ms_tile_rows = 32; int g_ms_strip = 64; int g_ms_tile_w = 128; }   // key 15: 128 (default) = 128 x 16 output tiles when the windows fit (NV <= 2), 64 = 64 x g_ms_tile_rows
 
-template <int NV, int INNER, int TH>
-static void launch_fz_th(const FzArgs& a, float* out, unsigned blocks, hipStream_t st) {
-    const dim3 grid(blocks), block(256);
-#define PTB_FZ(OUTER) do { if (a.align_corners) hipLaunchKernelGGL((ms_flip_reduce_kernel<NV, INNER, OUTER, 1, TH>), grid, block, 0, st, a, out); \
-                           else hipLaunchKernelGGL((ms_flip_reduce_kernel<NV, INNER, OUTER, 0, TH>), grid, block, 0, st, a, out); } while (0)
-    if (a.op_outer == PTB_RED_GMEAN) PTB_FZ(2);
-    else if (a.op_outer >= PTB_RED_GMEAN) PTB_FZ(1);
-    else PTB_FZ(0);
-#undef PTB_FZ
-}
-
-template <int NV, int INNER, int TH>
-static void launch_fz_wide(const FzArgs& a, float* out, hipStream_t st) {   // 128 x TH tiles
-    const long long tiles = (long long)a.planes * ((a.hout + TH - 1) / TH) * ((a.wout + 127) / 128);
+// ms_flip_reduce_kernel<NV, INNER, OUTER, ALIGN, TH, TW> over TW x th output tiles.  Compiled: NV = 1 | 2 | 4 views, a single view
+// without an inner reduction; 64-wide tiles of 16 | 32 | 64 rows, 128-wide tiles of 16 rows for NV <= 2 only.
+template <int TW>
+static void launch_fz(const FzArgs& a, float* out, int V, int th, int strip, hipStream_t st) {
+    const long long tiles = (long long)a.planes * ((a.hout + th - 1) / th) * ((a.wout + TW - 1) / TW);
     FzArgs b = a;
-    b.strip = 64;
+    b.strip = strip;
     b.total_tiles = tiles;
-    const dim3 grid((unsigned)(8 * ((tiles + 7) / 8))), block(256);
-#define PTB_FZW(OUTER) do { if (a.align_corners) hipLaunchKernelGGL((ms_flip_reduce_kernel<NV, INNER, OUTER, 1, TH, 128>), grid, block, 0, st, b, out); \
-                            else hipLaunchKernelGGL((ms_flip_reduce_kernel<NV, INNER, OUTER, 0, TH, 128>), grid, block, 0, st, b, out); } while (0)
-    if (a.op_outer == PTB_RED_GMEAN) PTB_FZW(2);
-    else if (a.op_outer >= PTB_RED_GMEAN) PTB_FZW(1);
-    else PTB_FZW(0);
-#undef PTB_FZW
-}
-
-template <int NV, int INNER>
-static void launch_fz(const FzArgs& a, float* out, int th, hipStream_t st) {
-    const long long tiles = (long long)a.planes * ((a.hout + th - 1) / th) * ((a.wout + FZ_T - 1) / FZ_T);
-    FzArgs b = a;
-    b.strip = g_ms_strip;
-    b.total_tiles = tiles;
-    const long long blocks = b.strip > 0 ? 8 * ((tiles + 7) / 8) : tiles;
-    if (th == 16) launch_fz_th<NV, INNER, 16>(b, out, (unsigned)blocks, st);
-    else if (th == 32) launch_fz_th<NV, INNER, 32>(b, out, (unsigned)blocks, st);
-    else launch_fz_th<NV, INNER, 64>(b, out, (unsigned)blocks, st);
+    const dim3 grid((unsigned)(b.strip > 0 ? 8 * ((tiles + 7) / 8) : tiles)), block(256);
+    with_value<1, 2, 4>(V, [&](auto nv) { with_reduction3(V == 1 ? PTB_RED_SUM : a.op_inner, [&](auto inner) {
+        with_reduction3(a.op_outer, [&](auto outer) { with_bool(a.align_corners, [&](auto al) { with_value<16, 32, 64>(th, [&](auto thv) {
+            if constexpr (!(nv() == 1 && inner() != 0) && !(TW == 128 && (nv() == 4 || thv() != 16)))
+                hipLaunchKernelGGL((ms_flip_reduce_kernel<nv(), inner(), outer(), (al() ? 1 : 0), thv(), TW>), grid, block, 0, st, b, out);
+            else no_instance("ms_flip_reduce_kernel");
+        }); }); }); }); });
 }
 
 static int ms_flip_impl(const float* const* inputs, const int* hs, const int* ws, const int* src_row0, const int* src_rows, int n, int V,
@@ -922,18 +898,12 @@ static int ms_flip_impl(const float* const* inputs, const int* hs, const int* ws
     const int th = g_ms_tile_rows;
     if (planes * ((out_rows + th - 1) / th) * ((wout + FZ_T - 1) / FZ_T) > 0x7fffffffLL) return PTB_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    const int inner = inner_reduction == PTB_RED_GMEAN ? 2 : (inner_reduction > PTB_RED_GMEAN ? 1 : 0);
     if (g_ms_tile_w == 128 && wide_ok && V <= 2 && planes * ((out_rows + 15) / 16) * ((wout + 127) / 128) <= 0x7fffffffLL) {
         // (128 x 32 tiles measured slower: 363 / 520 us mean / gmean at cfg5 against 337 / 385 us for 128 x 16)
-        if (V == 1) launch_fz_wide<1, 0, 16>(a, out, st);
-        else if (inner == 2) launch_fz_wide<2, 2, 16>(a, out, st);
-        else if (inner) launch_fz_wide<2, 1, 16>(a, out, st);
-        else launch_fz_wide<2, 0, 16>(a, out, st);
+        launch_fz<128>(a, out, V, 16, 64, st);
         return check_launch();
     }
-    if (V == 1) launch_fz<1, 0>(a, out, th, st);
-    else if (V == 2) { if (inner == 2) launch_fz<2, 2>(a, out, th, st); else if (inner) launch_fz<2, 1>(a, out, th, st); else launch_fz<2, 0>(a, out, th, st); }
-    else { if (inner == 2) launch_fz<4, 2>(a, out, th, st); else if (inner) launch_fz<4, 1>(a, out, th, st); else launch_fz<4, 0>(a, out, th, st); }
+    launch_fz<FZ_T>(a, out, V, th, g_ms_strip, st);
     return check_launch();
 }
 
@@ -972,8 +942,8 @@ extern "C" int ptb_resize_nearest(const float* in, float* out, int64_t planes, i
     if (planes > 0x7fffffffLL) return PTB_EUNSUPPORTED;
     const float sh = (float)hin / (float)hout, sw = (float)win / (float)wout;
     const dim3 grid(grid_1d(planes * hout * wout)), block(256);
-    if (backward) hipLaunchKernelGGL(resize_nearest_kernel<true>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout, sh, sw);
-    else hipLaunchKernelGGL(resize_nearest_kernel<false>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout, sh, sw);
+    with_bool(backward, [&](auto bw) {
+        hipLaunchKernelGGL(resize_nearest_kernel<bw()>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout, sh, sw); });
     return check_launch();
 }
 
@@ -984,8 +954,8 @@ extern "C" int ptb_resize_nearest_exact(const float* in, float* out, int64_t pla
     if (planes > 0x7fffffffLL) return PTB_EUNSUPPORTED;
     const float sh = (float)hin / (float)hout, sw = (float)win / (float)wout;
     const dim3 grid(grid_1d(planes * hout * wout)), block(256);
-    if (backward) hipLaunchKernelGGL(resize_nearest_exact_kernel<true>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout, sh, sw);
-    else hipLaunchKernelGGL(resize_nearest_exact_kernel<false>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout, sh, sw);
+    with_bool(backward, [&](auto bw) {
+        hipLaunchKernelGGL(resize_nearest_exact_kernel<bw()>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout, sh, sw); });
     return check_launch();
 }
 
@@ -994,8 +964,8 @@ extern "C" int ptb_resize_area(const float* in, float* out, int64_t planes, int 
     if (planes == 0) return PTB_OK;
     if (planes > 0x7fffffffLL) return PTB_EUNSUPPORTED;
     const dim3 grid(grid_1d(planes * hout * wout)), block(256);
-    if (backward) hipLaunchKernelGGL(resize_area_kernel<true>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout);
-    else hipLaunchKernelGGL(resize_area_kernel<false>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout);
+    with_bool(backward, [&](auto bw) {
+        hipLaunchKernelGGL(resize_area_kernel<bw()>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout); });
     return check_launch();
 }
 
@@ -1007,8 +977,8 @@ extern "C" int ptb_resize_bicubic(const float* in, float* out, int64_t planes, i
     float sh, sw;
     resize_scales(hin, win, hout, wout, align_corners, sh, sw);
     const dim3 grid(grid_1d(planes * hout * wout)), block(256);
-    if (backward) hipLaunchKernelGGL(resize_bicubic_kernel<true>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout, sh, sw, align_corners);
-    else hipLaunchKernelGGL(resize_bicubic_kernel<false>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout, sh, sw, align_corners);
+    with_bool(backward, [&](auto bw) {
+        hipLaunchKernelGGL(resize_bicubic_kernel<bw()>, grid, block, 0, (hipStream_t)stream, in, out, (int)planes, hin, win, hout, wout, sh, sw, align_corners); });
     return check_launch();
 }
 

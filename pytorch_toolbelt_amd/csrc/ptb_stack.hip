@@ -6,6 +6,7 @@
 // tencrop TTA (T = 10), ensembles of more than 8 models, harmonic_mean / logodd_mean called with their eps argument -- as ONE pass
 // over the T planes (HBM-bound: T reads + 1 write per element), plus its backward (T + 2 reads, T writes).
 #include "ptb_common.h"
+#include "ptb_dispatch.h"
 
 namespace ptb {
 namespace {
@@ -150,10 +151,8 @@ extern "C" int ptb_stack_reduce(const float* src, int T, int64_t n, int reductio
     if (n == 0) return PTB_OK;
     const Eps e{(float)eps, (float)(1.0 - eps)};
     hipStream_t s = (hipStream_t)stream;
-    if (!g_force_scalar && n % 4 == 0 && aligned16(src) && aligned16(out))
-        hipLaunchKernelGGL((stack_reduce_kernel<true>), dim3(grid_for(n / 4)), dim3(256), 0, s, src, T, (long long)n, reduction, e, out);
-    else
-        hipLaunchKernelGGL((stack_reduce_kernel<false>), dim3(grid_for(n)), dim3(256), 0, s, src, T, (long long)n, reduction, e, out);
+    with_bool(!g_force_scalar && n % 4 == 0 && aligned16(src) && aligned16(out), [&](auto v) {
+        hipLaunchKernelGGL((stack_reduce_kernel<v()>), dim3(grid_for(v() ? n / 4 : n)), dim3(256), 0, s, src, T, (long long)n, reduction, e, out); });
     return check_launch();
 }
 
@@ -163,9 +162,7 @@ extern "C" int ptb_stack_reduce_bwd(const float* src, const float* out, const fl
     if (n == 0) return PTB_OK;
     const Eps e{(float)eps, (float)(1.0 - eps)};
     hipStream_t s = (hipStream_t)stream;
-    if (!g_force_scalar && n % 4 == 0 && aligned16(src) && aligned16(out) && aligned16(grad_out) && aligned16(grad))
-        hipLaunchKernelGGL((stack_reduce_bwd_kernel<true>), dim3(grid_for(n / 4)), dim3(256), 0, s, src, out, grad_out, T, (long long)n, reduction, e, grad);
-    else
-        hipLaunchKernelGGL((stack_reduce_bwd_kernel<false>), dim3(grid_for(n)), dim3(256), 0, s, src, out, grad_out, T, (long long)n, reduction, e, grad);
+    with_bool(!g_force_scalar && n % 4 == 0 && aligned16(src) && aligned16(out) && aligned16(grad_out) && aligned16(grad), [&](auto v) {
+        hipLaunchKernelGGL((stack_reduce_bwd_kernel<v()>), dim3(grid_for(v() ? n / 4 : n)), dim3(256), 0, s, src, out, grad_out, T, (long long)n, reduction, e, grad); });
     return check_launch();
 }

@@ -5,6 +5,7 @@
 #include <initializer_list>
 
 #include "ptb_common.h"
+#include "ptb_dispatch.h"
 
 namespace ptb {
 
@@ -259,6 +260,10 @@ __device__ __forceinline__ float widen(const void* p, long long i) {
     else return (float)static_cast<const uint16_t*>(p)[i];
 }
 
+// LD (the ld4 codes: 1 = fp32 non-temporal, 2 = fp16, 3 = bf16) -> the PTB_* element type widen<> reads
+template <int LD>
+constexpr int ld_dtype() { return LD == 2 ? PTB_F16 : (LD == 3 ? PTB_BF16 : PTB_F32); }
+
 // 4 consecutive output elements at element offset `off` of `dst`, whose element type is OUT: fp32 as one 16-byte store, fp16 / bf16
 // rounded (half_bits) as one 8-byte store (off % 4 == 0 and an 8-byte aligned dst)
 template <int OUT>
@@ -346,6 +351,19 @@ constexpr int CODES_FLIPUD = pack_codes({0, 2});
 constexpr int CODES_FLIPS = pack_codes({0, 4, 2});
 constexpr int CODES_D2 = pack_codes({0, 4, 2, 6});
 constexpr int CODES_D4 = pack_codes({0, 5, 6, 3, 1, 4, 7, 2});  // inverse views of d4_image_deaugment, tta.py:455-466
+
+// (NV, CODES) of the view sets that have compiled-in instances; every other set runs the (8, -1) instance, which reads
+// a.nviews and a.codes at run time
+template <class F>
+void with_view_set(int nviews, int codes, F&& f) {
+    if (nviews == 1 && codes == CODES_ID) f(int_c<1>{}, int_c<CODES_ID>{});
+    else if (nviews == 2 && codes == CODES_FLIPLR) f(int_c<2>{}, int_c<CODES_FLIPLR>{});
+    else if (nviews == 2 && codes == CODES_FLIPUD) f(int_c<2>{}, int_c<CODES_FLIPUD>{});
+    else if (nviews == 3 && codes == CODES_FLIPS) f(int_c<3>{}, int_c<CODES_FLIPS>{});
+    else if (nviews == 4 && codes == CODES_D2) f(int_c<4>{}, int_c<CODES_D2>{});
+    else if (nviews == 8 && codes == CODES_D4) f(int_c<8>{}, int_c<CODES_D4>{});
+    else f(int_c<8>{}, int_c<-1>{});
+}
 
 
 // The second half of gather_reduce: this thread's NV loaded float4 (row-preserving views already in output orientation, transposing

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "ptb_dispatch.h"
 #include "ptb_view_device.h"
 
 namespace ptb {
@@ -562,62 +563,37 @@ static int pack_runtime(int V, const int* views) {
     return v;
 }
 
-template <int CH, int MODE>
-static void launch_plain_ch(const ViewArgs& a, int blocks, hipStream_t s, bool nonlinear) {
-    const dim3 grid(blocks), block(CH * 16);
-    // half-precision sources (in_dtype != PTB_F32) are compiled for the default chunk rows only (callers check)
-#define PTB_PLAIN_LD(NV, CODES, LD)                                                                               \
-    do {                                                                                                          \
-        if (nonlinear) hipLaunchKernelGGL((view_plain_kernel<CH, NV, CODES, 1, MODE, LD>), grid, block, 0, s, a); \
-        else hipLaunchKernelGGL((view_plain_kernel<CH, NV, CODES, 0, MODE, LD>), grid, block, 0, s, a);           \
-    } while (0)
-#define PTB_PLAIN(NV, CODES)                                                                                      \
-    do {                                                                                                          \
-        if constexpr (CH == 32) {                                                                                 \
-            if (a.in_dtype == PTB_F16) { PTB_PLAIN_LD(NV, CODES, 2); break; }                                     \
-            if (a.in_dtype == PTB_BF16) { PTB_PLAIN_LD(NV, CODES, 3); break; }                                    \
-        }                                                                                                         \
-        PTB_PLAIN_LD(NV, CODES, 1);                                                                               \
-    } while (0)
-    if constexpr (MODE == MODE_PERVIEW) {
-        hipLaunchKernelGGL((view_plain_kernel<CH, 1, -1, 0, MODE_PERVIEW, 1>), grid, block, 0, s, a);
-    } else {
-        if (a.nviews == 2 && a.codes == CODES_FLIPLR) PTB_PLAIN(2, CODES_FLIPLR);
-        else if (a.nviews == 2 && a.codes == CODES_FLIPUD) PTB_PLAIN(2, CODES_FLIPUD);
-        else if (a.nviews == 3 && a.codes == CODES_FLIPS) PTB_PLAIN(3, CODES_FLIPS);
-        else if (a.nviews == 4 && a.codes == CODES_D2) PTB_PLAIN(4, CODES_D2);
-        else if (a.nviews == 8 && a.codes == CODES_D4) PTB_PLAIN(8, CODES_D4);
-        else PTB_PLAIN(8, -1);
-    }
-#undef PTB_PLAIN
-#undef PTB_PLAIN_LD
+// (CH, LD) of the plain and accumulate view kernels: half-precision sources (LD 2 / 3) are compiled for the default chunk rows
+// (CH == 32) only; run_plain refuses them at the other sizes, and the accumulate callers check.
+template <class F>
+static void with_view_src(int ch, int in_dtype, F&& f) {
+    with_value<64, 32, 16>(ch, [&](auto chv) {
+        if constexpr (chv() == 32) with_src_dtype(in_dtype, [&](auto ld) { f(chv, ld); });
+        else f(chv, int_c<1>{});
+    });
 }
 
-template <int CH>
-static void launch_accum_ch(const ViewArgs& a, const CellArgs& g, int blocks, hipStream_t s, bool nonlinear) {
-    const dim3 grid(blocks), block(CH * 16);
-#define PTB_ACCUM_LD(NV, CODES, LD)                                                                               \
-    do {                                                                                                          \
-        if (nonlinear) hipLaunchKernelGGL((view_accum_kernel<CH, NV, CODES, 1, LD>), grid, block, 0, s, a, g);    \
-        else hipLaunchKernelGGL((view_accum_kernel<CH, NV, CODES, 0, LD>), grid, block, 0, s, a, g);              \
-    } while (0)
-#define PTB_ACCUM(NV, CODES)                                                                                      \
-    do {                                                                                                          \
-        if constexpr (CH == 32) {                                                                                 \
-            if (a.in_dtype == PTB_F16) { PTB_ACCUM_LD(NV, CODES, 2); break; }                                     \
-            if (a.in_dtype == PTB_BF16) { PTB_ACCUM_LD(NV, CODES, 3); break; }                                    \
-        }                                                                                                         \
-        PTB_ACCUM_LD(NV, CODES, 1);                                                                               \
-    } while (0)
-    if (a.nviews == 1 && a.codes == CODES_ID) PTB_ACCUM(1, CODES_ID);
-    else if (a.nviews == 2 && a.codes == CODES_FLIPLR) PTB_ACCUM(2, CODES_FLIPLR);
-    else if (a.nviews == 2 && a.codes == CODES_FLIPUD) PTB_ACCUM(2, CODES_FLIPUD);
-    else if (a.nviews == 3 && a.codes == CODES_FLIPS) PTB_ACCUM(3, CODES_FLIPS);
-    else if (a.nviews == 4 && a.codes == CODES_D2) PTB_ACCUM(4, CODES_D2);
-    else if (a.nviews == 8 && a.codes == CODES_D4) PTB_ACCUM(8, CODES_D4);
-    else PTB_ACCUM(8, -1);
-#undef PTB_ACCUM
-#undef PTB_ACCUM_LD
+static void launch_plain(const ViewArgs& a, int blocks, int ch, int mode, hipStream_t s) {
+    const dim3 grid(blocks);
+    if (mode == MODE_PERVIEW) {
+        with_value<64, 32, 16>(ch, [&](auto chv) {
+            hipLaunchKernelGGL((view_plain_kernel<chv(), 1, -1, 0, MODE_PERVIEW, 1>), grid, dim3(chv() * 16), 0, s, a); });
+        return;
+    }
+    with_view_src(ch, a.in_dtype, [&](auto chv, auto ld) { with_reduction(a.op, [&](auto opk) {
+        with_view_set(a.nviews, a.codes, [&](auto nv, auto codes) {
+            // no identity instance of the reduce: a single view goes through the run-time codes
+            constexpr int NV = nv() == 1 ? 8 : nv(), CODES = nv() == 1 ? -1 : codes();
+            hipLaunchKernelGGL((view_plain_kernel<chv(), NV, CODES, opk(), MODE_REDUCE, ld()>), grid, dim3(chv() * 16), 0, s, a);
+        }); }); });
+}
+
+static void launch_accum(const ViewArgs& a, const CellArgs& g, int blocks, int ch, hipStream_t s) {
+    const dim3 grid(blocks);
+    with_view_src(ch, a.in_dtype, [&](auto chv, auto ld) { with_reduction(a.op, [&](auto opk) {
+        with_view_set(a.nviews, a.codes, [&](auto nv, auto codes) {
+            hipLaunchKernelGGL((view_accum_kernel<chv(), nv(), codes(), opk(), ld()>), grid, dim3(chv() * 16), 0, s, a, g);
+        }); }); });
 }
 
 static bool has_transpose(int V, int codes) {
@@ -651,7 +627,6 @@ static bool aligned_elems(const void* p, int dtype) {  // 4 source elements per 
 }
 
 static int run_plain(ViewArgs& a, int ntiles_out, int mode, hipStream_t s, bool src_cl = false) {
-    const bool nonlinear = a.op >= PTB_RED_GMEAN;
     const int nT = mode == MODE_PERVIEW ? 1 : count_transpose(a.nviews, a.codes);
     const bool tr = mode == MODE_PERVIEW ? has_transpose(a.nviews, a.codes) : nT > 0;
     bool fast = !g_force_scalar && (a.W % 4 == 0) && (a.dst_row_stride % 4 == 0) && (a.dst_chan_stride % 4 == 0) &&
@@ -674,15 +649,7 @@ static int run_plain(ViewArgs& a, int ntiles_out, int mode, hipStream_t s, bool 
         else hipLaunchKernelGGL(view_plain_scalar_kernel<MODE_REDUCE>, dim3((unsigned)blocks), dim3(256), 0, s, a);
         return check_launch();
     }
-    if (mode == MODE_PERVIEW) {
-        if (ch == 64) launch_plain_ch<64, MODE_PERVIEW>(a, (int)blocks, s, false);
-        else if (ch == 32) launch_plain_ch<32, MODE_PERVIEW>(a, (int)blocks, s, false);
-        else launch_plain_ch<16, MODE_PERVIEW>(a, (int)blocks, s, false);
-    } else {
-        if (ch == 64) launch_plain_ch<64, MODE_REDUCE>(a, (int)blocks, s, nonlinear);
-        else if (ch == 32) launch_plain_ch<32, MODE_REDUCE>(a, (int)blocks, s, nonlinear);
-        else launch_plain_ch<16, MODE_REDUCE>(a, (int)blocks, s, nonlinear);
-    }
+    launch_plain(a, (int)blocks, ch, mode, s);
     return check_launch();
 }
 
@@ -691,22 +658,16 @@ static int launch_group(const ViewArgs& a, const CellArgs& g, const std::vector<
     const long long blocks = (long long)a.total_chunks * a.C;
     if (blocks <= 0) return PTB_OK;
     if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
-    const bool nonlinear = a.op >= PTB_RED_GMEAN;
     if (!a.dst) {  // norm only (C == 1)
         if (!fast) hipLaunchKernelGGL(norm_accum_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, g);
-        else if (ch == 64) hipLaunchKernelGGL(norm_accum_kernel<64>, dim3((unsigned)blocks), dim3(1024), 0, s, a, g);
-        else if (ch == 32) hipLaunchKernelGGL(norm_accum_kernel<32>, dim3((unsigned)blocks), dim3(512), 0, s, a, g);
-        else hipLaunchKernelGGL(norm_accum_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, a, g);
+        else with_value<64, 32, 16>(ch, [&](auto chv) {
+            hipLaunchKernelGGL(norm_accum_kernel<chv()>, dim3((unsigned)blocks), dim3(chv() * 16), 0, s, a, g); });
     } else if (src_cl) {   // PTB_SRC_CHANNELS_LAST: the same cells and chunks, one workgroup per chunk over all channels, any shape
         cl_launch_accum(a, g, ch, s);
     } else if (!fast) {
         hipLaunchKernelGGL(view_accum_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, g);
-    } else if (ch == 64) {
-        launch_accum_ch<64>(a, g, (int)blocks, s, nonlinear);
-    } else if (ch == 32) {
-        launch_accum_ch<32>(a, g, (int)blocks, s, nonlinear);
     } else {
-        launch_accum_ch<16>(a, g, (int)blocks, s, nonlinear);
+        launch_accum(a, g, (int)blocks, ch, s);
     }
     const int rc = check_launch();
     if (rc == PTB_OK) mark_written(cells, fr);
@@ -926,27 +887,10 @@ extern "C" int ptb_accumulate_planned2(float* image, const float* norm_full, flo
 
 static void launch_band(const ViewArgs& a, const BandArgs& g, int blocks, hipStream_t s) {
     const dim3 grid(blocks), block(512);
-    const bool nonlinear = a.op >= PTB_RED_GMEAN;
-#define PTB_BAND_LD(NV, CODES, LD)                                                                             \
-    do {                                                                                                       \
-        if (nonlinear) hipLaunchKernelGGL((band_merge_kernel<NV, CODES, 1, LD>), grid, block, 0, s, a, g);     \
-        else hipLaunchKernelGGL((band_merge_kernel<NV, CODES, 0, LD>), grid, block, 0, s, a, g);               \
-    } while (0)
-#define PTB_BAND(NV, CODES)                                                                                    \
-    do {                                                                                                       \
-        if (a.in_dtype == PTB_F16) PTB_BAND_LD(NV, CODES, 2);                                                  \
-        else if (a.in_dtype == PTB_BF16) PTB_BAND_LD(NV, CODES, 3);                                            \
-        else PTB_BAND_LD(NV, CODES, 1);                                                                        \
-    } while (0)
-    if (a.nviews == 1 && a.codes == CODES_ID) PTB_BAND(1, CODES_ID);
-    else if (a.nviews == 2 && a.codes == CODES_FLIPLR) PTB_BAND(2, CODES_FLIPLR);
-    else if (a.nviews == 2 && a.codes == CODES_FLIPUD) PTB_BAND(2, CODES_FLIPUD);
-    else if (a.nviews == 3 && a.codes == CODES_FLIPS) PTB_BAND(3, CODES_FLIPS);
-    else if (a.nviews == 4 && a.codes == CODES_D2) PTB_BAND(4, CODES_D2);
-    else if (a.nviews == 8 && a.codes == CODES_D4) PTB_BAND(8, CODES_D4);
-    else PTB_BAND(8, -1);
-#undef PTB_BAND
-#undef PTB_BAND_LD
+    with_src_dtype(a.in_dtype, [&](auto ld) { with_reduction(a.op, [&](auto opk) {
+        with_view_set(a.nviews, a.codes, [&](auto nv, auto codes) {
+            hipLaunchKernelGGL((band_merge_kernel<nv(), codes(), opk(), ld()>), grid, block, 0, s, a, g);
+        }); }); });
 }
 
 extern "C" int ptb_merge_band(float* merged, const float* norm_full, const float* weight, const void* const* tile_src,
@@ -1112,9 +1056,8 @@ extern "C" int ptb_view_transform(const float* in, float* out, int V, const int*
         const long long blocks = (long long)B * C * a.chunks_x * a.chunks_y;
         if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
         hipStream_t s = (hipStream_t)stream;
-        if (ch == 64) hipLaunchKernelGGL((view_scatter_kernel<64, false>), dim3((unsigned)blocks), dim3(1024), 0, s, a, B);
-        else if (ch == 32) hipLaunchKernelGGL((view_scatter_kernel<32, false>), dim3((unsigned)blocks), dim3(512), 0, s, a, B);
-        else hipLaunchKernelGGL((view_scatter_kernel<16, false>), dim3((unsigned)blocks), dim3(256), 0, s, a, B);
+        with_value<64, 32, 16>(ch, [&](auto chv) {
+            hipLaunchKernelGGL((view_scatter_kernel<chv(), false>), dim3((unsigned)blocks), dim3(chv() * 16), 0, s, a, B); });
         return check_launch();
     }
     return run_plain(a, V * B, MODE_PERVIEW, (hipStream_t)stream);
@@ -1184,9 +1127,8 @@ extern "C" int ptb_deaug_reduce_bwd(const float* in, const float* out, const flo
         a.chunks_y = (H + ch - 1) / ch;
         const long long blocks = (long long)B * C * a.chunks_x * a.chunks_y;
         if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
-        if (ch == 64) hipLaunchKernelGGL((view_scatter_kernel<64, true>), dim3((unsigned)blocks), dim3(1024), 0, s, a, B);
-        else if (ch == 32) hipLaunchKernelGGL((view_scatter_kernel<32, true>), dim3((unsigned)blocks), dim3(512), 0, s, a, B);
-        else hipLaunchKernelGGL((view_scatter_kernel<16, true>), dim3((unsigned)blocks), dim3(256), 0, s, a, B);
+        with_value<64, 32, 16>(ch, [&](auto chv) {
+            hipLaunchKernelGGL((view_scatter_kernel<chv(), true>), dim3((unsigned)blocks), dim3(chv() * 16), 0, s, a, B); });
     } else {
         const long long n = (long long)B * C * H * W;
         const long long want = (n + 255) / 256;

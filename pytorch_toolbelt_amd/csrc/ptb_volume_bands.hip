@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ptb_crop_device.h"
+#include "ptb_dispatch.h"
 #include "ptb_mirror_device.h"
 #include "ptb_volume_device.h"
 
@@ -243,31 +244,11 @@ __global__ __launch_bounds__(VB_BLOCK) void volume_gather_kernel(const VolArgs a
     }
 }
 
-template <int LD, int MODE, int PIX>
-static void launch_gather_kind(const VolArgs& a, const VolTiles& t, int kind, int n_items, hipStream_t s) {
+static void launch_gather(const VolArgs& a, const VolTiles& t, int in_dtype, int mode, bool vec, int kind, int n_items, hipStream_t s) {
     const dim3 grid((unsigned)n_items), block(VB_BLOCK);
-    switch (kind) {
-        case PTB_CROP_F32: hipLaunchKernelGGL((volume_gather_kernel<LD, MODE, PIX, PTB_CROP_F32>), grid, block, 0, s, a, t); break;
-        case PTB_CROP_U8: hipLaunchKernelGGL((volume_gather_kernel<LD, MODE, PIX, PTB_CROP_U8>), grid, block, 0, s, a, t); break;
-        case PTB_CROP_ARGMAX_U8: hipLaunchKernelGGL((volume_gather_kernel<LD, MODE, PIX, PTB_CROP_ARGMAX_U8>), grid, block, 0, s, a, t); break;
-        case PTB_CROP_ARGMAX_I64: hipLaunchKernelGGL((volume_gather_kernel<LD, MODE, PIX, PTB_CROP_ARGMAX_I64>), grid, block, 0, s, a, t); break;
-        case PTB_CROP_F16: hipLaunchKernelGGL((volume_gather_kernel<LD, MODE, PIX, PTB_CROP_F16>), grid, block, 0, s, a, t); break;
-        default: hipLaunchKernelGGL((volume_gather_kernel<LD, MODE, PIX, PTB_CROP_BF16>), grid, block, 0, s, a, t); break;
-    }
-}
-
-template <int LD>
-static void launch_gather_ld(const VolArgs& a, const VolTiles& t, int mode, bool vec, int kind, int n_items, hipStream_t s) {
-    if (mode == 0) {
-        if (vec) launch_gather_kind<LD, 0, 4>(a, t, kind, n_items, s);
-        else launch_gather_kind<LD, 0, 1>(a, t, kind, n_items, s);
-    } else if (mode == 1) {
-        if (vec) launch_gather_kind<LD, 1, 4>(a, t, kind, n_items, s);
-        else launch_gather_kind<LD, 1, 1>(a, t, kind, n_items, s);
-    } else {
-        if (vec) launch_gather_kind<LD, 2, 4>(a, t, kind, n_items, s);
-        else launch_gather_kind<LD, 2, 1>(a, t, kind, n_items, s);
-    }
+    with_src_dtype(in_dtype, [&](auto ld) { with_value<0, 1, 2>(mode, [&](auto m) { with_bool(vec, [&](auto v) {
+        with_crop_kind(kind, [&](auto k) {
+            hipLaunchKernelGGL((volume_gather_kernel<ld(), m(), (v() ? 4 : 1), k()>), grid, block, 0, s, a, t); }); }); }); });
 }
 
 }  // namespace ptb
@@ -576,10 +557,8 @@ extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const 
         hipStream_t s = (hipStream_t)stream;
         if (src_cl) {   // PTB_SRC_CHANNELS_LAST: the same work-item table, one lane per voxel over all channels
             cl3_launch_gather(a, t, (int)g.tiles.size(), in_dtype, mode, p->kind, g.n_items, s);
-        } else switch (in_dtype) {
-            case PTB_F32: launch_gather_ld<1>(a, t, mode, vec, p->kind, g.n_items, s); break;
-            case PTB_F16: launch_gather_ld<2>(a, t, mode, vec, p->kind, g.n_items, s); break;
-            default: launch_gather_ld<3>(a, t, mode, vec, p->kind, g.n_items, s); break;
+        } else {
+            launch_gather(a, t, in_dtype, mode, vec, p->kind, g.n_items, s);
         }
         if (int rc = check_launch()) return rc;
         ++p->groups_done;

@@ -18,6 +18,7 @@
 // the divisor, the reduced value of a half-precision source rounded to its type (round_src1), then tile * window rounded and added in
 // integration order (no contraction) -- bit-identical results.
 #include "ptb_crop_device.h"
+#include "ptb_dispatch.h"
 #include "ptb_mirror_device.h"
 #include "ptb_volume_device.h"
 
@@ -332,7 +333,7 @@ __global__ __launch_bounds__(VB_BLOCK) void cl3_gather_kernel(const VolArgs a, c
 
 // ------------------------------------------------------------------------------------------------ dispatch
 // four channels per load: C a multiple of 4 (then every voxel of an aligned tile is aligned), 16- / 8-byte aligned tiles, view strides on
-// the same grid, and the force-scalar switch off
+// the same grid, and the force-scalar switch off.  (cl_vec_ok of the 2-D unit does not look at that switch: known, and left as it is.)
 static bool cl3_vec_ok(int dtype, int C, const void* p, long long stride0, long long stride1) {
     const uintptr_t mask = dtype == PTB_F32 ? 15u : 7u;
     return !g_force_scalar && C % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & mask) == 0 && stride0 % 4 == 0 && stride1 % 4 == 0;
@@ -344,76 +345,33 @@ static dim3 cl3_grid(long long voxels, long long tiles) {
 }
 
 // (linear | non-linear reduction) x source dtype x (vector | element loads): 12 instances
-#define PTB_CL3_LAUNCH(KERNEL, dtype, nonlinear, vec, a)                                                                 \
-    do {                                                                                                                 \
-        if (dtype == PTB_F16) PTB_CL3_LAUNCH_LD(KERNEL, 2, nonlinear, vec, a);                                           \
-        else if (dtype == PTB_BF16) PTB_CL3_LAUNCH_LD(KERNEL, 3, nonlinear, vec, a);                                     \
-        else PTB_CL3_LAUNCH_LD(KERNEL, 1, nonlinear, vec, a);                                                            \
-    } while (0)
-#define PTB_CL3_LAUNCH_LD(KERNEL, LD, nonlinear, vec, a)                                                                 \
-    do {                                                                                                                 \
-        if (nonlinear) {                                                                                                 \
-            if (vec) hipLaunchKernelGGL((KERNEL<LD, 1, true>), grid, dim3(CL3_BLOCK), 0, s, a);                          \
-            else hipLaunchKernelGGL((KERNEL<LD, 1, false>), grid, dim3(CL3_BLOCK), 0, s, a);                             \
-        } else {                                                                                                         \
-            if (vec) hipLaunchKernelGGL((KERNEL<LD, 0, true>), grid, dim3(CL3_BLOCK), 0, s, a);                          \
-            else hipLaunchKernelGGL((KERNEL<LD, 0, false>), grid, dim3(CL3_BLOCK), 0, s, a);                             \
-        }                                                                                                                \
-    } while (0)
+template <class F>
+static void with_cl3_instance(int dtype, int op, bool vec, F&& f) {
+    with_src_dtype(dtype, [&](auto ld) { with_reduction(op, [&](auto opk) { with_bool(vec, [&](auto v) { f(ld, opk, v); }); }); });
+}
 
 void cl3_launch_reduce(const MirrorArgs& a, int dtype, hipStream_t s) {
     const long long plane = (long long)a.D * a.H * a.W;
     const dim3 grid = cl3_grid(plane, a.B);
     const bool vec = cl3_vec_ok(dtype, a.C, a.src, a.view_stride, 0);
-    const bool nonlinear = a.op >= PTB_RED_GMEAN;
-    PTB_CL3_LAUNCH(cl3_reduce_kernel, dtype, nonlinear, vec, a);
+    with_cl3_instance(dtype, a.op, vec, [&](auto ld, auto opk, auto v) {
+        hipLaunchKernelGGL((cl3_reduce_kernel<ld(), opk(), v()>), grid, dim3(CL3_BLOCK), 0, s, a); });
 }
 
 void cl3_launch_accum(const MirrorAccArgs& a, int dtype, hipStream_t s) {
     const dim3 grid = cl3_grid((long long)a.d * a.h * a.w, 1);
     const bool vec = cl3_vec_ok(dtype, a.C, a.tiles, a.view_stride, a.tile_off);
-    const bool nonlinear = a.op >= PTB_RED_GMEAN;
-    PTB_CL3_LAUNCH(cl3_accum_kernel, dtype, nonlinear, vec, a);
-}
-
-#undef PTB_CL3_LAUNCH
-#undef PTB_CL3_LAUNCH_LD
-
-template <int LD, int MODE, bool VEC>
-static void cl3_launch_gather_kind(const VolArgs& a, const VolTiles& t, int kind, int n_items, hipStream_t s) {
-    const dim3 grid((unsigned)n_items), block(VB_BLOCK);
-    switch (kind) {
-        case PTB_CROP_F32: hipLaunchKernelGGL((cl3_gather_kernel<LD, MODE, VEC, PTB_CROP_F32>), grid, block, 0, s, a, t); break;
-        case PTB_CROP_U8: hipLaunchKernelGGL((cl3_gather_kernel<LD, MODE, VEC, PTB_CROP_U8>), grid, block, 0, s, a, t); break;
-        case PTB_CROP_ARGMAX_U8: hipLaunchKernelGGL((cl3_gather_kernel<LD, MODE, VEC, PTB_CROP_ARGMAX_U8>), grid, block, 0, s, a, t); break;
-        case PTB_CROP_ARGMAX_I64: hipLaunchKernelGGL((cl3_gather_kernel<LD, MODE, VEC, PTB_CROP_ARGMAX_I64>), grid, block, 0, s, a, t); break;
-        case PTB_CROP_F16: hipLaunchKernelGGL((cl3_gather_kernel<LD, MODE, VEC, PTB_CROP_F16>), grid, block, 0, s, a, t); break;
-        default: hipLaunchKernelGGL((cl3_gather_kernel<LD, MODE, VEC, PTB_CROP_BF16>), grid, block, 0, s, a, t); break;
-    }
-}
-
-template <int LD>
-static void cl3_launch_gather_ld(const VolArgs& a, const VolTiles& t, int mode, bool vec, int kind, int n_items, hipStream_t s) {
-    if (mode == 0) {
-        if (vec) cl3_launch_gather_kind<LD, 0, true>(a, t, kind, n_items, s);
-        else cl3_launch_gather_kind<LD, 0, false>(a, t, kind, n_items, s);
-    } else if (mode == 1) {
-        if (vec) cl3_launch_gather_kind<LD, 1, true>(a, t, kind, n_items, s);
-        else cl3_launch_gather_kind<LD, 1, false>(a, t, kind, n_items, s);
-    } else {
-        if (vec) cl3_launch_gather_kind<LD, 2, true>(a, t, kind, n_items, s);
-        else cl3_launch_gather_kind<LD, 2, false>(a, t, kind, n_items, s);
-    }
+    with_cl3_instance(dtype, a.op, vec, [&](auto ld, auto opk, auto v) {
+        hipLaunchKernelGGL((cl3_accum_kernel<ld(), opk(), v()>), grid, dim3(CL3_BLOCK), 0, s, a); });
 }
 
 void cl3_launch_gather(const VolArgs& a, const VolTiles& t, int n_tiles, int dtype, int mode, int kind, int n_items, hipStream_t s) {
     bool vec = true;
     for (int k = 0; k < n_tiles; ++k) vec = vec && cl3_vec_ok(dtype, a.C, t.src[k], t.vs[k], 0);
-    switch (dtype) {
-        case PTB_F32: cl3_launch_gather_ld<1>(a, t, mode, vec, kind, n_items, s); break;
-        case PTB_F16: cl3_launch_gather_ld<2>(a, t, mode, vec, kind, n_items, s); break;
-        default: cl3_launch_gather_ld<3>(a, t, mode, vec, kind, n_items, s); break;
-    }
+    const dim3 grid((unsigned)n_items), block(VB_BLOCK);
+    with_src_dtype(dtype, [&](auto ld) { with_value<0, 1, 2>(mode, [&](auto m) { with_bool(vec, [&](auto v) {
+        with_crop_kind(kind, [&](auto k) {
+            hipLaunchKernelGGL((cl3_gather_kernel<ld(), m(), v(), k()>), grid, block, 0, s, a, t); }); }); }); });
 }
 
 }  // namespace ptb

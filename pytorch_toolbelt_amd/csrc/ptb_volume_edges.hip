@@ -14,6 +14,7 @@
 // H-flip changes the destination row, a W-flip mirrors the column chunk and writes each lane's LDS run reversed.  The views are a
 // workgroup-uniform kernel argument, not a template parameter.  The plain split keeps its own kernel: one identity view through the
 // views kernel measured 0.7-1.5 % slower than the kernel below, with the same inner store loop.
+#include "ptb_dispatch.h"
 #include "ptb_view_device.h"
 
 namespace ptb {
@@ -217,8 +218,8 @@ __global__ __launch_bounds__(256) void volume_split_views_kernel(const VolSplitA
     }
 }
 
-template <int IN, int OUT>
-int launch_split(VolSplitArgs& g, const int64_t* zs, const int64_t* ys, const int64_t* xs, int B, bool vec, hipStream_t s) {
+static int launch_split(int in_dtype, int out_dtype, VolSplitArgs& g, const int64_t* zs, const int64_t* ys, const int64_t* xs, int B, bool vec,
+                        hipStream_t s) {
     g.nb = B;
     const bool plain = g.nviews == 1 && g.masks == 0;  // ptb_volume_split: its own kernel, the views kernel otherwise
     for (int b0 = 0; b0 < B; b0 += VSPLIT_GROUP) {
@@ -227,23 +228,14 @@ int launch_split(VolSplitArgs& g, const int64_t* zs, const int64_t* ys, const in
         for (int t = 0; t < n; ++t) { g.tz[t] = (int)zs[b0 + t]; g.ty[t] = (int)ys[b0 + t]; g.tx[t] = (int)xs[b0 + t]; }
         const long long blocks = (long long)n * g.ncr * g.ncx;
         if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
-        if (plain) {
-            if (vec) hipLaunchKernelGGL((volume_split_kernel<IN, OUT, true>), dim3((unsigned)blocks), dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((volume_split_kernel<IN, OUT, false>), dim3((unsigned)blocks), dim3(256), 0, s, g);
-        } else {
-            if (vec) hipLaunchKernelGGL((volume_split_views_kernel<IN, OUT, true>), dim3((unsigned)blocks), dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((volume_split_views_kernel<IN, OUT, false>), dim3((unsigned)blocks), dim3(256), 0, s, g);
-        }
+        with_value<PTB_F32, PTB_F16, PTB_BF16, PTB_U8, PTB_I16, PTB_U16>(in_dtype, [&](auto in) {
+            with_value<PTB_F32, PTB_F16, PTB_BF16>(out_dtype, [&](auto out) { with_bool(vec, [&](auto v) {
+                if (plain) hipLaunchKernelGGL((volume_split_kernel<in(), out(), v()>), dim3((unsigned)blocks), dim3(256), 0, s, g);
+                else hipLaunchKernelGGL((volume_split_views_kernel<in(), out(), v()>), dim3((unsigned)blocks), dim3(256), 0, s, g);
+            }); }); });
         if (int rc = check_launch()) return rc;
     }
     return PTB_OK;
-}
-
-template <int IN>
-int launch_split_in(int out_dtype, VolSplitArgs& g, const int64_t* zs, const int64_t* ys, const int64_t* xs, int B, bool vec, hipStream_t s) {
-    if (out_dtype == PTB_F32) return launch_split<IN, PTB_F32>(g, zs, ys, xs, B, vec, s);
-    if (out_dtype == PTB_F16) return launch_split<IN, PTB_F16>(g, zs, ys, xs, B, vec, s);
-    return launch_split<IN, PTB_BF16>(g, zs, ys, xs, B, vec, s);
 }
 
 // ------------------------------------------------------------------------------------------------ accumulate
@@ -344,14 +336,7 @@ extern "C" int ptb_volume_split_mirror(const void* volume, int in_dtype, int D, 
     g.ncx = (w + g.XW - 1) / g.XW;
     g.ncr = (int)((rows + g.R - 1) / g.R);
     hipStream_t s = (hipStream_t)stream;
-    switch (in_dtype) {
-        case PTB_F32: return launch_split_in<PTB_F32>(out_dtype, g, zs, ys, xs, B, vec, s);
-        case PTB_F16: return launch_split_in<PTB_F16>(out_dtype, g, zs, ys, xs, B, vec, s);
-        case PTB_BF16: return launch_split_in<PTB_BF16>(out_dtype, g, zs, ys, xs, B, vec, s);
-        case PTB_U8: return launch_split_in<PTB_U8>(out_dtype, g, zs, ys, xs, B, vec, s);
-        case PTB_I16: return launch_split_in<PTB_I16>(out_dtype, g, zs, ys, xs, B, vec, s);
-        default: return launch_split_in<PTB_U16>(out_dtype, g, zs, ys, xs, B, vec, s);
-    }
+    return launch_split(in_dtype, out_dtype, g, zs, ys, xs, B, vec, s);
 }
 
 // ptb_volume_split keeps its own first checks, in their order, and is the split with the single identity view
@@ -385,8 +370,7 @@ extern "C" int ptb_volume_accumulate(float* volume, float* norm, const float* we
         const long long items = (long long)C * d * h * (vec ? w / 4 : w);
         const long long want = (items + 255) / 256;
         const dim3 grid((unsigned)(want < 16384 ? want : 16384)), block(256);
-        if (vec) hipLaunchKernelGGL(ptb::volume_accumulate_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(ptb::volume_accumulate_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+        with_bool(vec, [&](auto v) { hipLaunchKernelGGL(ptb::volume_accumulate_kernel<v()>, grid, block, 0, (hipStream_t)stream, a); });
         if (int rc = ptb::check_launch()) return rc;
     }
     return PTB_OK;

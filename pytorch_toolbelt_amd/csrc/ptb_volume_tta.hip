@@ -11,6 +11,7 @@
 // (one x per lane) instances.  The split with views (ptb_volume_split_mirror) extends the split kernel of ptb_volume_edges.hip.
 #include <type_traits>
 
+#include "ptb_dispatch.h"
 #include "ptb_mirror_device.h"
 #include "ptb_volume_device.h"
 
@@ -155,29 +156,11 @@ static dim3 plane_grid(long long units, long long planes) {
     return dim3((unsigned)(gx < MIRROR_GRID_X ? gx : MIRROR_GRID_X), (unsigned)(planes < 65535 ? planes : 65535));
 }
 
-template <int LD, int OPK>
-static int launch_reduce_ld(const MirrorArgs& a, bool vec, hipStream_t s) {
-    const int pix = vec ? 4 : 1;
-    const dim3 grid = plane_grid((long long)a.D * a.H * (a.W / pix), (long long)a.B * a.C);
-    if (vec) hipLaunchKernelGGL((volume_mirror_reduce_kernel<LD, OPK, 4>), grid, dim3(MIRROR_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((volume_mirror_reduce_kernel<LD, OPK, 1>), grid, dim3(MIRROR_BLOCK), 0, s, a);
-    return check_launch();
-}
-
-template <int LD, int OPK>
-static int launch_accumulate_ld(MirrorAccArgs& a, const int64_t* zs, const int64_t* ys, const int64_t* xs, int B, bool base_vec,
-                                hipStream_t s) {
-    const long long tile_elems = (long long)a.C * a.d * a.h * a.w;
-    for (int b = 0; b < B; ++b) {
-        a.tile_off = (long long)b * tile_elems;
-        a.z0 = (int)zs[b]; a.y0 = (int)ys[b]; a.x0 = (int)xs[b];
-        const bool vec = base_vec && a.x0 % 4 == 0;
-        const dim3 grid = plane_grid((long long)a.d * a.h * (vec ? a.w / 4 : a.w), a.C);
-        if (vec) hipLaunchKernelGGL((volume_mirror_accumulate_kernel<LD, OPK, 4>), grid, dim3(MIRROR_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL((volume_mirror_accumulate_kernel<LD, OPK, 1>), grid, dim3(MIRROR_BLOCK), 0, s, a);
-        if (int rc = check_launch()) return rc;
-    }
-    return PTB_OK;
+// source dtype x (linear | non-linear reduction) x (4 voxels | 1 voxel per lane)
+template <class F>
+static void with_mirror_instance(int dtype, int op, bool vec, F&& f) {
+    with_src_dtype(dtype, [&](auto ld) { with_reduction(op, [&](auto opk) { with_bool(vec, [&](auto v) {
+        f(ld, opk, int_c<(v() ? 4 : 1)>{}); }); }); });
 }
 
 }  // namespace ptb
@@ -200,13 +183,8 @@ extern "C" int ptb_volume_mirror(const void* src, int dtype, void* dst, int nvie
     const bool vec = !g_force_scalar && W % 4 == 0 && aligned_run(src, dtype) && aligned_run(dst, dtype);
     const dim3 grid = plane_grid((long long)D * H * (vec ? W / 4 : W), (long long)nviews * B * C);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == PTB_F32) {
-        if (vec) hipLaunchKernelGGL((volume_mirror_kernel<4, 4>), grid, dim3(MIRROR_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL((volume_mirror_kernel<4, 1>), grid, dim3(MIRROR_BLOCK), 0, s, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((volume_mirror_kernel<2, 4>), grid, dim3(MIRROR_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL((volume_mirror_kernel<2, 1>), grid, dim3(MIRROR_BLOCK), 0, s, a);
-    }
+    with_bool(dtype == PTB_F32, [&](auto f32) { with_bool(vec, [&](auto v) {   // element bytes x elements per lane
+        hipLaunchKernelGGL((volume_mirror_kernel<(f32() ? 4 : 2), (v() ? 4 : 1)>), grid, dim3(MIRROR_BLOCK), 0, s, a); }); });
     return check_launch();
 }
 
@@ -233,12 +211,10 @@ extern "C" int ptb_volume_mirror_reduce(const void* src, int dtype, void* dst, i
         return check_launch();
     }
     const bool vec = !g_force_scalar && W % 4 == 0 && aligned_run(src, dtype) && aligned_run(dst, dtype);
-    const bool nonlinear = reduction >= PTB_RED_GMEAN;
-    switch (dtype) {
-        case PTB_F32: return nonlinear ? launch_reduce_ld<1, 1>(a, vec, s) : launch_reduce_ld<1, 0>(a, vec, s);
-        case PTB_F16: return nonlinear ? launch_reduce_ld<2, 1>(a, vec, s) : launch_reduce_ld<2, 0>(a, vec, s);
-        default: return nonlinear ? launch_reduce_ld<3, 1>(a, vec, s) : launch_reduce_ld<3, 0>(a, vec, s);
-    }
+    const dim3 grid = plane_grid((long long)D * H * (vec ? W / 4 : W), (long long)B * C);
+    with_mirror_instance(dtype, reduction, vec, [&](auto ld, auto opk, auto pix) {
+        hipLaunchKernelGGL((volume_mirror_reduce_kernel<ld(), opk(), pix()>), grid, dim3(MIRROR_BLOCK), 0, s, a); });
+    return check_launch();
 }
 
 extern "C" int ptb_volume_mirror_accumulate(float* volume, float* norm, const float* weight, const void* tiles, int in_dtype, int nviews,
@@ -273,14 +249,16 @@ extern "C" int ptb_volume_mirror_accumulate(float* volume, float* norm, const fl
     }
     const bool base_vec = !g_force_scalar && w % 4 == 0 && W % 4 == 0 && aligned16(volume) && aligned16(norm) && aligned16(weight) &&
                           aligned_run(tiles, in_dtype);
-    const bool nonlinear = reduction >= PTB_RED_GMEAN;
     hipStream_t s = (hipStream_t)stream;
-    switch (in_dtype) {
-        case PTB_F32:
-            return nonlinear ? launch_accumulate_ld<1, 1>(a, zs, ys, xs, B, base_vec, s) : launch_accumulate_ld<1, 0>(a, zs, ys, xs, B, base_vec, s);
-        case PTB_F16:
-            return nonlinear ? launch_accumulate_ld<2, 1>(a, zs, ys, xs, B, base_vec, s) : launch_accumulate_ld<2, 0>(a, zs, ys, xs, B, base_vec, s);
-        default:
-            return nonlinear ? launch_accumulate_ld<3, 1>(a, zs, ys, xs, B, base_vec, s) : launch_accumulate_ld<3, 0>(a, zs, ys, xs, B, base_vec, s);
+    const long long tile_elems = (long long)C * d * h * w;
+    for (int b = 0; b < B; ++b) {
+        a.tile_off = (long long)b * tile_elems;
+        a.z0 = (int)zs[b]; a.y0 = (int)ys[b]; a.x0 = (int)xs[b];
+        const bool vec = base_vec && a.x0 % 4 == 0;
+        const dim3 grid = plane_grid((long long)d * h * (vec ? w / 4 : w), C);
+        with_mirror_instance(in_dtype, reduction, vec, [&](auto ld, auto opk, auto pix) {
+            hipLaunchKernelGGL((volume_mirror_accumulate_kernel<ld(), opk(), pix()>), grid, dim3(MIRROR_BLOCK), 0, s, a); });
+        if (int rc = check_launch()) return rc;
     }
+    return PTB_OK;
 }
