@@ -375,6 +375,20 @@ int ptb_volume_split(const void* volume, int in_dtype, int D, int H, int W, int 
 int ptb_volume_merge_crop(const float* volume, const float* norm, int C, int D, int H, int W, int z0, int y0, int x0, int OD, int OH,
                           int OW, int layout, int kind, void* out, ptb_stream_t stream);
 
+/* ---- Trilinear resampling of a volume before the 3-D loop (ptb_volume_resample.hip) ----
+ * F.interpolate(mode="trilinear", align_corners): per axis the float32 scale is n_in / n_out, or with align_corners
+ * (n_in - 1) / (n_out - 1) (0 when n_out == 1); src = max(scale * (dst + 0.5f) - 0.5f, 0) or scale * dst; i0 = min((int)src, n_in - 1),
+ * i1 = i0 + (i0 < n_in - 1), lambda = src - i0 -- aten's area_pixel_compute_source_index in float32, the taps of ptb_resize_bilinear.
+ * The blend runs x, then y, then z: a * (1 - lambda) + b * lambda each, products and sums rounded separately.
+ *
+ * ptb_volume_resize_trilinear == .float() -> trilinear resize -> .to(out_dtype) of a channel-last volume: volume DEVICE [D, H, W, C]
+ * contiguous of in_dtype (PTB_F32, PTB_F16, PTB_BF16, PTB_U8, PTB_I16, PTB_U16 -- what ptb_volume_split reads); out DEVICE
+ * [RD, RH, RW, C] of out_dtype (PTB_F32, PTB_F16, PTB_BF16).  PTB_EUNSUPPORTED: C > 16; a row of more than 2^31 - 1 elements; a call whose
+ * source window per 64 x 4 x 4 output brick exceeds 2560 elements (down-sampling by about 4 and more) on a volume of more than 2^32 - 1
+ * elements -- those launches index the whole volume with 32-bit offsets. */
+int ptb_volume_resize_trilinear(const void* volume, int in_dtype, int D, int H, int W, int C, int RD, int RH, int RW, int align_corners,
+                                int out_dtype, void* out, ptb_stream_t stream);
+
 /* ---- Mirror test-time augmentation of 3-D tiles (inference/tta_3d.py; no reference counterpart: the spec is the torch expression
  * cat([x.flip(dims_v)]) / stack([y_v.flip(dims_v)]).reduce(0)) -------------------------------------------------------------------
  * A view is a 3-bit mask: bit 0 flips W, bit 1 flips H, bit 2 flips D (view m of [B, C, D, H, W] = x.flip(dims) with dims holding 2

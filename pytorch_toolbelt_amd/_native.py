@@ -151,6 +151,7 @@ SIGNATURES = {
     "ptb_volume_split": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _i64p, _i64p, _i64p, _c_int, _c_int, _c_int, _c_int, _fp, _fp, _c_f,
                                   _c_int, _vp, _vp]),
     "ptb_volume_merge_crop": (_c_int, [_vp, _vp] + [_c_int] * 12 + [_vp, _vp]),
+    "ptb_volume_resize_trilinear": (_c_int, [_vp] + [_c_int] * 10 + [_vp, _vp]),
     "ptb_volume_mirror": (_c_int, [_vp, _c_int, _vp, _c_int, _ip] + [_c_int] * 6 + [_vp]),
     "ptb_volume_mirror_reduce": (_c_int, [_vp, _c_int, _vp, _c_int, _ip] + [_c_int] * 6 + [_vp]),
     "ptb_volume_mirror_accumulate": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _ip, _c_int, _i64p, _i64p, _i64p] + [_c_int] * 8 + [_vp]),

@@ -5,28 +5,12 @@
 #include <algorithm>
 
 #include "ptb_dispatch.h"
+#include "ptb_taps_device.h"
 #include "ptb_view_device.h"
 
 namespace ptb {
 
-struct Taps { int i0, i1; float l0, l1; };
-
-template <int ALIGN = -1>   // -1: run-time align_corners; 0 / 1: compile-time (no branch in the unrolled tap code)
-__device__ __forceinline__ Taps taps(int dst, float scale, int n_in, bool align_corners) {
-    float src;
-    if (ALIGN < 0 ? align_corners : (ALIGN == 1)) {
-        src = scale * (float)dst;
-    } else {
-        src = scale * ((float)dst + 0.5f) - 0.5f;
-        src = src < 0.f ? 0.f : src;
-    }
-    Taps t;
-    t.i0 = min((int)src, n_in - 1);
-    t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
-    t.l1 = fminf(fmaxf(src - (float)t.i0, 0.f), 1.f);
-    t.l0 = 1.f - t.l1;
-    return t;
-}
+// (Taps / taps(): ptb_taps_device.h, shared with the 3-D resize kernels)
 
 // one thread = 4 consecutive output columns of one output row (16 B store per lane)
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, int planes,

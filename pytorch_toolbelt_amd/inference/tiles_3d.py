@@ -19,7 +19,7 @@ from . import _host
 from ._merge_modes import HeldBatches
 from .tta_3d import flip_view, mirror_views
 
-__all__ = ["VolumeSlicer", "VolumeMerger"]
+__all__ = ["VolumeSlicer", "VolumeMerger", "resample_volume"]
 
 
 def _triple(v, what):
@@ -176,6 +176,55 @@ class VolumeSlicer:
 
     def _mean(self, volume_size):
         return np.ones(volume_size, dtype=np.float32)
+
+
+def _resample_size(size, what):
+    """``size`` of a resampling call -> three positive ints."""
+    try:
+        triple = tuple(size)
+        ok = len(triple) == 3 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 1 for v in triple)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: size must be three positive ints (depth, height, width), got {size!r}")
+    return tuple(int(v) for v in triple)
+
+
+def resample_volume(volume: torch.Tensor, size, align_corners: bool = False, dtype=torch.float32) -> torch.Tensor:
+    """Trilinear resampling of a ``[D, H, W]`` or ``[D, H, W, C]`` volume to ``size = (D', H', W')`` -- to the spacing the model was trained
+    at, before ``VolumeSlicer.split_device`` tiles it.
+
+    Equals ``F.interpolate(volume.float() moved to [1, C, D, H, W], size=size, mode="trilinear", align_corners=align_corners)`` moved back
+    to channels last, ``.to(dtype)``.  ``volume``: uint8, int16, uint16, float16, bfloat16 or float32 (what ``split_device`` takes), C <= 16;
+    ``dtype``: torch.float32, torch.float16 or torch.bfloat16 (round to nearest even).  A CUDA volume is one HIP launch that widens on load
+    and writes the result once (no float32 copy of the input); a CPU volume evaluates the torch expression.  Inference only.  Strong
+    down-sampling (a factor of about 4 and more) of a CUDA volume of more than 2^32 - 1 elements raises ``NotImplementedError``."""
+    if volume.dtype not in N.VOLUME_DTYPE_CODES:
+        raise NotImplementedError(f"resample_volume takes a uint8, int16, uint16, float16, bfloat16 or float32 volume, got {volume.dtype}")
+    if dtype not in N.DTYPE_CODES:
+        raise NotImplementedError(f"resample_volume writes float32, float16 or bfloat16, not {dtype}")
+    if volume.dim() not in (3, 4) or volume.numel() == 0:
+        raise ValueError(f"resample_volume takes a non-empty [D, H, W] or [D, H, W, C] volume, got shape {tuple(volume.shape)}")
+    size = _resample_size(size, "resample_volume")
+    channels = 1 if volume.dim() == 3 else int(volume.shape[3])
+    if channels > 16:
+        raise NotImplementedError(f"resample_volume takes at most 16 channels, got {channels}")
+    if not volume.is_cuda:
+        x = volume.float()
+        x = x[None, None] if volume.dim() == 3 else x.permute(3, 0, 1, 2)[None]
+        y = torch.nn.functional.interpolate(x, size=size, mode="trilinear", align_corners=align_corners)[0]
+        return (y[0] if volume.dim() == 3 else y.permute(1, 2, 3, 0)).to(dtype).contiguous()
+    if volume.requires_grad:
+        raise RuntimeError("resample_volume: the volume requires grad; the HIP resampling is inference-only (use torch.no_grad() / .detach())")
+    volume = volume.contiguous()
+    out = torch.empty(size + tuple(volume.shape[3:]), device=volume.device, dtype=dtype)
+    D, H, W = (int(s) for s in volume.shape[:3])
+    with N.on_device(volume.device):
+        rc = N.load().ptb_volume_resize_trilinear(volume.data_ptr(), N.VOLUME_DTYPE_CODES[volume.dtype], D, H, W, channels, *size,
+                                                  1 if align_corners else 0, N.DTYPE_CODES[dtype], out.data_ptr(), N.stream_ptr(volume.device))
+    N.bump()
+    N.check(rc, "resample_volume")
+    return out
 
 
 def _crop_kind(dtype, argmax):
