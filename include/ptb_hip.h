@@ -461,6 +461,28 @@ int ptb_volume_plan_submit(ptb_volume_plan* plan, int pos, int B, const void* ba
                            ptb_stream_t stream);
 void ptb_volume_plan_destroy(ptb_volume_plan* plan);
 
+/* ---- Activations inside the 3-D mirror de-augmentation and tile merges (ptb_volume_activation.hip) --------------------------------
+ * A(y) = sigmoid(y * temperature) | softmax over the channels of (y * temperature), evaluated in fp32 on the widened logits of every
+ * view of every tile, in registers (ApplySigmoidTo / ApplySoftmaxTo of the reference).  Each entry point takes the arguments of its
+ * namesake plus `activation` (PTB_ACT_*) and a finite `temperature`, and means the namesake on the float32 tensor A(y): z = x * t
+ * rounded; sigmoid 1 / (1 + exp(-z)); softmax exp(z - max_c z) summed in channel order, times the reciprocal of the sum; then
+ * red_pre, the view sum in view order, red_post, tile * weight in integration order.  The reduced value is NOT rounded to a half
+ * source type (the source counts as fp32), PTB_ACT_NONE included.  PTB_SRC_CHANNELS_LAST keeps its meaning.  A bad activation code or a
+ * non-finite temperature -> PTB_EINVAL; PTB_ACT_SOFTMAX with C > 16 -> PTB_EUNSUPPORTED; both before anything touches the device.
+ * ptb_volume_mirror_reduce_act writes dense fp32 [B, C, D, H, W].  ptb_volume_plan_submit_act: activation and temperature belong to
+ * the image's configuration, as does the entry point itself (a change -> PTB_EUNSUPPORTED, nothing recorded or launched). */
+#define PTB_ACT_NONE 0
+#define PTB_ACT_SIGMOID 1
+#define PTB_ACT_SOFTMAX 2
+int ptb_volume_mirror_reduce_act(const void* src, int dtype, float* dst, int nviews, const int* masks, int reduction, int B, int C, int D,
+                                 int H, int W, int activation, float temperature, ptb_stream_t stream);
+int ptb_volume_mirror_accumulate_act(float* volume, float* norm, const float* weight, const void* tiles, int in_dtype, int nviews,
+                                     const int* masks, int reduction, const int64_t* zs, const int64_t* ys, const int64_t* xs, int B, int C,
+                                     int d, int h, int w, int D, int H, int W, int activation, float temperature, ptb_stream_t stream);
+int ptb_volume_plan_submit_act(ptb_volume_plan* plan, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride,
+                               int in_dtype, int nviews, const int* masks, int reduction, const float* weight, void* out, int activation,
+                               float temperature, ptb_stream_t stream);
+
 /* ---- {fliplr,flipud,flips,d2,d4}_image_deaugment (inference/tta.py:287-316,344-365,442-467,503-524) -------------
  * in [V*B, C, H, W] (chunk-major: rows [k*B,(k+1)*B) are view k), views HOST int[V] = inverse transform of each chunk.
  * out [B, C, H, W] = reduce_k view_k(in[k*B + b]).  V <= 8.  Transposing views require H == W. */

@@ -15,6 +15,7 @@
 // are read-once (non-temporal), the window is re-read by every tile (ordinary loads).  Channels run in a loop with running argmax
 // state, so registers do not depend on C.  No LDS, no scratch, no atomics.
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "ptb_crop_device.h"
@@ -279,6 +280,9 @@ struct ptb_volume_plan {
     int pos = 0, groups_done = 0;
     bool configured = false;
     int in_dtype = 0, nviews = 0, masks = 0, reduction = 0;
+    bool act_entry = false;           // the image came in through ptb_volume_plan_submit_act
+    int activation = 0;
+    float temperature = 1.0f;
     const float* weight = nullptr;
     void* out = nullptr;
     std::vector<const void*> tile_src;
@@ -501,9 +505,10 @@ extern "C" int ptb_volume_plan_state(const ptb_volume_plan* p, int* pos, int* la
 
 extern "C" void ptb_volume_plan_destroy(ptb_volume_plan* p) { delete p; }
 
-extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride,
-                                      int in_dtype, int nviews, const int* masks, int reduction, const float* weight, void* out,
-                                      ptb_stream_t stream) {
+// ptb_volume_plan_submit (act_entry = false) and ptb_volume_plan_submit_act (true: the kernels of ptb_volume_activation.hip)
+static int plan_submit(ptb_volume_plan* p, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride, int in_dtype, int nviews,
+                       const int* masks, int reduction, const float* weight, void* out, bool act_entry, int activation, float temperature,
+                       ptb_stream_t stream) {
     if (!p || !batch || !weight || !out || B < 1 || tile_stride < 1) return PTB_EINVAL;
     const int dtype_arg = in_dtype;      // (with PTB_SRC_CHANNELS_LAST: part of the image's configuration)
     const bool src_cl = (in_dtype & PTB_SRC_CHANNELS_LAST) != 0;
@@ -520,12 +525,15 @@ extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const 
         reduction = 0;
         view_stride = 0;
     }
+    if (activation == PTB_ACT_SOFTMAX && p->C > 16) return PTB_EUNSUPPORTED; // the channels of a voxel are resident
     if (!p->dev_items) return PTB_EINVAL;                                   // ptb_volume_plan_upload comes first
     if (pos != p->pos || (long long)pos + B > p->n) return PTB_EUNSUPPORTED;   // off the planned sequence
     if (p->configured && (dtype_arg != p->in_dtype || nviews != p->nviews || packed != p->masks || reduction != p->reduction ||
-                          weight != p->weight || out != p->out))
+                          weight != p->weight || out != p->out || act_entry != p->act_entry || activation != p->activation ||
+                          temperature != p->temperature))
         return PTB_EUNSUPPORTED;                                            // one configuration per image
     p->configured = true;
+    p->act_entry = act_entry; p->activation = activation; p->temperature = temperature;
     p->in_dtype = dtype_arg; p->nviews = nviews; p->masks = packed; p->reduction = reduction; p->weight = weight; p->out = out;
     const size_t es = in_dtype == PTB_F32 ? 4 : 2;
     for (int b = 0; b < B; ++b) {
@@ -542,6 +550,7 @@ extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const 
     a.nv = nviews; a.masks = packed; a.op = reduction;
     a.divisor = reduction == PTB_RED_SUM ? 1.0f : (float)nviews;
     const int mode = nviews == 0 ? 0 : (reduction >= PTB_RED_GMEAN ? 2 : 1);
+    if (act_entry && nviews == 0) { a.nv = 1; a.op = PTB_RED_SUM; }       // plain tiles: the identity view, summed (exact)
     const uintptr_t run_mask = in_dtype == PTB_F32 ? 15u : 7u;            // 4 elements per lane: 16 B of fp32, 8 B of fp16 / bf16
     int launches = 0;
     while (p->groups_done < (int)p->groups.size() && p->groups[p->groups_done].complete < p->pos) {
@@ -555,7 +564,9 @@ extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const 
         }
         a.items = p->dev_items + g.item0;
         hipStream_t s = (hipStream_t)stream;
-        if (src_cl) {   // PTB_SRC_CHANNELS_LAST: the same work-item table, one lane per voxel over all channels
+        if (act_entry) {
+            act_launch_gather(a, t, (int)g.tiles.size(), in_dtype, src_cl, vec, p->kind, g.n_items, activation, temperature, s);
+        } else if (src_cl) {   // PTB_SRC_CHANNELS_LAST: the same work-item table, one lane per voxel over all channels
             cl3_launch_gather(a, t, (int)g.tiles.size(), in_dtype, mode, p->kind, g.n_items, s);
         } else {
             launch_gather(a, t, in_dtype, mode, vec, p->kind, g.n_items, s);
@@ -565,4 +576,19 @@ extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const 
         ++launches;
     }
     return launches;
+}
+
+extern "C" int ptb_volume_plan_submit(ptb_volume_plan* p, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride,
+                                      int in_dtype, int nviews, const int* masks, int reduction, const float* weight, void* out,
+                                      ptb_stream_t stream) {
+    return plan_submit(p, pos, B, batch, tile_stride, view_stride, in_dtype, nviews, masks, reduction, weight, out, false, PTB_ACT_NONE, 1.0f,
+                       stream);
+}
+
+extern "C" int ptb_volume_plan_submit_act(ptb_volume_plan* p, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride,
+                                          int in_dtype, int nviews, const int* masks, int reduction, const float* weight, void* out,
+                                          int activation, float temperature, ptb_stream_t stream) {
+    if (activation < PTB_ACT_NONE || activation > PTB_ACT_SOFTMAX || !std::isfinite(temperature)) return PTB_EINVAL;
+    return plan_submit(p, pos, B, batch, tile_stride, view_stride, in_dtype, nviews, masks, reduction, weight, out, true, activation,
+                       temperature, stream);
 }

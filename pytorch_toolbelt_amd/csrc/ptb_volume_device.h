@@ -83,4 +83,11 @@ void cl3_launch_accum(const MirrorAccArgs& a, int dtype, hipStream_t s);        
 void cl3_launch_gather(const VolArgs& a, const VolTiles& t, int n_tiles, int dtype, int mode, int kind, int n_items,
                        hipStream_t s);                                                     // ptb_volume_plan_submit: one launch group
 
+// ------------------------------------------------------------------------------------------------ activations
+// One launch group of ptb_volume_plan_submit_act: the slab merge over A(tile) (PTB_ACT_*), dense or channels-last sources (`src_cl`).
+// `dense_vec`: the dense criterion of the 4-voxel lanes holds (plan, weight and tile pointers on the 4-voxel grid).  Defined in
+// ptb_volume_activation.hip.
+void act_launch_gather(const VolArgs& a, const VolTiles& t, int n_tiles, int dtype, bool src_cl, bool dense_vec, int kind, int n_items,
+                       int activation, float temperature, hipStream_t s);
+
 }  // namespace ptb

@@ -17,7 +17,7 @@ import torch
 from .. import _native as N
 from . import _host
 from ._merge_modes import HeldBatches
-from .tta_3d import flip_view, mirror_views
+from .tta_3d import _activation_code, _check_softmax_channels, apply_activation, flip_view, mirror_views
 
 __all__ = ["VolumeSlicer", "VolumeMerger", "resample_volume"]
 
@@ -392,7 +392,7 @@ class _DeferredVolume:
         if self._pos == 0:
             self._config = config
         elif config != self._config:
-            raise RuntimeError(f"{what}: dtype / mirror / reduction / layout {config} differ from the image's first batch {self._config}; one configuration "
+            raise RuntimeError(f"{what}: dtype / mirror / reduction / layout / activation {config} differ from the image's first batch {self._config}; one configuration "
                                f"per image in deferred mode -- {_DEFER_HINT}")
 
     def _finished_result(self, what):
@@ -443,7 +443,15 @@ class VolumeMerger(_DeferredVolume):
     ``peak_held_tiles`` (from the plan) is the most tiles held at once -- with z-major crops two z-layers of tiles, plus the batch in
     flight (98 tiles = 3.3 GB for 343 tiles of 4 x 128^3 float32; 8 x that with the 8 float32 views of ``"dhw"``).  No byte budget is
     enforced.  More than 8 tiles over a voxel (a step below half the tile) raises ``NotImplementedError``.  ``reset()`` starts the
-    next volume of the same geometry on the same plan."""
+    next volume of the same geometry on the same plan.
+
+    ``activation=, temperature=`` (keyword-only, on ``integrate_batch``, ``accumulate_single`` and ``integrate_batch_deaugment``, plain and
+    deferred): the call means the same call on ``A(batch) = (batch.float() * temperature).sigmoid()`` / ``.softmax(dim=1)`` -- the
+    reference's ``ApplySigmoidTo`` / ``ApplySoftmaxTo`` -- evaluated inside the merge launch on the logits where they lie
+    (``ptb_volume_activation.hip``; dense or ``channels_last_3d``, float32 / float16 / bfloat16), so no probability tensor is written.  The
+    source then counts as float32: the reduced value of a half-precision batch is not rounded to the batch's dtype.  Softmax serves
+    1 <= C <= 16 (NotImplementedError above; apply ``y.softmax(1)`` yourself), sigmoid any C.  A deferred merger holds the caller's raw
+    logits, and activation and temperature belong to the image's configuration.  ``activation=None`` is the call without the keyword."""
 
     def __new__(cls, volume_shape=None, channels=None, weight=None, device="cpu", *args, **kwargs):
         # like TileMerger: the device the caller names decides -- "cpu" (the reference's default) and float64 accumulators are the
@@ -521,7 +529,7 @@ class VolumeMerger(_DeferredVolume):
         self._pos, self._config, self._groups_done = 0, None, 0
         self._result = torch.empty(self._spec.out_shape(self.channels), device=self.weight.device, dtype=self._spec.out_dtype)
 
-    def _submit(self, batch, rois, views, code, what):
+    def _submit(self, batch, rois, views, code, what, act=N.ACT_NONE, temperature=1.0):
         """Deferred mode: take the batch into custody and launch every slab that is now complete."""
         if not torch.is_tensor(batch) or not batch.is_cuda:
             raise RuntimeError(f"{what}: a deferred merger reads the batches where they lie, on the GPU -- got a host batch; move it to "
@@ -541,7 +549,11 @@ class VolumeMerger(_DeferredVolume):
         # a channels_last_3d model output is held and read where it lies (N.SRC_CHANNELS_LAST); any other strides are copied
         layout = N.volume_layout(batch)
         channels_last = layout == N.LAYOUT_CHANNELS_LAST
-        self._same_config((batch.dtype, tuple(views), code, "channels_last_3d" if channels_last else "dense"), what)
+        config = (batch.dtype, tuple(views), code, "channels_last_3d" if channels_last else "dense")
+        if act != N.ACT_NONE:
+            _check_softmax_channels(act, self.channels, what)
+            config += (act, temperature)
+        self._same_config(config, what)
         if B == 0:
             return
         if layout == N.LAYOUT_OTHER:
@@ -553,10 +565,13 @@ class VolumeMerger(_DeferredVolume):
         span = self._held.admit(batch, due)
         tile_elems = self.channels * d * h * w
         dev = self.weight.device
+        args = (plan.handle, pos, B, batch.data_ptr(), tile_elems, B * tile_elems, dtype, len(views), N.int_array(views) if views else None, code,
+                self.weight.data_ptr(), self._result.data_ptr())
         with N.on_device(dev):
-            rc = N.load().ptb_volume_plan_submit(plan.handle, pos, B, batch.data_ptr(), tile_elems, B * tile_elems, dtype, len(views),
-                                                 N.int_array(views) if views else None, code, self.weight.data_ptr(), self._result.data_ptr(),
-                                                 N.stream_ptr(dev))
+            if act == N.ACT_NONE:
+                rc = N.load().ptb_volume_plan_submit(*args, N.stream_ptr(dev))
+            else:
+                rc = N.load().ptb_volume_plan_submit_act(*args, act, temperature, N.stream_ptr(dev))
         N.bump()
         if rc < 0:
             N.check(rc, what)
@@ -588,18 +603,29 @@ class VolumeMerger(_DeferredVolume):
         N.bump()
         N.check(rc, "VolumeMerger.integrate_batch")
 
-    def accumulate_single(self, tile: torch.Tensor, roi):
-        """Accumulate one ``[C, d, h, w]`` prediction at ``roi`` (3 slices)."""
+    def accumulate_single(self, tile: torch.Tensor, roi, *, activation=None, temperature=1.0):
+        """Accumulate one ``[C, d, h, w]`` prediction at ``roi`` (3 slices); ``activation`` / ``temperature``: see the class."""
+        if _activation_code(activation, temperature, "VolumeMerger.accumulate_single") != N.ACT_NONE:
+            return self.integrate_batch(tile.unsqueeze(0), [roi], activation=activation, temperature=temperature)
         if self._defer:
             return self.integrate_batch(tile.unsqueeze(0), [roi])
         if self._channels_last(tile.unsqueeze(0)):
             return self.integrate_batch(tile.unsqueeze(0), [roi])
         self._accumulate(tile.detach().to(device=self.volume.device, dtype=torch.float32).unsqueeze(0).contiguous(), [roi])
 
-    def integrate_batch(self, batch: torch.Tensor, rois):
-        """Accumulate ``[B, C, d, h, w]`` predictions at ``rois[b]`` (3 slices each)."""
+    def integrate_batch(self, batch: torch.Tensor, rois, *, activation=None, temperature=1.0):
+        """Accumulate ``[B, C, d, h, w]`` predictions at ``rois[b]`` (3 slices each); ``activation`` / ``temperature``: see the class (a host
+        batch is uploaded as without them, in its own dtype, and then activated in the launch)."""
         if len(batch) != len(rois):
             raise ValueError("Number of images in batch does not correspond to number of coordinates")
+        act = _activation_code(activation, temperature, "VolumeMerger.integrate_batch")
+        if act != N.ACT_NONE:
+            if self._defer:
+                return self._submit(batch, rois, (), 0, "VolumeMerger.integrate_batch", act, float(temperature))
+            batch = batch.detach().to(device=self.volume.device)
+            if batch.dtype not in N.DTYPE_CODES:
+                batch = batch.float()
+            return self._mirror_accumulate(batch, rois, (0,), N.RED_SUM, "VolumeMerger.integrate_batch", act, float(temperature))
         if self._defer:
             return self._submit(batch, rois, (), 0, "VolumeMerger.integrate_batch")
         if self._channels_last(batch):       # read where it lies: the identity view summed (exact), so no float32 / dense copy exists
@@ -611,13 +637,15 @@ class VolumeMerger(_DeferredVolume):
         return (torch.is_tensor(batch) and batch.is_cuda and batch.device == self.volume.device and batch.dtype in N.DTYPE_CODES
                 and N.volume_layout(batch) == N.LAYOUT_CHANNELS_LAST)
 
-    def _mirror_accumulate(self, batch, rois, views, code, what):
-        """``ptb_volume_mirror_accumulate`` on a dense or channels_last_3d ``[V*B, C, d, h, w]`` batch of the accumulators' device."""
+    def _mirror_accumulate(self, batch, rois, views, code, what, act=N.ACT_NONE, temperature=1.0):
+        """``ptb_volume_mirror_accumulate`` (with an activation: ``ptb_volume_mirror_accumulate_act``) on a dense or channels_last_3d
+        ``[V*B, C, d, h, w]`` batch of the accumulators' device."""
         self._check_accumulators("VolumeMerger")
         dtype = N.DTYPE_CODES[batch.dtype]
         d, h, w = (int(s) for s in self.weight.shape[1:])
         if tuple(batch.shape[1:]) != (self.channels, d, h, w):
             raise RuntimeError(f"tile batch of shape {tuple(batch.shape)} does not match [{'V*' if len(views) > 1 else ''}B, {self.channels}, {d}, {h}, {w}]")
+        _check_softmax_channels(act, self.channels, what)
         if N.volume_layout(batch) == N.LAYOUT_CHANNELS_LAST:
             dtype |= N.SRC_CHANNELS_LAST
         else:
@@ -626,16 +654,20 @@ class VolumeMerger(_DeferredVolume):
         D, H, W = (int(s) for s in self.volume.shape[1:])
         lib = N.load()
         dev = self.volume.device
+        args = (self.volume.data_ptr(), self.norm_mask.data_ptr(), self.weight.data_ptr(), batch.data_ptr(), dtype, len(views), N.int_array(views),
+                code, starts[0].ctypes.data_as(N._i64p), starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), len(rois),
+                self.channels, d, h, w, D, H, W)
         with N.on_device(dev):
-            rc = lib.ptb_volume_mirror_accumulate(self.volume.data_ptr(), self.norm_mask.data_ptr(), self.weight.data_ptr(), batch.data_ptr(),
-                                                  dtype, len(views), N.int_array(views), code, starts[0].ctypes.data_as(N._i64p),
-                                                  starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), len(rois),
-                                                  self.channels, d, h, w, D, H, W, N.stream_ptr(dev))
+            if act == N.ACT_NONE:
+                rc = lib.ptb_volume_mirror_accumulate(*args, N.stream_ptr(dev))
+            else:
+                rc = lib.ptb_volume_mirror_accumulate_act(*args, act, temperature, N.stream_ptr(dev))
         N.bump()
         N.check(rc, what)
 
-    def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean"):
-        """Fused ``integrate_batch(mirror_volume_deaugment(batch, mirror, reduction), rois)``, bit for bit.
+    def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean", *, activation=None, temperature=1.0):
+        """Fused ``integrate_batch(mirror_volume_deaugment(batch, mirror, reduction), rois)``, bit for bit -- with ``activation`` /
+        ``temperature`` (see the class) of ``integrate_batch(mirror_volume_deaugment(batch, mirror, reduction, activation=, temperature=), rois)``.
 
         ``batch``: the model output for the ``mirror_volume_augment``-ed tiles, ``[V*B, C, d, h, w]`` chunk-major, float32, float16 or
         bfloat16, on the merger's CUDA device (read as it is, no float32 copy; unlike ``integrate_batch``, a host batch is refused
@@ -650,8 +682,10 @@ class VolumeMerger(_DeferredVolume):
         code = _reduction_code(reduction)
         if code is None:
             raise ValueError(f"reduction={reduction!r} cannot be fused into the tile merge")
+        act = _activation_code(activation, temperature, "VolumeMerger.integrate_batch_deaugment")
+        temperature = float(temperature)
         if self._defer:
-            return self._submit(batch, rois, tuple(views), code, "VolumeMerger.integrate_batch_deaugment")
+            return self._submit(batch, rois, tuple(views), code, "VolumeMerger.integrate_batch_deaugment", act, temperature)
         self._check_accumulators("VolumeMerger")
         dtype = N.DTYPE_CODES.get(batch.dtype)
         if dtype is None:
@@ -662,7 +696,7 @@ class VolumeMerger(_DeferredVolume):
             raise RuntimeError(f"tile batch of shape {tuple(batch.shape)} does not match [V*B, {self.channels}, {d}, {h}, {w}]")
         if batch.device != self.volume.device:
             raise ValueError(f"integrate_batch_deaugment: batch is on {batch.device}, the accumulators on {self.volume.device}")
-        self._mirror_accumulate(batch.detach(), rois, views, code, "VolumeMerger.integrate_batch_deaugment")
+        self._mirror_accumulate(batch.detach(), rois, views, code, "VolumeMerger.integrate_batch_deaugment", act, temperature)
 
     def merge(self) -> torch.Tensor:
         """``volume / norm_mask`` as a new tensor (no eps clamp: never-covered voxels are NaN)."""
@@ -747,6 +781,12 @@ class HostBackedVolumeMerger(VolumeMerger):
             spec = self._spec
             self._result = self._host_merge() if spec.default else self._host_merge_crop(spec.window, spec.layout, spec.dtype, spec.argmax)
 
+    @staticmethod
+    def _act_config(activation, temperature, what):
+        """The activation's part of a deferred image's configuration: () without one."""
+        act = _activation_code(activation, temperature, what)
+        return () if act == N.ACT_NONE else (act, float(temperature))
+
     def _blend(self, tiles, rois):
         d, h, w = (int(s) for s in self.weight.shape[1:])
         if tuple(tiles.shape[1:]) != (self.channels, d, h, w):
@@ -761,21 +801,24 @@ class HostBackedVolumeMerger(VolumeMerger):
             self._volume[roi] += tile * self.weight
             self._norm_mask[roi] += self.weight
 
-    def accumulate_single(self, tile: torch.Tensor, roi):
-        if self._defer:
-            return self.integrate_batch(tile.unsqueeze(0), [roi])
+    def accumulate_single(self, tile: torch.Tensor, roi, *, activation=None, temperature=1.0):
+        if self._defer or _activation_code(activation, temperature, "VolumeMerger.accumulate_single") != N.ACT_NONE:
+            return self.integrate_batch(tile.unsqueeze(0), [roi], activation=activation, temperature=temperature)
         self._blend(tile.to(device=self.volume.device, dtype=self.volume.dtype).unsqueeze(0), [roi])
 
-    def integrate_batch(self, batch: torch.Tensor, rois):
+    def integrate_batch(self, batch: torch.Tensor, rois, *, activation=None, temperature=1.0):
+        """``VolumeMerger.integrate_batch`` in torch ops; an activation is ``A(batch)`` evaluated first (``tta_3d.apply_activation``)."""
         if len(batch) != len(rois):
             raise ValueError("Number of images in batch does not correspond to number of coordinates")
+        act = self._act_config(activation, temperature, "VolumeMerger.integrate_batch")
         if self._defer:
-            return self._deferred_blend(batch, rois, (batch.dtype, (), 0), "VolumeMerger.integrate_batch")
+            return self._deferred_blend(apply_activation(batch, activation, temperature), rois, (batch.dtype, (), 0) + act, "VolumeMerger.integrate_batch")
+        batch = apply_activation(batch, activation, temperature)
         self._blend(batch.to(device=self.volume.device, dtype=self.volume.dtype), rois)
 
-    def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean"):
+    def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean", *, activation=None, temperature=1.0):
         """``VolumeMerger.integrate_batch_deaugment`` in torch ops: the views un-flipped and reduced in the batch's dtype
-        (``_host.reduce_stack``), then blended by ``integrate_batch``."""
+        (``_host.reduce_stack``; with an activation: of ``A(batch)``, float32), then blended by ``integrate_batch``."""
         from .tta import _reduction_code
 
         views = mirror_views(mirror)
@@ -784,12 +827,14 @@ class HostBackedVolumeMerger(VolumeMerger):
         code = _reduction_code(reduction)
         if code is None:
             raise ValueError(f"reduction={reduction!r} cannot be fused into the tile merge")
-        batch = batch.to(device=self._volume.device)
+        act = self._act_config(activation, temperature, "VolumeMerger.integrate_batch_deaugment")
+        raw_dtype = batch.dtype
+        batch = apply_activation(batch.to(device=self._volume.device), activation, temperature)
         if N.volume_layout(batch) == N.LAYOUT_CHANNELS_LAST:
             batch = batch.contiguous()      # torch's sum over the stacked views follows the strides: reduce as the dense batch does
         stack = torch.stack([flip_view(c, m) for c, m in zip(torch.chunk(batch, len(views)), views)])
         if self._defer:
-            return self._deferred_blend(_host.reduce_stack(stack, code), rois, (batch.dtype, tuple(views), code), "VolumeMerger.integrate_batch_deaugment")
+            return self._deferred_blend(_host.reduce_stack(stack, code), rois, (raw_dtype, tuple(views), code) + act, "VolumeMerger.integrate_batch_deaugment")
         self.integrate_batch(_host.reduce_stack(stack, code), rois)
 
     def _host_merge(self):

@@ -13,7 +13,14 @@ lies (``ptb_volume_channels_last.hip``; fusable reductions), with the bits of it
 refused with NotImplementedError, while a host tensor keeps torch's autograd through the torch ops.
 ``VolumeSlicer.split_device(.., mirror=)`` writes the augmented batch straight from the volume and
 ``VolumeMerger.integrate_batch_deaugment`` un-flips, reduces and blends in one pass per tile.
+
+``activation=`` ("sigmoid" | "softmax", with ``temperature=``) on ``mirror_volume_deaugment`` and on the ``VolumeMerger`` calls applies
+``A(y) = (y.float() * temperature).sigmoid()`` / ``.softmax(dim=1)`` -- the reference's ``ApplySigmoidTo`` / ``ApplySoftmaxTo`` -- to the
+model's logits inside the same launch (``ptb_volume_activation.hip``): the call means the call without it on ``A(y)``, a float32 tensor that
+is never written.
 """
+import math
+
 from typing import Callable, Optional, Tuple, Union
 
 import torch
@@ -21,7 +28,7 @@ import torch
 from .. import _native as N
 from . import _host
 
-__all__ = ["MIRROR_VIEWS", "mirror_volume_augment", "mirror_volume_deaugment"]
+__all__ = ["MIRROR_VIEWS", "mirror_volume_augment", "mirror_volume_deaugment", "apply_activation"]
 
 _AXIS_BITS = {"d": 4, "h": 2, "w": 1}
 
@@ -60,6 +67,35 @@ def _check_volume_batch(x: torch.Tensor, what: str) -> int:
     return code
 
 
+def _activation_code(activation, temperature, what: str) -> int:
+    """PTB_ACT_* of ``activation`` (None | "sigmoid" | "softmax"); anything else, or a non-finite ``temperature``, raises ValueError."""
+    if activation is not None and not (isinstance(activation, str) and activation in N.ACT_CODES):
+        raise ValueError(f"{what}: activation must be None, 'sigmoid' or 'softmax', got {activation!r}")
+    try:
+        finite = not isinstance(temperature, bool) and math.isfinite(temperature)
+    except TypeError:
+        finite = False
+    if not finite:
+        raise ValueError(f"{what}: temperature must be a finite float, got {temperature!r}")
+    return N.ACT_CODES[activation]
+
+
+def apply_activation(y: torch.Tensor, activation, temperature: float = 1.0) -> torch.Tensor:
+    """``A(y)`` in torch ops: ``(y.float() * temperature).sigmoid()`` | ``.softmax(dim=1)`` (float32; ``y`` itself for None) -- what the fused
+    calls mean, and what the host paths evaluate."""
+    code = _activation_code(activation, temperature, "apply_activation")
+    if code == N.ACT_NONE:
+        return y
+    z = y.float() * float(temperature)
+    return z.sigmoid() if code == N.ACT_SIGMOID else z.softmax(dim=1)
+
+
+def _check_softmax_channels(code: int, channels: int, what: str):
+    if code == N.ACT_SOFTMAX and channels > N.ACT_MAX_SOFTMAX_CHANNELS:
+        raise NotImplementedError(f"{what}: the fused softmax keeps the channels of a voxel in registers and serves 1..{N.ACT_MAX_SOFTMAX_CHANNELS} "
+                                  f"of them, got {channels}; apply y.softmax(1) yourself and call without activation=")
+
+
 def _divisible(n: int, V: int):
     if n % V != 0:
         raise RuntimeError(f"Input batch size ({n}) must be divisible by {V}.")
@@ -87,13 +123,42 @@ def mirror_volume_augment(x: torch.Tensor, mirror: str = "dhw") -> torch.Tensor:
     return _mirror(x, code, views, True, (len(views) * x.shape[0],) + tuple(x.shape[1:]))
 
 
+def _deaugment_activated(y, views, code, act, temperature):
+    """``ptb_volume_mirror_reduce_act``: the fused reduction over ``A(y)``, dense float32 out."""
+    dtype = _check_volume_batch(y, "mirror_volume_deaugment")
+    V = len(views)
+    B = y.shape[0] // V
+    _, C, D, H, W = y.shape
+    _check_softmax_channels(act, C, "mirror_volume_deaugment")
+    if N.volume_layout(y) == N.LAYOUT_CHANNELS_LAST:
+        dtype |= N.SRC_CHANNELS_LAST
+    else:
+        y = y.contiguous()
+    out = torch.empty((B, C, D, H, W), device=y.device, dtype=torch.float32)
+    with N.on_device(y.device):
+        rc = N.load().ptb_volume_mirror_reduce_act(y.data_ptr(), dtype, out.data_ptr(), V, N.int_array(views), code, B, C, D, H, W, act,
+                                                   temperature, N.stream_ptr(y.device))
+    N.bump()
+    N.check(rc, "ptb_volume_mirror_reduce_act")
+    return out
+
+
 def mirror_volume_deaugment(y: torch.Tensor, mirror: str = "dhw",
-                            reduction: Optional[Union[str, Callable]] = "mean") -> torch.Tensor:
+                            reduction: Optional[Union[str, Callable]] = "mean", *, activation: Optional[str] = None,
+                            temperature: float = 1.0) -> torch.Tensor:
     """Undo ``mirror_volume_augment`` on the model output ``[V*B, C, D, H, W]`` and reduce the views.
 
     ``reduction``: the reductions of ``tta._deaugment_averaging`` -- "mean" | "sum" | "gmean" | "hmean" | "harmonic1p" | "logodd" |
     "log1p" (and their long names) reduce in fp32 in view order in one launch and return ``[B, C, D, H, W]`` in ``y``'s dtype; a
-    callable is given the un-flipped ``[V, B, C, D, H, W]`` stack (``reduction(stack, dim=0)``); None returns that stack."""
+    callable is given the un-flipped ``[V, B, C, D, H, W]`` stack (``reduction(stack, dim=0)``); None returns that stack.
+
+    ``activation``: None | "sigmoid" | "softmax" (anything else: ValueError), ``temperature``: a finite float.  The call then equals
+    ``mirror_volume_deaugment(A(y), mirror, reduction)`` with ``A(y) = (y.float() * temperature).sigmoid()`` / ``.softmax(dim=1)``, so the
+    result is float32 whatever ``y``'s dtype.  On a CUDA tensor with a fusable reduction ``A`` runs inside the one launch, on the logits where
+    they lie (dense or ``channels_last_3d``, float32 / float16 / bfloat16): per voxel and view ``z = x * temperature`` rounded, sigmoid
+    ``1 / (1 + exp(-z))`` (exact 0 / 1 when it saturates, never NaN), softmax ``exp(z - max_c z) / sum_c exp(..)`` summed in channel order,
+    then the reduction as without it.  Finite logits are the defined inputs.  The fused softmax serves 1 <= C <= 16 (NotImplementedError
+    above that), sigmoid any C.  Host tensors, and a callable or None reduction, apply ``A`` with torch ops and go on as without it."""
     from .tta import _reduction_code
 
     views = mirror_views(mirror)
@@ -102,6 +167,11 @@ def mirror_volume_deaugment(y: torch.Tensor, mirror: str = "dhw",
     code = _reduction_code(reduction)
     if code is None and not (callable(reduction) or reduction in {None, "None", "none"}):
         raise KeyError(f"Unsupported reduction mode {reduction}")
+    act = _activation_code(activation, temperature, "mirror_volume_deaugment")
+    if act != N.ACT_NONE:
+        if y.device.type == "cuda" and code is not None:
+            return _deaugment_activated(y, views, code, act, float(temperature))
+        y = apply_activation(y, activation, temperature)
     if y.device.type != "cuda":
         if code is not None and N.volume_layout(y) == N.LAYOUT_CHANNELS_LAST:
             y = y.contiguous()      # torch's sum over the stacked views follows the strides (1 ulp with 8 views): reduce as the dense batch does

@@ -120,5 +120,20 @@ for scalar in (0, 1):
             call("ptb_volume_plan_upload", plan, p(9), NUL)
             call("ptb_volume_plan_submit", plan, i32(0), i32(4), p(1), i64(4 * 8 * 8 * w), i64(4 * 4 * 8 * 8 * w), i32(dt | cl), i32(nv), arr(i32, list(range(nv))), i32(red), p(8), p(6), NUL)
             L.ptb_volume_plan_destroy(plan)
+    # the activations of ptb_volume_activation.hip: softmax on both sides of the 8 channels of the 4-voxel lanes, sigmoid beyond 16
+    for (act, Cc), dt, cl, W, nv in it.product(((2, 4), (2, 8), (2, 9), (2, 16), (1, 3), (1, 20), (0, 4)), (0, 1, 2), (0, 0x200), (8, 7), (1, 8)):
+        masks = arr(i32, list(range(nv)))
+        call("ptb_volume_mirror_reduce_act", p(1), i32(dt | cl), p(6), i32(nv), masks, i32(2), i32(2), i32(Cc), i32(8), i32(8), i32(W), i32(act), f32(1.0), NUL)
+        z = arr(i64, [0, 8]); y = arr(i64, [0, 4]); x = arr(i64, [0, 3])
+        call("ptb_volume_mirror_accumulate_act", p(1), p(2), p(3), p(4), i32(dt | cl), i32(nv), masks, i32(2), z, y, x, i32(2), i32(Cc), i32(8), i32(8), i32(W), i32(16), i32(16), i32(16), i32(act), f32(1.0), NUL)
+    z = arr(i64, [0, 0, 4, 4]); y = arr(i64, [0, 4, 0, 4]); x = arr(i64, [0, 0, 0, 0])
+    for kind, dt, cl, nv, w, (act, Cc) in it.product(range(6), (0, 1, 2), (0, 0x200), (0, 8), (8, 6), ((2, 4), (2, 9), (1, 20))):
+        plan = C.c_void_p()
+        nb = L.ptb_volume_plan_create(z, y, x, i32(4), i32(Cc), i32(8), i32(8), i32(w), i32(12), i32(12), i32(w), arr(i64, [0, 0, 0, 12, 12, w]), i32(0), i32(kind), C.byref(plan))
+        shim.ptb_shim_mark(("volume plan %d" % nb).encode())
+        if nb >= 0 and plan:
+            call("ptb_volume_plan_upload", plan, p(9), NUL)
+            call("ptb_volume_plan_submit_act", plan, i32(0), i32(4), p(1), i64(Cc * 8 * 8 * w), i64(4 * Cc * 8 * 8 * w), i32(dt | cl), i32(nv), arr(i32, list(range(nv))), i32(2), p(8), p(6), i32(act), f32(1.0), NUL)
+            L.ptb_volume_plan_destroy(plan)
 L.ptb_set_tunable(1, 0)
 shim.ptb_shim_close()
