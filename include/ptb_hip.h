@@ -506,6 +506,29 @@ int ptb_deaug_accumulate_t(float* image, float* norm, const float* weight, const
                            int reduction, const int64_t* xs, const int64_t* ys, int B, int C, int th, int tw, int H, int W,
                            uint8_t* fresh, int fresh_rows, ptb_stream_t stream);
 
+/* ---- Activations inside the 2-D de-augmentation and tile merges (ptb_tile_activation.hip) -------------------------------------------
+ * The 2-D twins of the 3-D block above ("Activations inside the 3-D ..."), with its semantics: each entry point takes the arguments of
+ * its namesake (ptb_deaug_reduce_t, ptb_deaug_accumulate_t with its first-touch bitmap, ptb_band_plan_submit) plus `activation`
+ * (PTB_ACT_*) and a finite `temperature`, and means the namesake on the float32 tensor A(y) = sigmoid(y * temperature) | softmax over
+ * the channels of (y * temperature), evaluated per view and pixel in registers on the widened logits: z = x * t rounded; sigmoid
+ * 1 / (1 + exp(-z)); softmax exp(z - max_c z) summed in channel order, times the reciprocal of the sum; then red_pre, the view sum in
+ * view order, red_post, tile * weight in integration order.  The reduced value is NOT rounded to a half source type (the source
+ * counts as fp32; PTB_ROUND_SRC is ignored), PTB_ACT_NONE included; ptb_deaug_reduce_act writes dense fp32 [B, C, H, W].
+ * PTB_SRC_CHANNELS_LAST keeps its meaning.  Before anything touches the device: a bad activation code or a non-finite temperature ->
+ * PTB_EINVAL; PTB_ACT_SOFTMAX with C > 16 -> PTB_EUNSUPPORTED; a planar source whose shape the vector kernels do not take (tiles off
+ * the 4-pixel grid or unaligned: the scalar-kernel shapes of the namesakes) -> PTB_EUNSUPPORTED -- the caller applies A itself and
+ * calls the namesake.  A planar source of any dtype is served at every chunk size.  ptb_band_plan_submit_act: the entry point,
+ * activation and temperature belong to the image's configuration (a change -> PTB_EUNSUPPORTED, nothing recorded or launched);
+ * ptb_band_plan_submit_next declines such an image (PTB_EUNSUPPORTED): every batch of it takes this call. */
+int ptb_deaug_reduce_act(const void* in, int in_dtype, float* out, int V, const int* views, int reduction, int B, int C, int H, int W,
+                         int activation, float temperature, ptb_stream_t stream);
+int ptb_deaug_accumulate_act(float* image, float* norm, const float* weight, const void* in, int in_dtype, int V, const int* views,
+                             int reduction, const int64_t* xs, const int64_t* ys, int B, int C, int th, int tw, int H, int W,
+                             uint8_t* fresh, int fresh_rows, int activation, float temperature, ptb_stream_t stream);
+int ptb_band_plan_submit_act(ptb_band_plan* plan, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride,
+                             int in_dtype, int V, const int* views, int reduction, float* merged, const float* norm_full,
+                             const float* weight, int activation, float temperature, ptb_stream_t stream);
+
 /* ---- reductions over a stack of ANY length, explicit eps (inference/functional.py:247-331; tta.py:63-95) ----------
  * out[i] = post(mean_t pre(src[t, i])) for src [T, n] contiguous fp32: geometric_mean, harmonic_mean(eps), harmonic1p_mean,
  * logodd_mean(eps), log1p_mean, mean, sum along dim 0.  The fused view kernels above take at most 8 planes and the default

@@ -36,7 +36,7 @@ ROUND_SRC = 0x100           # PTB_ROUND_SRC, or-ed into a dtype code: round the 
 SRC_CHANNELS_LAST = 0x200   # PTB_SRC_CHANNELS_LAST, or-ed into a dtype code: the batch is [V*B, th, tw, C] memory (a model in torch.channels_last)
 DTYPE_MASK = 0xFF           # the PTB_F32 / PTB_F16 / PTB_BF16 part of a dtype code that carries flags
 LAYOUT_DENSE, LAYOUT_CHANNELS_LAST, LAYOUT_OTHER = range(3)
-ACT_NONE, ACT_SIGMOID, ACT_SOFTMAX = range(3)   # PTB_ACT_*: the activation fused into the 3-D de-augmentation and tile merges
+ACT_NONE, ACT_SIGMOID, ACT_SOFTMAX = range(3)   # PTB_ACT_*: the activation fused into the 2-D / 3-D de-augmentation and tile merges
 ACT_CODES = {None: ACT_NONE, "sigmoid": ACT_SIGMOID, "softmax": ACT_SOFTMAX}
 ACT_MAX_SOFTMAX_CHANNELS = 16
 
@@ -170,6 +170,9 @@ SIGNATURES = {
     "ptb_volume_plan_destroy": (None, [_vp]),
     "ptb_volume_mirror_reduce_act": (_c_int, [_vp, _c_int, _vp, _c_int, _ip] + [_c_int] * 7 + [_c_f, _vp]),
     "ptb_volume_mirror_accumulate_act": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _ip, _c_int, _i64p, _i64p, _i64p] + [_c_int] * 9 + [_c_f, _vp]),
+    "ptb_deaug_reduce_act": (_c_int, [_vp, _c_int, _vp, _c_int, _ip] + [_c_int] * 6 + [_c_f, _vp]),
+    "ptb_deaug_accumulate_act": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _ip, _c_int, _i64p, _i64p] + [_c_int] * 6 + [_vp, _c_int, _c_int, _c_f, _vp]),
+    "ptb_band_plan_submit_act": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_i64, _c_int, _c_int, _ip, _c_int, _vp, _vp, _vp, _c_int, _c_f, _vp]),
     "ptb_volume_plan_submit_act": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_i64, _c_int, _c_int, _ip, _c_int, _vp, _vp, _c_int, _c_f, _vp]),
 }
 

@@ -16,6 +16,7 @@
 // 768 that fit the chip, so ramp-up, the partial last round and the kernel boundary cost ~10 % of its 100 us; a group of 4 bands
 // pays them once per 400 us.  Items are ordered heavy-first (4-tile items before 2- and 1-tile ones) so the tail is short work.
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "ptb_dispatch.h"
@@ -211,6 +212,9 @@ struct ptb_band_plan {
     std::vector<long long> vs;
     int cfg_set = 0, cfg_dtype = 0, cfg_V = 0, cfg_codes = 0, cfg_red = 0;
     int cfg_views[ptb::MAX_VIEWS] = {0};
+    bool cfg_act_entry = false;           // the image came in through ptb_band_plan_submit_act
+    int cfg_activation = 0;
+    float cfg_temperature = 1.0f;
     const void *cfg_merged = nullptr, *cfg_norm = nullptr, *cfg_weight = nullptr;
     // custody (round 6): the byte ranges of the batches of this image that a later launch group still reads, in integration order --
     // what ptb_band_plan_submit_next checks a new batch against (a model writing into a reused output buffer)
@@ -475,9 +479,10 @@ extern "C" int ptb_band_plan_state(const ptb_band_plan* p, int* pos, int* launch
 
 extern "C" void ptb_band_plan_destroy(ptb_band_plan* p) { delete p; }
 
-extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride,
-                                    int in_dtype, int V, const int* views, int reduction, float* merged, const float* norm_full,
-                                    const float* weight, ptb_stream_t stream) {
+// ptb_band_plan_submit (act_entry = false) and ptb_band_plan_submit_act (true: the kernels of ptb_tile_activation.hip)
+static int plan_submit(ptb_band_plan* p, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride, int in_dtype, int V,
+                       const int* views, int reduction, float* merged, const float* norm_full, const float* weight, bool act_entry, int activation,
+                       float temperature, ptb_stream_t stream) {
     if (!p || !batch || !merged || !norm_full || !weight || B < 1) return PTB_EINVAL;
     if (!p->dev_items) return PTB_EINVAL;
     const int dtype_arg = in_dtype;      // (with PTB_ROUND_SRC and PTB_SRC_CHANNELS_LAST: part of the image's configuration)
@@ -491,12 +496,16 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
         nT += views[k] & 1;
     }
     if (nT && p->th != p->tw) return PTB_EINVAL;
+    if (activation == PTB_ACT_SOFTMAX && p->C > 16) return PTB_EUNSUPPORTED;   // the channels of a pixel are resident
+    if (act_entry && !src_cl && !ta_view_set_ok(V, [&] { int v = 0; for (int k = 0; k < V; ++k) v |= (views[k] & 7) << (3 * k); return v; }()))
+        return PTB_EUNSUPPORTED;                                                // planar sources: identity and the TTA groups
     // not the next planned tiles, or a different configuration than the image started with: the caller leaves deferred mode
     if (pos != p->pos || pos + B > p->n) return PTB_EUNSUPPORTED;
     const int codes = [&] { int v = 0; for (int k = 0; k < V; ++k) v |= (views[k] & 7) << (3 * k); return v; }();
     if (p->cfg_set) {
         if (p->cfg_dtype != dtype_arg || p->cfg_V != V || p->cfg_codes != codes || p->cfg_red != reduction || p->cfg_merged != merged ||
-            p->cfg_norm != norm_full || p->cfg_weight != weight) return PTB_EUNSUPPORTED;
+            p->cfg_norm != norm_full || p->cfg_weight != weight || p->cfg_act_entry != act_entry || p->cfg_activation != activation ||
+            p->cfg_temperature != temperature) return PTB_EUNSUPPORTED;
     }
     const long long per_tile = (long long)p->C * p->th * p->tw;
     const unsigned mask = in_dtype == PTB_F32 ? 15u : 7u;
@@ -507,6 +516,7 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
     p->cfg_set = 1; p->cfg_dtype = dtype_arg; p->cfg_V = V; p->cfg_codes = codes; p->cfg_red = reduction;
     for (int k = 0; k < V; ++k) p->cfg_views[k] = views[k];
     p->cfg_merged = merged; p->cfg_norm = norm_full; p->cfg_weight = weight;
+    p->cfg_act_entry = act_entry; p->cfg_activation = activation; p->cfg_temperature = temperature;
     {
         int lg = 0;
         for (int b = 0; b < B; ++b) lg = std::max(lg, p->last_group[pos + b]);
@@ -540,8 +550,9 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
             GroupTiles gt;
             for (size_t s = 0; s < g.tiles.size(); ++s) { gt.src[s] = p->src[g.tiles[s]]; gt.vs[s] = p->vs[g.tiles[s]]; }
             for (size_t s = g.tiles.size(); s < (size_t)PLAN_TILES; ++s) { gt.src[s] = nullptr; gt.vs[s] = 0; }
-            if (src_cl) {   // PTB_SRC_CHANNELS_LAST: the same work-item table, one workgroup per item over all channels
-                cl_launch_plan(a, p->dev_items + g.item_off, gt, g.item_cnt, (hipStream_t)stream);
+            if (act_entry || src_cl) {   // activations / PTB_SRC_CHANNELS_LAST: the same work-item table, one workgroup per item over all channels
+                if (act_entry) ta_launch_plan(a, p->dev_items + g.item_off, gt, g.item_cnt, src_cl, activation, temperature, (hipStream_t)stream);
+                else cl_launch_plan(a, p->dev_items + g.item_off, gt, g.item_cnt, (hipStream_t)stream);
                 const int rc = check_launch();
                 if (rc != PTB_OK) return rc;
                 ++p->launched;
@@ -570,6 +581,23 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
     return launched;
 }
 
+extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride,
+                                    int in_dtype, int V, const int* views, int reduction, float* merged, const float* norm_full,
+                                    const float* weight, ptb_stream_t stream) {
+    return plan_submit(p, pos, B, batch, tile_stride, view_stride, in_dtype, V, views, reduction, merged, norm_full, weight, false, PTB_ACT_NONE, 1.0f,
+                       stream);
+}
+
+// ptb_band_plan_submit on A(batch) = sigmoid / softmax of the logits (PTB_ACT_*), evaluated in registers.  The source counts as fp32
+// (PTB_ROUND_SRC is ignored); entry point, activation and temperature belong to the image's configuration.
+extern "C" int ptb_band_plan_submit_act(ptb_band_plan* p, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride,
+                                        int in_dtype, int V, const int* views, int reduction, float* merged, const float* norm_full,
+                                        const float* weight, int activation, float temperature, ptb_stream_t stream) {
+    if (activation < PTB_ACT_NONE || activation > PTB_ACT_SOFTMAX || !std::isfinite(temperature)) return PTB_EINVAL;
+    return plan_submit(p, pos, B, batch, tile_stride, view_stride, in_dtype & ~PTB_ROUND_SRC, V, views, reduction, merged, norm_full, weight, true,
+                       activation, temperature, stream);
+}
+
 // The next planned batch of an image as the shortest possible host call (round 6: one integrate_batch of the reference's loop, inference/
 // tiles.py:321-339, costs the interpreter ~7 us through the 14-argument form above -- more than the kernels of the plain, TTA-free loop).
 // Everything but the batch itself is what the image's first ptb_band_plan_submit set: dtype (+ PTB_ROUND_SRC), views, reduction, merged /
@@ -579,7 +607,7 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
 // has no configuration yet / the tiles run out, or a negative code of ptb_band_plan_submit.
 extern "C" int ptb_band_plan_submit_next(ptb_band_plan* p, const void* batch, int B, ptb_stream_t stream) {
     if (!p || !batch || B < 1) return PTB_EINVAL;
-    if (!p->cfg_set || p->pos + B > p->n) return PTB_EUNSUPPORTED;
+    if (!p->cfg_set || p->cfg_act_entry || p->pos + B > p->n) return PTB_EUNSUPPORTED;      // (an activated image takes the full call)
     const int dt = p->cfg_dtype & ~(PTB_ROUND_SRC | PTB_SRC_CHANNELS_LAST);
     const size_t esz = dt == PTB_F32 ? 4 : 2;
     const long long per_tile = (long long)p->C * p->th * p->tw;

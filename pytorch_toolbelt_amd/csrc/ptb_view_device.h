@@ -570,4 +570,14 @@ void cl_launch_accum(const ViewArgs& a, const CellArgs& g, int ch, hipStream_t s
 void cl_launch_band(const ViewArgs& a, const BandArgs& g, int chunks, hipStream_t s);                            // ptb_merge_band (32-row chunks)
 void cl_launch_plan(const ViewArgs& a, const BandItem* items, const GroupTiles& t, int n_items, hipStream_t s);  // ptb_band_plan_submit
 
+// ------------------------------------------------------------------------------------------------ activations (PTB_ACT_*)
+// The accumulate launch and the band-plan launch group over A(tile) = sigmoid / softmax of the logits, dense (the planar vector kernels'
+// shapes only) or channels-last (`src_cl`) sources; the same cells / chunk rows `ch` / work-item table as their namesakes.  Defined in
+// ptb_tile_activation.hip.
+struct ActCfg { int activation; float temperature; };
+bool ta_view_set_ok(int nviews, int codes);   // planar sources: identity and the five TTA groups (compiled-in view codes) only
+void ta_launch_accum(const ViewArgs& a, const CellArgs& g, int ch, bool src_cl, int activation, float temperature, hipStream_t s);   // ptb_deaug_accumulate_act
+void ta_launch_plan(const ViewArgs& a, const BandItem* items, const GroupTiles& t, int n_items, bool src_cl, int activation, float temperature,
+                    hipStream_t s);                                                                              // ptb_band_plan_submit_act
+
 }  // namespace ptb

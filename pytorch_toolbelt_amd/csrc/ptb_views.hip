@@ -20,6 +20,7 @@
 // what makes this correct on MI355X; it also halves the RMW traffic of 50%-overlap batches and
 // reproduces the reference's sequential fp32 order bit-for-bit (mul and add are not contracted).
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "ptb_dispatch.h"
@@ -654,7 +655,7 @@ static int run_plain(ViewArgs& a, int ntiles_out, int mode, hipStream_t s, bool 
 }
 
 static int launch_group(const ViewArgs& a, const CellArgs& g, const std::vector<Cell>& cells, const Fresh& fr, bool fast, int ch,
-                        hipStream_t s, bool src_cl = false) {
+                        hipStream_t s, bool src_cl = false, const ActCfg* act = nullptr) {
     const long long blocks = (long long)a.total_chunks * a.C;
     if (blocks <= 0) return PTB_OK;
     if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
@@ -662,6 +663,8 @@ static int launch_group(const ViewArgs& a, const CellArgs& g, const std::vector<
         if (!fast) hipLaunchKernelGGL(norm_accum_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, g);
         else with_value<64, 32, 16>(ch, [&](auto chv) {
             hipLaunchKernelGGL(norm_accum_kernel<chv()>, dim3((unsigned)blocks), dim3(chv() * 16), 0, s, a, g); });
+    } else if (act) {      // ptb_deaug_accumulate_act: the same cells and chunks, one workgroup per chunk over all channels (ptb_tile_activation.hip)
+        ta_launch_accum(a, g, ch, src_cl, act->activation, act->temperature, s);
     } else if (src_cl) {   // PTB_SRC_CHANNELS_LAST: the same cells and chunks, one workgroup per chunk over all channels, any shape
         cl_launch_accum(a, g, ch, s);
     } else if (!fast) {
@@ -675,7 +678,8 @@ static int launch_group(const ViewArgs& a, const CellArgs& g, const std::vector<
 }
 
 // Accumulate a run of tiles [lo, hi) of the batch; splits recursively until each launch group decomposes.
-static int run_accum(ViewArgs& a, const int* xs, const int* ys, int lo, int hi, bool fast, int ch, const Fresh& fr, hipStream_t s, bool src_cl = false) {
+static int run_accum(ViewArgs& a, const int* xs, const int* ys, int lo, int hi, bool fast, int ch, const Fresh& fr, hipStream_t s, bool src_cl = false,
+                     const ActCfg* act = nullptr) {
     if (lo >= hi) return PTB_OK;
     CellArgs g;
     int ids[MAX_GROUP];
@@ -690,10 +694,10 @@ static int run_accum(ViewArgs& a, const int* xs, const int* ys, int lo, int hi, 
     if (st == DECOMP_SPLIT) {
         if (n == 1) return PTB_EUNSUPPORTED;  // cannot happen: one tile is one cell
         const int mid = lo + n / 2;
-        const int rc = run_accum(a, xs, ys, lo, mid, fast, ch, fr, s, src_cl);
-        return rc ? rc : run_accum(a, xs, ys, mid, hi, fast, ch, fr, s, src_cl);
+        const int rc = run_accum(a, xs, ys, lo, mid, fast, ch, fr, s, src_cl, act);
+        return rc ? rc : run_accum(a, xs, ys, mid, hi, fast, ch, fr, s, src_cl, act);
     }
-    return launch_group(a, g, cells, fr, fast, ch, s, src_cl);
+    return launch_group(a, g, cells, fr, fast, ch, s, src_cl, act);
 }
 
 // Dry run of run_accum's grouping on a scratch bitmap: PTB_EFRESH if any launch group would need a zero-fill.
@@ -732,8 +736,8 @@ static int probe_accum(const int* xs, const int* ys, int lo, int hi, int tw, int
 
 static int accumulate_impl(float* image, float* norm, const float* weight, const float* in, int V, const int* views,
                            int reduction, const int64_t* xs64, const int64_t* ys64, int B, int C, int th, int tw, int H, int W,
-                           uint8_t* fresh, int fresh_rows, hipStream_t s, int in_dtype = PTB_F32) {
-    const int round_src = (in_dtype & PTB_ROUND_SRC) ? 1 : 0;
+                           uint8_t* fresh, int fresh_rows, hipStream_t s, int in_dtype = PTB_F32, const ActCfg* act = nullptr) {
+    const int round_src = (in_dtype & PTB_ROUND_SRC) && !act ? 1 : 0;      // (an activated source counts as fp32: nothing is rounded to it)
     const bool src_cl = (in_dtype & PTB_SRC_CHANNELS_LAST) != 0;
     in_dtype &= ~(PTB_ROUND_SRC | PTB_SRC_CHANNELS_LAST);
     if (in_dtype < PTB_F32 || in_dtype > PTB_BF16) return PTB_EINVAL;
@@ -742,6 +746,7 @@ static int accumulate_impl(float* image, float* norm, const float* weight, const
     if (B < 0 || C < 1 || th < 1 || tw < 1 || H < 1 || W < 1) return PTB_EINVAL;
     if (reduction < PTB_RED_SUM || reduction > PTB_RED_LOG1P) return PTB_EINVAL;
     if (int rc = validate_views(V, views, th, tw)) return rc;
+    if (act && act->activation == PTB_ACT_SOFTMAX && C > 16) return PTB_EUNSUPPORTED;   // the channels of a pixel are resident
     if (B == 0) return PTB_OK;
     std::vector<int> xs(B), ys(B);
     bool aligned = true;
@@ -774,7 +779,9 @@ static int accumulate_impl(float* image, float* norm, const float* weight, const
         for (int b = 0; b < B && fast; ++b) if ((ys[b] - ys[0]) % 4) fast = false;
     }
     const int ch = fast ? g_chunk_rows : 64;
-    if (in_dtype != PTB_F32 && (!fast || ch != 32)) return PTB_EUNSUPPORTED;  // half sources: default vector kernels only
+    if (act) {   // planar sources: the vector kernels' shapes only (any chunk rows, any dtype); channels-last lanes own a pixel: any shape
+        if (norm_only || (!src_cl && (!fast || !ta_view_set_ok(V, a.codes)))) return PTB_EUNSUPPORTED;
+    } else if (in_dtype != PTB_F32 && (!fast || ch != 32)) return PTB_EUNSUPPORTED;  // half sources: default vector kernels only
     Fresh fr{fresh, fresh_rows, H, W};
     if (fresh) {
         if (fresh_rows < 1) return PTB_EINVAL;
@@ -801,11 +808,11 @@ static int accumulate_impl(float* image, float* norm, const float* weight, const
                 if (rc) return rc;
             } else {  // one group: launch it right away with the plan we already have
                 a.ncells = nc; a.total_chunks = tc;
-                return launch_group(a, g, cells, fr, fast, ch, s, src_cl);
+                return launch_group(a, g, cells, fr, fast, ch, s, src_cl, act);
             }
         }
     }
-    return run_accum(a, xs.data(), ys.data(), 0, B, fast, ch, fr, s, src_cl);
+    return run_accum(a, xs.data(), ys.data(), 0, B, fast, ch, fr, s, src_cl, act);
 }
 
 }  // namespace ptb
@@ -988,6 +995,17 @@ extern "C" int ptb_deaug_accumulate_t(float* image, float* norm, const float* we
                                       int tw, int H, int W, uint8_t* fresh, int fresh_rows, ptb_stream_t stream) {
     return accumulate_impl(image, norm, weight, static_cast<const float*>(in), V, views, reduction, xs, ys, B, C, th, tw, H, W, fresh,
                            fresh_rows, (hipStream_t)stream, in_dtype);
+}
+
+// ptb_deaug_accumulate_t on A(in) = sigmoid / softmax of the logits (PTB_ACT_*), evaluated in registers: kernels of ptb_tile_activation.hip
+extern "C" int ptb_deaug_accumulate_act(float* image, float* norm, const float* weight, const void* in, int in_dtype, int V,
+                                        const int* views, int reduction, const int64_t* xs, const int64_t* ys, int B, int C, int th,
+                                        int tw, int H, int W, uint8_t* fresh, int fresh_rows, int activation, float temperature,
+                                        ptb_stream_t stream) {
+    if (activation < PTB_ACT_NONE || activation > PTB_ACT_SOFTMAX || !std::isfinite(temperature)) return PTB_EINVAL;
+    const ActCfg act{activation, temperature};
+    return accumulate_impl(image, norm, weight, static_cast<const float*>(in), V, views, reduction, xs, ys, B, C, th, tw, H, W, fresh,
+                           fresh_rows, (hipStream_t)stream, in_dtype, &act);
 }
 
 static int deaug_reduce_impl(const float* in, int in_dtype, float* out, int V, const int* views, int reduction, int B, int C, int H,

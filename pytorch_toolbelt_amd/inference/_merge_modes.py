@@ -377,8 +377,8 @@ class DeferredBands(_OfMerger):
         m._plan.active = keep_plan and m._plan.blocks      # (a band-only plan has no block strategy to hand the image to)
         m._merged = None                                   # (nothing was launched into it; the planned strategy makes its own)
         m._log, m._applied = [], 0
-        for batch, (coords, views, reduction, rnd), *_rest in held:
-            m._accumulate(batch, coords, views, reduction, rnd)
+        for batch, replay, *_rest in held:
+            m._accumulate(batch, *replay)      # (coords, views, reduction, rnd[, act])
 
     def soften(self, what):
         """A merger that deferred ON ITS OWN ACCOUNT (self-planned) is asked for something deferred merging cannot serve after bands
@@ -403,8 +403,8 @@ class DeferredBands(_OfMerger):
         plan.active = False
         log = list(m._log)                 # every crop of the image so far (the normaliser is built from it); the replay must not log twice
         m._materialize()
-        for batch, (coords, views, reduction, rnd), *_rest in held:
-            m._accumulate(batch, coords, views, reduction, rnd)
+        for batch, replay, *_rest in held:
+            m._accumulate(batch, *replay)
         m._log = log
         m._norm_ready()
         for y0, y1 in launched:
@@ -423,9 +423,11 @@ class DeferredBands(_OfMerger):
             return True
         return self.done < len(bands.bands) and end > bands.bands[self.done][2]
 
-    def _submit(self, batch, coords, views, pos, B, dcode, n_views, varr, code):
+    def _submit(self, batch, coords, views, pos, B, dcode, n_views, varr, code, act=None):
         """Take the planned tiles ``pos .. pos+B-1`` into custody and merge the launch groups they complete
-        (``ptb_band_plan_submit``: the pointer bookkeeping and the launches happen in C).  Returns its code: < 0 nothing was taken."""
+        (``ptb_band_plan_submit``: the pointer bookkeeping and the launches happen in C).  Returns its code: < 0 nothing was taken.
+        ``act`` = (PTB_ACT_* code, temperature): the held batch is logits, merged as ``A(batch)`` (``ptb_band_plan_submit_act``); entry
+        point, activation and temperature belong to the image's configuration -- a change is PTB_EUNSUPPORTED like a change of dtype."""
         m, bands = self.m, self.bands
         plan = m._plan
         if self.soft and not (dcode & LAZY_SRC) and tensor_version(batch) is None:
@@ -447,13 +449,18 @@ class DeferredBands(_OfMerger):
         per_tile = m.channels * int(m.weight.shape[1]) * int(m.weight.shape[2])
         dev = m._image.device
         with N.on_device(dev):
-            rc = N.load().ptb_band_plan_submit(bands.handle, pos, B, batch.data_ptr(), per_tile, B * per_tile, dcode, n_views, varr, code,
-                                               m._merged.data_ptr(), plan.norm_full.data_ptr(), m.weight.data_ptr(), N.stream_ptr(dev))
+            if act is None:
+                rc = N.load().ptb_band_plan_submit(bands.handle, pos, B, batch.data_ptr(), per_tile, B * per_tile, dcode, n_views, varr, code,
+                                                   m._merged.data_ptr(), plan.norm_full.data_ptr(), m.weight.data_ptr(), N.stream_ptr(dev))
+            else:
+                rc = N.load().ptb_band_plan_submit_act(bands.handle, pos, B, batch.data_ptr(), per_tile, B * per_tile, dcode, n_views, varr, code,
+                                                       m._merged.data_ptr(), plan.norm_full.data_ptr(), m.weight.data_ptr(), act[0], act[1],
+                                                       N.stream_ptr(dev))
         N.bump()
         if rc < 0:
             return rc
         lg = bands.last_group
-        self.held.keep(batch, span, (coords, views, code, dcode & N.ROUND_SRC), int(lg[pos + B - 1]) if bands.sorted_tiles else int(lg[pos:pos + B].max()))
+        self.held.keep(batch, span, (coords, views, code, dcode & N.ROUND_SRC) + ((act,) if act is not None else ()), int(lg[pos + B - 1]) if bands.sorted_tiles else int(lg[pos:pos + B].max()))
         plan.pos = pos + B
         if rc:
             done = self.done = self.done + rc
@@ -561,9 +568,10 @@ class DeferredBands(_OfMerger):
                          n_views * m.channels * th * tw * batch.element_size(), views, code, src_cl)
         return True
 
-    def take(self, batch, coords, xy, views, reduction, dcode):
+    def take(self, batch, coords, xy, views, reduction, dcode, act=None):
         """Any validated batch.  False: not deferrable -- the held batches were replayed and the caller goes on with the next
-        strategy."""
+        strategy.  (A batch with an activation always comes here: ``take_fast`` / ``take_slim`` serve calls without one, and an image that
+        was configured with one makes ``ptb_band_plan_submit_next`` decline.)"""
         m = self.m
         plan = m._plan
         B = xy.shape[1]
@@ -571,7 +579,7 @@ class DeferredBands(_OfMerger):
         soft = self.soft        # (read before _submit: its budget / provability exits rebind the strategy, and what follows is about the merger the caller made)
         if plan.active and not m._eager_norm and plan.follows(xy, B):
             varr = N.int_array(views) if views is not None else N.int_array([N.IDENT])
-            rc = self._submit(batch, coords, views, plan.pos, B, dcode, len(views) if views is not None else 1, varr, reduction)
+            rc = self._submit(batch, coords, views, plan.pos, B, dcode, len(views) if views is not None else 1, varr, reduction, act)
         if rc == N.PTB_EUNSUPPORTED:
             if not soft:
                 warn_once(("defer-deviation",), "TileMerger(defer=True): a batch deviates from the planned crop sequence / configuration (or "
@@ -728,7 +736,7 @@ class Incremental(_OfMerger):
     def __init__(self, merger):
         self._m = weakref.ref(merger)
 
-    def take(self, batch, coords, xy, xs, ys, views, n_views, varr, reduction, dcode):
+    def take(self, batch, coords, xy, xs, ys, views, n_views, varr, reduction, dcode, act=None):
         m = self.m
         B = xy.shape[1]
         lib = N.load()
@@ -737,6 +745,10 @@ class Incremental(_OfMerger):
         norm_ptr = m._norm.data_ptr() if m._eager_norm else None
 
         def launch(fresh_ptr):
+            if act is not None:      # ``A(batch)`` in registers (csrc/ptb_tile_activation.hip)
+                return lib.ptb_deaug_accumulate_act(m._image.data_ptr(), norm_ptr, m.weight.data_ptr(), batch.data_ptr(), dcode, n_views, varr,
+                                                    reduction, xs, ys, B, m.channels, th, tw, m.image_height, m.image_width, fresh_ptr,
+                                                    FRESH_ROWS, act[0], act[1], N.stream_ptr(dev))
             return lib.ptb_deaug_accumulate_t(m._image.data_ptr(), norm_ptr, m.weight.data_ptr(), batch.data_ptr(), dcode, n_views, varr,
                                               reduction, xs, ys, B, m.channels, th, tw, m.image_height, m.image_width, fresh_ptr,
                                               FRESH_ROWS, N.stream_ptr(dev))
@@ -748,6 +760,11 @@ class Incremental(_OfMerger):
                 m._materialize()
                 rc = launch(None)
         N.bump()
+        if rc == -2 and act is not None:   # a shape of the scalar kernels (tiles off the 4-pixel grid): A in torch ops, then today's entry point
+            from .tta_3d import apply_activation
+
+            name = {N.ACT_SIGMOID: "sigmoid", N.ACT_SOFTMAX: "softmax"}[act[0]]
+            return m._accumulate(apply_activation(batch, name, act[1]), coords, views, reduction)
         if rc == -2 and dcode & N.DTYPE_MASK != N.F32:   # shape needs the scalar kernels: take the reference's route (cast, then accumulate)
             if dcode & N.ROUND_SRC:        # (the source of a lazy de-augmentation handle: evaluate it as the eager call would -- a half tensor -- and blend that)
                 from ._views import deaug_reduce

@@ -677,11 +677,22 @@ class TileMerger:
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError("TileMerger accumulators must be contiguous float32 tensors")
 
-    def _accumulate(self, batch, coords, views, reduction, rnd=0):
+    def _activation(self, activation, temperature, what):
+        """(PTB_ACT_* code, temperature) of a call's keywords, or None without an activation; the argument errors of the 3-D calls."""
+        from .tta_3d import _activation_code, _check_softmax_channels
+
+        code = _activation_code(activation, temperature, what)
+        if code == N.ACT_NONE:
+            return None
+        _check_softmax_channels(code, self.channels, what)
+        return code, float(temperature)
+
+    def _accumulate(self, batch, coords, views, reduction, rnd=0, act=None):
         """Any batch, validated once, offered to the strategies in order: deferred bands, planned blocks, incremental.  ``rnd`` (flags):
         ``N.ROUND_SRC`` -- the batch is the half-precision source of a lazy de-augmentation handle (the reduced value is rounded to the
         source dtype before it is blended, as the reference's two calls do); ``_LAZY_SRC`` -- it is the source of such a handle at all
-        (what a self-deferring merger may keep without a version counter: ``_merge_modes.DeferredBands._submit``)."""
+        (what a self-deferring merger may keep without a version counter: ``_merge_modes.DeferredBands._submit``).  ``act``: None, or
+        ``(PTB_ACT_* code, temperature)`` -- the batch holds logits and stands for ``A(batch)`` (float32; ``csrc/ptb_tile_activation.hip``)."""
         self._check_state()
         if self._plan is not None and self._plan.active and self._window_edited():
             self._planned.off("integrating with an edited blending window")   # (the planned normaliser was built from the original one)
@@ -702,14 +713,22 @@ class TileMerger:
         dcode |= N.layout_flag(batch)
         if B:
             self._selfplan.observe(batch, n_views, rnd & _LAZY_SRC)
-        if B and self._deferred.active and self._deferred.take(batch, coords, xy, views, reduction, dcode | (rnd & _LAZY_SRC)):
+        if act is not None:
+            dcode &= ~N.ROUND_SRC          # (A(batch) is a float32 tensor: nothing is rounded to the batch's dtype)
+        if B and self._deferred.active and self._deferred.take(batch, coords, xy, views, reduction, dcode | (rnd & _LAZY_SRC), act):
             return
         xs = xy[0].ctypes.data_as(N._i64p)
         ys = xy[1].ctypes.data_as(N._i64p)
         varr = N.int_array(views) if views is not None else N.int_array([N.IDENT])
-        if B and self._plan is not None and self._planned.take(batch, xy, xs, ys, n_views, varr, reduction, dcode):
+        if act is not None and self._plan is not None and self._plan.active:
+            # planned blocks have no native activation: the image goes on incrementally (same bits)
+            _warn_once(("planned-activation",), "TileMerger: activation= is not fused into the planned-block kernels; this image continues on the "
+                                                "incremental path (same results).  TileMerger(crops=, defer=True) and self-planned deferred mergers "
+                                                "take an activation natively.")
+            self._planned.off("integrating with activation=")
+        if B and act is None and self._plan is not None and self._planned.take(batch, xy, xs, ys, n_views, varr, reduction, dcode):
             return
-        return self._incremental.take(batch, coords, xy, xs, ys, views, n_views, varr, reduction, dcode)
+        return self._incremental.take(batch, coords, xy, xs, ys, views, n_views, varr, reduction, dcode, act)
 
     def _offer_fast(self, batch, crop_coords, key, views, code, rnd=0):
         """The live strategy's cheap host path for the common call; False: ``_accumulate`` validates and decides."""
@@ -718,12 +737,21 @@ class TileMerger:
         return self._plan is not None and self._planned.take_fast(batch, crop_coords, key, views, code, rnd)
 
     # ------------------------------------------------------------------ reference API
-    def accumulate_single(self, tile: torch.Tensor, coords):
-        """Accumulate one ``[C, h, w]`` prediction at ``coords = (x, y, w, h)``."""
-        self._accumulate(self._prep(tile.unsqueeze(0)), _coords_xy([coords]), None, N.RED_SUM)
+    def accumulate_single(self, tile: torch.Tensor, coords, *, activation=None, temperature=1.0):
+        """Accumulate one ``[C, h, w]`` prediction at ``coords = (x, y, w, h)`` (``activation`` / ``temperature``: see ``integrate_batch``)."""
+        act = self._activation(activation, temperature, "TileMerger.accumulate_single") if activation is not None else None
+        self._accumulate(self._prep(tile.unsqueeze(0)), _coords_xy([coords]), None, N.RED_SUM, act=act)
 
-    def integrate_batch(self, batch: torch.Tensor, crop_coords):
-        """Accumulate ``[B, C, h, w]`` predictions at ``crop_coords[b] = (x, y, w, h)``."""
+    def integrate_batch(self, batch: torch.Tensor, crop_coords, *, activation=None, temperature=1.0):
+        """Accumulate ``[B, C, h, w]`` predictions at ``crop_coords[b] = (x, y, w, h)``.
+
+        ``activation``: None | "sigmoid" | "softmax" (anything else: ValueError), ``temperature``: a finite float.  The call then means the
+        call without them on ``A(batch) = (batch.float() * temperature).sigmoid()`` / ``.softmax(dim=1)``: the logits are read once, where
+        they lie and in their dtype, and activated in registers inside the merge launch (incremental and deferred bands; a deferred merger
+        holds the raw logits) -- no probability tensor is written.  Softmax serves 1 <= C <= 16 (NotImplementedError above), sigmoid any C.
+        A planned-blocks merger degrades to the incremental path; tiles off the 4-pixel grid apply ``A`` with torch ops first."""
+        if activation is not None:
+            return self._integrate_activated(batch, crop_coords, None, N.RED_SUM, activation, temperature, "TileMerger.integrate_batch")
         kind = type(batch)
         # (Tensor.__len__ is a Python function: 0.9 us; on a lazy handle it travels through __torch_function__: 3 us -- the handle knows its length)
         if (batch.shape[0] if kind is torch.Tensor else (batch._len if kind is _lazy.LazyDeaugment else len(batch))) != len(crop_coords):
@@ -745,15 +773,34 @@ class TileMerger:
             return
         self._accumulate(self._prep(batch), _coords_xy(crop_coords), None, N.RED_SUM)
 
-    def integrate_batch_deaugment(self, batch: torch.Tensor, crop_coords, group: str = "d4", reduction="mean"):
+    def _integrate_activated(self, batch, crop_coords, views, code, activation, temperature, what):
+        """``integrate_batch`` / ``integrate_batch_deaugment`` with ``activation=``: always the validated route (the cheap host paths
+        decline such a call)."""
+        act = self._activation(activation, temperature, what)
+        if type(batch) is _lazy.LazyDeaugment:
+            batch = batch._evaluate()      # (the handle is evaluated first: an ordinary batch from here on)
+        n_views = len(views) if views is not None else 1
+        if len(batch) != len(crop_coords) * n_views:
+            raise ValueError("Number of images in batch does not correspond to number of coordinates" + (" x views" if views is not None else ""))
+        self._accumulate(self._prep(batch), _coords_xy(crop_coords), list(views) if views is not None else None, code, act=act)
+
+    def integrate_batch_deaugment(self, batch: torch.Tensor, crop_coords, group: str = "d4", reduction="mean", *, activation=None,
+                                  temperature=1.0):
         """Fused ``integrate_batch(tta.<group>_image_deaugment(batch, reduction), crop_coords)``.
 
         ``batch`` is the model output for the ``<group>_image_augment``-ed tiles, ``[V*B, C, h, w]`` chunk-major.
         One HIP launch reads the V views, applies the inverse transforms on the fly, reduces and blends.
+        ``activation`` / ``temperature``: the fused ``integrate_batch(tta.<group>_image_deaugment(batch, reduction, activation=...), crop_coords)``
+        -- ``A`` is applied to every view before the reduction; see ``integrate_batch``.
         """
         from .tta import DEAUGMENT_VIEWS, _reduction_code
 
         views = DEAUGMENT_VIEWS[group]
+        if activation is not None:
+            code = _reduction_code(reduction)
+            if code is None:
+                raise ValueError(f"reduction={reduction!r} cannot be fused into the tile merge")
+            return self._integrate_activated(batch, crop_coords, views, code, activation, temperature, "TileMerger.integrate_batch_deaugment")
         if type(reduction) is str:
             code = _reduction_code(reduction)
             if code is not None and self._offer_fast(batch, crop_coords, (group, code), views, code):
@@ -887,10 +934,15 @@ class HostBackedTileMerger(TileMerger):
     def reset(self):
         self._host.reset()
 
-    def accumulate_single(self, tile: torch.Tensor, coords):
-        self._host.blend(tile.to(device=self.image.device).unsqueeze(0), [coords])
+    def accumulate_single(self, tile: torch.Tensor, coords, *, activation=None, temperature=1.0):
+        from .tta_3d import apply_activation
 
-    def integrate_batch(self, batch: torch.Tensor, crop_coords):
+        self._host.blend(apply_activation(tile.to(device=self.image.device).unsqueeze(0), activation, temperature), [coords])
+
+    def integrate_batch(self, batch: torch.Tensor, crop_coords, *, activation=None, temperature=1.0):
+        from .tta_3d import apply_activation
+
+        batch = apply_activation(batch, activation, temperature)      # (A in torch ops, then today's code)
         if len(batch) != len(crop_coords):
             raise ValueError("Number of images in batch does not correspond to number of coordinates")
         image = self._host.image
@@ -900,12 +952,15 @@ class HostBackedTileMerger(TileMerger):
             batch = batch.type_as(image)
         self._host.blend(batch, crop_coords)
 
-    def integrate_batch_deaugment(self, batch: torch.Tensor, crop_coords, group: str = "d4", reduction="mean"):
+    def integrate_batch_deaugment(self, batch: torch.Tensor, crop_coords, group: str = "d4", reduction="mean", *, activation=None,
+                                  temperature=1.0):
         from .tta import DEAUGMENT_VIEWS, _image_deaugment
+        from .tta_3d import apply_activation
 
         if len(batch) != len(crop_coords) * len(DEAUGMENT_VIEWS[group]):
             raise ValueError("Number of images in batch does not correspond to number of coordinates x views")
-        self.integrate_batch(_image_deaugment(batch.to(device=self.image.device), group, reduction, lazy=False), crop_coords)
+        batch = apply_activation(batch.to(device=self.image.device), activation, temperature)
+        self.integrate_batch(_image_deaugment(batch, group, reduction, lazy=False), crop_coords)
 
     def merge(self) -> torch.Tensor:
         return self._host.image / self._host.norm_mask

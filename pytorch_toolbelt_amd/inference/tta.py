@@ -130,6 +130,46 @@ def _image_deaugment(image: Tensor, group: str, reduction: MaybeStrOrCallable, l
     return reduction(stack, dim=0) if callable(reduction) else stack
 
 
+def _image_deaugment_activated(image: Tensor, group: str, reduction: MaybeStrOrCallable, activation, temperature) -> Tensor:
+    """``<group>_image_deaugment(A(image), reduction)`` with ``A(y) = (y.float() * temperature).sigmoid()`` / ``.softmax(dim=1)`` (the reference's
+    ``ApplySigmoidTo`` / ``ApplySoftmaxTo`` in front of the de-augmentation), float32 whatever the dtype of ``image``.  A CUDA tensor with a
+    fusable reduction takes ONE launch of ``ptb_deaug_reduce_act`` (``csrc/ptb_tile_activation.hip``): the logits are read where they lie
+    (dense or ``torch.channels_last``; float32 / float16 / bfloat16), activated per view and pixel in registers, and no probability tensor is
+    written; the result is evaluated on the spot (never a lazy handle).  Host tensors, tensors that require grad, callable / None reductions
+    -- and, on CUDA, the shapes the planar vector kernels do not take (tiles off the 4-pixel grid) -- apply ``A`` with torch ops
+    (``tta_3d.apply_activation``) and go on as without it.  The fused softmax serves 1 <= C <= 16 (NotImplementedError above), sigmoid any C."""
+    from .tta_3d import _activation_code, _check_softmax_channels, apply_activation
+
+    act = _activation_code(activation, temperature, f"{group}_image_deaugment")
+    views = DEAUGMENT_VIEWS[group]
+    if image.size(0) % len(views) != 0:
+        raise RuntimeError(f"Input batch size ({image.size(0)}) must be divisible by {len(views)}.")
+    code = _reduction_code(reduction)
+    if code is None and not (callable(reduction) or reduction in {None, "None", "none"}):
+        raise KeyError(f"Unsupported reduction mode {reduction}")
+    if (act != N.ACT_NONE and code is not None and image.is_cuda and image.dim() == 4 and image.dtype in N.DTYPE_CODES
+            and not (image.requires_grad and torch.is_grad_enabled())):
+        if any(v & 1 for v in views) and image.shape[2] != image.shape[3]:
+            raise ValueError(f"Input tensor must have number of rows equal to number of cols. Got input tensor of shape {image.size()}")
+        _check_softmax_channels(act, int(image.shape[1]), f"{group}_image_deaugment")
+        N.require_device(image, f"{group}_image_deaugment")
+        y = image.detach()
+        y = y if N.dense_or_channels_last(y) else y.contiguous()
+        n, C, H, W = y.shape
+        B = n // len(views)
+        out = torch.empty((B, C, H, W), device=y.device, dtype=torch.float32)
+        if out.numel() == 0:
+            return out
+        with N.on_device(y.device):
+            rc = N.load().ptb_deaug_reduce_act(y.data_ptr(), N.DTYPE_CODES[y.dtype] | N.layout_flag(y), out.data_ptr(), len(views), N.int_array(views),
+                                               code, B, C, H, W, act, float(temperature), N.stream_ptr(y.device))
+        N.bump()
+        if rc != N.PTB_EUNSUPPORTED:      # (unsupported: a shape of the scalar kernels -- A in torch ops, then today's call)
+            N.check(rc, "ptb_deaug_reduce_act")
+            return out
+    return _image_deaugment(apply_activation(image, activation, temperature), group, reduction, lazy=False)
+
+
 def _labels_deaugment(logits: Tensor, n: int, reduction: MaybeStrOrCallable, order=None) -> Tensor:
     chunks = split_into_chunks(logits, n)
     if (order is None and logits.is_cuda and n <= 8 and N.batch_layout(logits) == N.LAYOUT_CHANNELS_LAST and logits.dtype in N.DTYPE_CODES
@@ -277,30 +317,45 @@ if not _refcount_probe_works():
     _TEMP_REFS = -1      # (no argument ever counts as a temporary of the call expression)
 
 
-def fliplr_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean") -> Tensor:
+def fliplr_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean", *, activation: Optional[str] = None,
+                           temperature: float = 1.0) -> Tensor:
     """[2B,C,H,W] -> [B,C,H,W] (or the [2,B,C,H,W] stack when reduction is None)."""
     owned = sys.getrefcount(image) <= _TEMP_REFS      # (its own statement: inside the call below `image` already sits on the stack once more)
+    if activation is not None:
+        return _image_deaugment_activated(image, "fliplr", reduction, activation, temperature)
     return _image_deaugment(image, "fliplr", reduction, owned=owned)
 
 
-def flipud_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean") -> Tensor:
+def flipud_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean", *, activation: Optional[str] = None,
+                           temperature: float = 1.0) -> Tensor:
     owned = sys.getrefcount(image) <= _TEMP_REFS      # (its own statement: inside the call below `image` already sits on the stack once more)
+    if activation is not None:
+        return _image_deaugment_activated(image, "flipud", reduction, activation, temperature)
     return _image_deaugment(image, "flipud", reduction, owned=owned)
 
 
-def flips_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean") -> Tensor:
+def flips_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean", *, activation: Optional[str] = None,
+                           temperature: float = 1.0) -> Tensor:
     owned = sys.getrefcount(image) <= _TEMP_REFS      # (its own statement: inside the call below `image` already sits on the stack once more)
+    if activation is not None:
+        return _image_deaugment_activated(image, "flips", reduction, activation, temperature)
     return _image_deaugment(image, "flips", reduction, owned=owned)
 
 
-def d2_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean") -> Tensor:
+def d2_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean", *, activation: Optional[str] = None,
+                           temperature: float = 1.0) -> Tensor:
     owned = sys.getrefcount(image) <= _TEMP_REFS      # (its own statement: inside the call below `image` already sits on the stack once more)
+    if activation is not None:
+        return _image_deaugment_activated(image, "d2", reduction, activation, temperature)
     return _image_deaugment(image, "d2", reduction, owned=owned)
 
 
-def d4_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean") -> Tensor:
+def d4_image_deaugment(image: Tensor, reduction: MaybeStrOrCallable = "mean", *, activation: Optional[str] = None,
+                           temperature: float = 1.0) -> Tensor:
     """[8B,C,N,N] -> [B,C,N,N] (or the [8,B,C,N,N] stack when reduction is None)."""
     owned = sys.getrefcount(image) <= _TEMP_REFS      # (its own statement: inside the call below `image` already sits on the stack once more)
+    if activation is not None:
+        return _image_deaugment_activated(image, "d4", reduction, activation, temperature)
     return _image_deaugment(image, "d4", reduction, owned=owned)
 
 

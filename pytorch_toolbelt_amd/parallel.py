@@ -952,7 +952,14 @@ class ShardedTileMerger:
         if launched and not self._exchanged and self._deferred.all_packed.value:
             self._start_exchange()      # every outgoing rectangle has been written by its launch and packed (in the same C call)
 
-    def integrate_batch(self, batch, crop_coords):
+    @staticmethod
+    def _no_activation(activation, what):
+        if activation is not None:
+            raise NotImplementedError(f"ShardedTileMerger.{what}: activation= is not fused into the sharded merge; apply it yourself -- "
+                                      f"{what}(tta_3d.apply_activation(batch, activation, temperature), ...) -- and call without activation=")
+
+    def integrate_batch(self, batch, crop_coords, *, activation=None, temperature=1.0):
+        self._no_activation(activation, "integrate_batch")
         if len(batch) != len(crop_coords):
             raise ValueError("Number of images in batch does not correspond to number of coordinates")
         from .inference import _lazy
@@ -974,7 +981,8 @@ class ShardedTileMerger:
         self.local.integrate_batch(batch, c)
         self._after_integrate(origins)
 
-    def integrate_batch_deaugment(self, batch, crop_coords, group="d4", reduction="mean"):
+    def integrate_batch_deaugment(self, batch, crop_coords, group="d4", reduction="mean", *, activation=None, temperature=1.0):
+        self._no_activation(activation, "integrate_batch_deaugment")
         if self._deferred is not None:
             from . import _native as N
             from .inference.tta import DEAUGMENT_VIEWS, _reduction_code

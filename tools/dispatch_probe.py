@@ -135,5 +135,27 @@ for scalar in (0, 1):
             call("ptb_volume_plan_upload", plan, p(9), NUL)
             call("ptb_volume_plan_submit_act", plan, i32(0), i32(4), p(1), i64(Cc * 8 * 8 * w), i64(4 * Cc * 8 * 8 * w), i32(dt | cl), i32(nv), arr(i32, list(range(nv))), i32(2), p(8), p(6), i32(act), f32(1.0), NUL)
             L.ptb_volume_plan_destroy(plan)
+    # the activations of ptb_tile_activation.hip: every view set, source type and layout, on and off the 4-pixel grid, at the three chunk
+    # sizes; softmax on both sides of 16 channels, sigmoid beyond them
+    L.ptb_band_plan_submit_act.restype = C.c_int
+    for ch in (16, 32, 64):
+        L.ptb_set_tunable(0, ch)
+        for (vn, v), dt, W, cl, (act, Cc) in it.product(VIEWS.items(), (0, 1, 2), (32, 30), (0, 0x200), ((2, 3), (2, 16), (2, 17), (1, 20), (0, 4))):
+            views = arr(i32, v)
+            call("ptb_deaug_reduce_act", p(1), i32(dt | cl), p(6), i32(len(v)), views, i32(2), i32(2), i32(Cc), i32(W), i32(W), i32(act), f32(1.0), NUL)
+            xs = arr(i64, [0, 16]); ys = arr(i64, [0, 16])
+            call("ptb_deaug_accumulate_act", p(6), p(7), p(8), p(1), i32(dt | cl), i32(len(v)), views, i32(2), xs, ys, i32(2), i32(Cc), i32(W), i32(W), i32(64), i32(64), NUL, i32(0), i32(act), f32(1.0), NUL)
+    L.ptb_set_tunable(0, 32)
+    xs = arr(i64, [0, 16, 0, 16]); ys = arr(i64, [0, 0, 16, 16])
+    for (vn, v), dt, cl, rows, (act, Cc) in it.product(VIEWS.items(), (0, 1, 2), (0, 0x200), (32, 64), ((2, 3), (2, 17), (1, 20))):
+        L.ptb_set_tunable(11, rows)
+        plan = C.c_void_p()
+        nb = L.ptb_band_plan_create(xs, ys, i32(4), i32(Cc), i32(32), i32(32), i32(48), i32(48), i32(1024), i32(0), i32(48), NUL, i32(0), C.byref(plan))
+        shim.ptb_shim_mark(("plan %d rows %d" % (nb, rows)).encode())
+        if nb >= 0 and plan:
+            call("ptb_band_plan_upload", plan, p(9), NUL)
+            call("ptb_band_plan_submit_act", plan, i32(0), i32(4), p(1), i64(Cc * 32 * 32), i64(4 * Cc * 32 * 32), i32(dt | cl), i32(len(v)), arr(i32, v), i32(2), p(6), p(7), p(8), i32(act), f32(1.0), NUL)
+            L.ptb_band_plan_destroy(plan)
+    L.ptb_set_tunable(11, 64)
 L.ptb_set_tunable(1, 0)
 shim.ptb_shim_close()
