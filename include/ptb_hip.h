@@ -834,6 +834,29 @@ int ptb_lovasz_bwd(const float* pred, const int64_t* labels, const float* flabel
                    const float* grad_at_pixel, float* grad, int B, int C, int64_t HW, int mode, int per_image,
                    int has_ignore, int64_t ignore_label, float ignore_value, ptb_stream_t stream);
 
+/* ---- Run-length codec of masks (utils/rle.py:6-39) --------------------------------------------------------------
+ * mask = [B, H, W] contiguous, elem_bytes 1 (bool / uint8), 2, 4 or 8 (signed); N = H*W <= 2^31 - 2 (PTB_EUNSUPPORTED above).
+ * labels = HOST int64[K]: one encoding per (slice, label) with foreground mask == label, encoding index e = slice * K + label index;
+ * K = 0 (labels may be NULL): one encoding per slice with foreground mask != 0.  With f[p] = fg[p % H][p / H] (column-major, the
+ * order of mask.T.flatten()) an encoding lists the maximal runs of f as (start + 1, length) pairs.
+ * Two phases around the caller's one D2H read:
+ *   ptb_rle_count   counts the run boundaries per (encoding, column, 32-row segment) and scans them (launches of their own; no
+ *                   workgroup waits for another); on return (stream order) the first E + 1 int64 of the workspace hold the exclusive
+ *                   offsets of the E = B * max(K, 1) encodings in the concatenated output, the last one the total.
+ *   ptb_rle_write   out = int64[total]: encoding e is out[enc[e] .. enc[e + 1]).  Same mask, labels and workspace as the count call.
+ * workspace = DEVICE buffer of ptb_rle_workspace_bytes(B, K, H, W) bytes (negative: a PTB_E* code), 16-byte aligned. */
+int64_t ptb_rle_workspace_bytes(int B, int K, int H, int W);
+int ptb_rle_count(const void* mask, int elem_bytes, int B, int H, int W, const int64_t* labels, int K, void* workspace,
+                  int64_t workspace_bytes, ptb_stream_t stream);
+int ptb_rle_write(const void* mask, int elem_bytes, int B, int H, int W, const int64_t* labels, int K, void* workspace,
+                  int64_t workspace_bytes, int64_t* out, int64_t total, ptb_stream_t stream);
+/* mask[H, W] (bytes) = 1 where some (start, length) pair of runs (DEVICE int64[2 * pairs], any order, overlapping) covers the pixel,
+ * 0 elsewhere.  Runs are clamped to the mask, so unvalidated runs store nothing out of bounds.  workspace = DEVICE buffer of
+ * ptb_rle_decode_workspace_bytes(H, W) bytes: the column-major image the runs are filled into before it is transposed. */
+int64_t ptb_rle_decode_workspace_bytes(int H, int W);
+int ptb_rle_decode(const int64_t* runs, int64_t pairs, int H, int W, uint8_t* mask, void* workspace, int64_t workspace_bytes,
+                   ptb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

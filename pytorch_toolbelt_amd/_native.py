@@ -174,6 +174,11 @@ SIGNATURES = {
     "ptb_deaug_accumulate_act": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _ip, _c_int, _i64p, _i64p] + [_c_int] * 6 + [_vp, _c_int, _c_int, _c_f, _vp]),
     "ptb_band_plan_submit_act": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_i64, _c_int, _c_int, _ip, _c_int, _vp, _vp, _vp, _c_int, _c_f, _vp]),
     "ptb_volume_plan_submit_act": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_i64, _c_int, _c_int, _ip, _c_int, _vp, _vp, _c_int, _c_f, _vp]),
+    "ptb_rle_workspace_bytes": (_c_i64, [_c_int, _c_int, _c_int, _c_int]),
+    "ptb_rle_count": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _i64p, _c_int, _vp, _c_i64, _vp]),
+    "ptb_rle_write": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _i64p, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "ptb_rle_decode_workspace_bytes": (_c_i64, [_c_int, _c_int]),
+    "ptb_rle_decode": (_c_int, [_vp, _c_i64, _c_int, _c_int, _vp, _vp, _c_i64, _vp]),
 }
 
 _lib = None
