@@ -857,6 +857,25 @@ int64_t ptb_rle_decode_workspace_bytes(int H, int W);
 int ptb_rle_decode(const int64_t* runs, int64_t pairs, int H, int W, uint8_t* mask, void* workspace, int64_t workspace_bytes,
                    ptb_stream_t stream);
 
+/* ---- Confusion matrix of label maps and of logits (no counterpart in the reference) ---------------------------------
+ * out = int64[G, K, K], ADDED to: out[g][t][p] += number of positions of group g with target == t and pred == p.  Values compare after
+ * widening to int64 (elem_bytes 1 = bool / uint8 unsigned, 2 / 4 / 8 signed).  A position whose target equals ignore_index (when
+ * has_ignore) is skipped; any other position whose target or pred lies outside [0, K) is skipped and counted in *invalid (int64,
+ * ADDED to; the caller zeroes it).  1 <= K <= 256 (PTB_EUNSUPPORTED above).  The inputs are read where they lie, once per row block
+ * (ptb_confusion_plan: 1 for K <= 128, up to 4 at K = 256); there is no workspace -- workgroups count in private 32-bit LDS
+ * histograms of lds_bytes <= 64 KiB and flush them with 64-bit integer atomics, so the result is exact and independent of arrival
+ * order.  Every launch is one kernel on `stream`; nothing is read back.
+ *   ptb_confusion_labels   pred, target = [B, n_per_sample] contiguous; G = B (the pooled matrix of a whole tensor is B = 1).
+ *   ptb_confusion_logits   logits = [N, C, S] contiguous in `dtype` (PTB_F32 / PTB_F16 / PTB_BF16), target = [N, S]; C <= 256.
+ *                          C >= 2: K = C, pred = argmax over channels (first maximum wins, NaN counts as the maximum: the rule of
+ *                          ptb_merge_crop's argmax kinds); C == 1: K = 2, pred = logit > threshold (NaN gives 0).
+ *                          per_sample: G = N, else G = 1. */
+int ptb_confusion_plan(int K, int* row_blocks, int* lds_bytes);
+int ptb_confusion_labels(const void* pred, int pred_elem_bytes, const void* target, int target_elem_bytes, int64_t B, int64_t n_per_sample,
+                         int K, int has_ignore, int64_t ignore_index, int64_t* out, int64_t* invalid, ptb_stream_t stream);
+int ptb_confusion_logits(const void* logits, int dtype, int64_t N, int C, int64_t S, float threshold, const void* target, int target_elem_bytes,
+                         int per_sample, int has_ignore, int64_t ignore_index, int64_t* out, int64_t* invalid, ptb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,9 @@ SIGNATURES = {
     "ptb_rle_write": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _i64p, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
     "ptb_rle_decode_workspace_bytes": (_c_i64, [_c_int, _c_int]),
     "ptb_rle_decode": (_c_int, [_vp, _c_i64, _c_int, _c_int, _vp, _vp, _c_i64, _vp]),
+    "ptb_confusion_plan": (_c_int, [_c_int, _ip, _ip]),
+    "ptb_confusion_labels": (_c_int, [_vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _vp, _vp, _vp]),
+    "ptb_confusion_logits": (_c_int, [_vp, _c_int, _c_i64, _c_int, _c_i64, _c_f, _vp, _c_int, _c_int, _c_int, _c_i64, _vp, _vp, _vp]),
 }
 
 _lib = None
