@@ -876,6 +876,35 @@ int ptb_confusion_labels(const void* pred, int pred_elem_bytes, const void* targ
 int ptb_confusion_logits(const void* logits, int dtype, int64_t N, int C, int64_t S, float threshold, const void* target, int target_elem_bytes,
                          int per_sample, int has_ignore, int64_t ignore_index, int64_t* out, int64_t* invalid, ptb_stream_t stream);
 
+/* ---- Connected components of label maps (no counterpart in the reference) -------------------------------------------
+ * labels = [B, D, H, W] contiguous (dims = 2: D == 1), elem_bytes 1 = bool / uint8, 2 / 4 / 8 signed; the B entries are labelled
+ * independently in the same launches.  Two neighbouring positions are in one component iff they hold the same value and that value is
+ * not `background` (has_background = 0: every value is foreground; a background the element type cannot hold occurs nowhere).
+ * connectivity: 4 | 8 (dims = 2), 6 | 26 (dims = 3).  B * D * H * W <= 2^31 - 2 (PTB_EUNSUPPORTED above).  Block-based union-find,
+ * every phase a launch of its own on `stream` (tiles in LDS -> seams by atomicMin on a parent map -> flatten -> scan -> rank); no
+ * workgroup waits for another one, every loop is capped, nothing is read back, and the result is a function of the input alone.
+ *   ptb_cc_plan          host only: tile = {TZ, TY, TX} of phase 1, the tiles and the 1024-position chunks of the call, the levels of
+ *                        the scan over chunks + 1 root counts, and the workspace bytes of ptb_cc_label / ptb_cc_remove_small.
+ *   ptb_cc_label         cc = int32 like labels: 0 at background, else 1 .. n within each entry, numbered in row-major order of each
+ *                        component's first position; count = int64[B] = n, or -1 for an entry in which a step cap was exceeded.
+ *   ptb_cc_remove_small  out (like labels; may be labels) = labels with every component of fewer than min_area positions replaced
+ *                        by fill; an entry in which a step cap was exceeded is copied unchanged.  No scan, no numbering.
+ *   ptb_cc_stats         of ONE entry's cc map and components 1 .. max_components (larger numbers are left out): area =
+ *                        int64[max_components]; bbox = int64[max_components, 2 * dims], minima then exclusive maxima in (z,) y, x
+ *                        order, all zero where area is 0; value[c] (values_elem_bytes each; both NULL: none) = values at a position
+ *                        of component c + 1.  Runs of equal numbers are folded across the wave and the workgroup before the 64-bit
+ *                        integer atomics.
+ * workspace: DEVICE, 16-byte aligned, at least the plan's bytes (PTB_EINVAL otherwise); cc 16-byte aligned. */
+int ptb_cc_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W, int* tile, int64_t* tiles, int64_t* chunks, int* scan_levels,
+                int64_t* label_workspace_bytes, int64_t* remove_workspace_bytes);
+int ptb_cc_label(const void* labels, int elem_bytes, int dims, int64_t B, int64_t D, int64_t H, int64_t W, int connectivity, int has_background,
+                 int64_t background, int32_t* cc, int64_t* count, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+int ptb_cc_remove_small(const void* labels, int elem_bytes, int dims, int64_t B, int64_t D, int64_t H, int64_t W, int connectivity,
+                        int has_background, int64_t background, int64_t min_area, int64_t fill, void* out, void* workspace,
+                        int64_t workspace_bytes, ptb_stream_t stream);
+int ptb_cc_stats(const int32_t* cc, int dims, int64_t D, int64_t H, int64_t W, int64_t max_components, const void* values, int values_elem_bytes,
+                 int64_t* area, int64_t* bbox, void* value, ptb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,10 @@ SIGNATURES = {
     "ptb_confusion_plan": (_c_int, [_c_int, _ip, _ip]),
     "ptb_confusion_labels": (_c_int, [_vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _vp, _vp, _vp]),
     "ptb_confusion_logits": (_c_int, [_vp, _c_int, _c_i64, _c_int, _c_i64, _c_f, _vp, _c_int, _c_int, _c_int, _c_i64, _vp, _vp, _vp]),
+    "ptb_cc_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _ip, _i64p, _i64p, _ip, _i64p, _i64p]),
+    "ptb_cc_label": (_c_int, [_vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
+    "ptb_cc_remove_small": (_c_int, [_vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp]),
+    "ptb_cc_stats": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_int, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

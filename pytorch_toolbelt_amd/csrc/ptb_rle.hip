@@ -21,6 +21,7 @@
 
 #include "ptb_common.h"
 #include "ptb_dispatch.h"
+#include "ptb_scan_device.h"
 
 namespace ptb {
 
@@ -31,8 +32,6 @@ constexpr int RLE_WY = 4;                      // segments (waves) of a workgrou
 constexpr int RLE_ROWS = RLE_SEG * RLE_WY;
 constexpr int RLE_CHUNK = 8;                   // rows whose loads are in flight together
 constexpr int RLE_MAX_LABELS = 16;             // labels of one launch (by-value kernel argument)
-constexpr int SCAN_PER = 8, SCAN_TILE = 256 * SCAN_PER;
-constexpr int SCAN_MAX_LEVELS = 4;             // SCAN_TILE^4 > 2^36 counts
 constexpr long long RLE_MAX_COUNTS = 1LL << 36;
 constexpr long long RLE_MAX_PIXELS = 0x7fffffffLL - 1;
 constexpr int FILL_SHORT = 16;                 // runs up to this length are stored by the lane that read them
@@ -153,53 +152,6 @@ __global__ __launch_bounds__(RLE_LANES * RLE_WY) void rle_pass_kernel(const RleA
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------- scan
-// Sum of one tile of SCAN_TILE values -> sums[tile].
-template <class IN>
-__global__ __launch_bounds__(256) void scan_reduce_kernel(const IN* __restrict__ in, long long m, long long* __restrict__ sums) {
-    __shared__ long long wsum[4];
-    const long long i0 = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_PER;
-    long long t = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_PER; ++j) t += i0 + j < m ? (long long)in[i0 + j] : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) t += __shfl_xor(t, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// Exclusive scan of one tile, plus base[tile] when given.  `out` may be `in` (every lane reads its SCAN_PER values before it writes them).
-template <class IN>
-__global__ __launch_bounds__(256) void scan_tile_kernel(const IN* in, long long m, const long long* __restrict__ base, long long* out) {
-    __shared__ long long wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long i0 = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_PER;
-    long long v[SCAN_PER], t = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_PER; ++j) {
-        v[j] = i0 + j < m ? (long long)in[i0 + j] : 0;
-        t += v[j];
-    }
-    long long inc = t;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long up = __shfl_up(inc, d);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    long long ex = inc - t + (base ? base[blockIdx.x] : 0);
-#pragma unroll
-    for (int w = 0; w < 3; ++w)
-        if (w < wave) ex += wsum[w];
-#pragma unroll
-    for (int j = 0; j < SCAN_PER; ++j) {
-        if (i0 + j < m) out[i0 + j] = ex;
-        ex += v[j];
-    }
-}
-
 // enc[e] = first output entry of encoding e; enc[E] = the total
 __global__ __launch_bounds__(256) void rle_enc_offsets_kernel(const long long* __restrict__ offsets, const unsigned* __restrict__ counts, long long n,
                                                               long long per_enc, long long E, long long* __restrict__ enc) {
@@ -288,11 +240,7 @@ static int make_plan(int B, int K, int H, int W, RlePlan& p) {
     const long long per = (long long)W * p.S;
     if (per > RLE_MAX_COUNTS / p.E) return PTB_EUNSUPPORTED;
     p.n = p.E * per;
-    p.levels = 0;
-    for (long long m = p.n; m > SCAN_TILE;) {
-        m = (m + SCAN_TILE - 1) / SCAN_TILE;
-        p.cnt[p.levels++] = m;
-    }
+    p.levels = scan_levels(p.n, p.cnt);
     long long o = 0;
     p.off_enc = o; o += up16(8 * (p.E + 1));
     p.off_offsets = o; o += up16(8 * p.n);
@@ -358,20 +306,9 @@ extern "C" int ptb_rle_count(const void* mask, int elem_bytes, int B, int H, int
 
     const unsigned* counts = reinterpret_cast<const unsigned*>(ws + p.off_counts);
     long long* offsets = reinterpret_cast<long long*>(ws + p.off_offsets);
-    auto sums = [&](int l) { return reinterpret_cast<long long*>(ws + p.off_sums[l]); };
-    auto tiles = [](long long m) { return dim3((unsigned)((m + SCAN_TILE - 1) / SCAN_TILE)); };
-    if (p.levels == 0) {
-        hipLaunchKernelGGL((scan_tile_kernel<unsigned>), dim3(1), dim3(256), 0, s, counts, p.n, (const long long*)nullptr, offsets);
-    } else {
-        hipLaunchKernelGGL((scan_reduce_kernel<unsigned>), tiles(p.n), dim3(256), 0, s, counts, p.n, sums(0));
-        for (int l = 1; l < p.levels; ++l)
-            hipLaunchKernelGGL((scan_reduce_kernel<long long>), tiles(p.cnt[l - 1]), dim3(256), 0, s, (const long long*)sums(l - 1), p.cnt[l - 1], sums(l));
-        const int top = p.levels - 1;                                                        // (<= SCAN_TILE sums: one workgroup)
-        hipLaunchKernelGGL((scan_tile_kernel<long long>), dim3(1), dim3(256), 0, s, (const long long*)sums(top), p.cnt[top], (const long long*)nullptr, sums(top));
-        for (int l = top - 1; l >= 0; --l)
-            hipLaunchKernelGGL((scan_tile_kernel<long long>), tiles(p.cnt[l]), dim3(256), 0, s, (const long long*)sums(l), p.cnt[l], (const long long*)sums(l + 1), sums(l));
-        hipLaunchKernelGGL((scan_tile_kernel<unsigned>), tiles(p.n), dim3(256), 0, s, counts, p.n, (const long long*)sums(0), offsets);
-    }
+    long long* sums[SCAN_MAX_LEVELS] = {};
+    for (int l = 0; l < p.levels; ++l) sums[l] = reinterpret_cast<long long*>(ws + p.off_sums[l]);
+    scan_exclusive(counts, p.n, p.levels, p.cnt, sums, offsets, s);                          // (ptb_scan_device.h)
     hipLaunchKernelGGL(rle_enc_offsets_kernel, dim3((unsigned)((p.E + 256) / 256)), dim3(256), 0, s, (const long long*)offsets, counts, p.n,
                        (long long)W * p.S, p.E, reinterpret_cast<long long*>(ws + p.off_enc));
     return check_launch();
