@@ -905,6 +905,36 @@ int ptb_cc_remove_small(const void* labels, int elem_bytes, int dims, int64_t B,
 int ptb_cc_stats(const int32_t* cc, int dims, int64_t D, int64_t H, int64_t W, int64_t max_components, const void* values, int values_elem_bytes,
                  int64_t* area, int64_t* bbox, void* value, ptb_stream_t stream);
 
+/* ---- Exact Euclidean distance transform of label maps (no counterpart in the reference) -----------------------------
+ * labels = [B, D, H, W] contiguous (dims = 2: D == 1), elem_bytes 1 = bool / uint8, 2 / 4 / 8 signed, read where it lies; the B entries
+ * are transformed independently in the same launches.  SITES are the positions distances are measured to: the positions that hold
+ * `value` (site_rule PTB_EDT_SITES_EQUAL: value is the background) or that do not hold it (PTB_EDT_SITES_NOT_EQUAL: value is the one
+ * foreground class); a value the element type cannot hold occurs nowhere.  out[p] = the Euclidean distance from p to the nearest site
+ * of its entry, 0 at sites; an entry without a site gets +inf (int32 form: 2^31 - 1).
+ *   spacing       NULL: unit spacing, the passes run on exact int32 squared distances.  Else HOST, three positive finite doubles in
+ *                 z, y, x order (z is ignored for dims = 2): float32 maps, every parabola evaluated in double and rounded once per pass.
+ *   flags         PTB_EDT_SQUARED: the squared distance.  PTB_EDT_SIGNED: out = d(p -> nearest position that is NOT a site) -
+ *                 d(p -> nearest site) (squared: the same sign times d^2): two runs of the passes, the second one with the
+ *                 complementary rule, whose last pass subtracts what the first run left in out.
+ *   out_kind      PTB_EDT_OUT_F32, or PTB_EDT_OUT_I32 (only with PTB_EDT_SQUARED and spacing == NULL: the exact integers).
+ * Passes, each a launch of its own on `stream`: a row pass along W (a wave per row, forward and backward with the last site carried),
+ * then one lower-envelope pass (Meijster) along H and, for dims = 3, along D: a lane per line, the envelope's stack in the workspace.
+ * No workgroup waits for another one, there are no atomics, every loop is capped by the extent of its axis; nothing is read back and
+ * the result is a function of the input alone.  B * D * H * W <= 2^31 - 2 and (dims = 3: D^2 +) H^2 + W^2 <= 2^31 - 2
+ * (PTB_EUNSUPPORTED above), so every squared index distance and every intermediate of the envelope is an int32.
+ * workspace: DEVICE, 16-byte aligned, ptb_edt_plan's bytes: 12 bytes per position (the 32-bit map of the previous axis + two 32-bit
+ * stack words; `out` serves as the other map), + 4 per position for a signed dims = 3 call (the second run must not overwrite out
+ * before its last pass), each rounded up to 16.  out 16-byte aligned. */
+#define PTB_EDT_SITES_EQUAL 0
+#define PTB_EDT_SITES_NOT_EQUAL 1
+#define PTB_EDT_SQUARED 1
+#define PTB_EDT_SIGNED 2
+#define PTB_EDT_OUT_F32 0
+#define PTB_EDT_OUT_I32 1
+int ptb_edt_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W, int is_signed, int64_t* workspace_bytes);
+int ptb_edt(const void* labels, int elem_bytes, int dims, int64_t B, int64_t D, int64_t H, int64_t W, int site_rule, int64_t value,
+            const double* spacing, int flags, void* out, int out_kind, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

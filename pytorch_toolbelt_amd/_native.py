@@ -186,6 +186,8 @@ SIGNATURES = {
     "ptb_cc_label": (_c_int, [_vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
     "ptb_cc_remove_small": (_c_int, [_vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp]),
     "ptb_cc_stats": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_int, _vp, _vp, _vp, _vp]),
+    "ptb_edt_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _i64p]),
+    "ptb_edt": (_c_int, [_vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, ctypes.POINTER(_c_d), _c_int, _vp, _c_int, _vp, _c_i64, _vp]),
 }
 
 _lib = None
