@@ -935,6 +935,38 @@ int ptb_edt_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W, int is_si
 int ptb_edt(const void* labels, int elem_bytes, int dims, int64_t B, int64_t D, int64_t H, int64_t W, int site_rule, int64_t value,
             const double* spacing, int flags, void* out, int out_kind, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Surface metrics of two label maps (no counterpart in the reference) ---------------------------------------------
+ * pred, truth = [B, D, H, W] contiguous label maps (dims = 2: D == 1), each with its own elem_bytes (1 = bool / uint8, 2 / 4 / 8
+ * signed), read where they lie.  Object k of an entry is, with PTB_SURFACE_CLASSES, the positions that hold class_values[k] (HOST, K
+ * values) and, with PTB_SURFACE_NOT_BACKGROUND (K == 1), the positions that do not hold class_values[0]; a value the element type
+ * cannot hold occurs nowhere.  The SURFACE of an object: its positions with a `connectivity`-neighbour (4 / 8, dims = 3: 6 / 26) that
+ * is not in it or lies outside the map.  The directed sample set pred -> truth: the Euclidean distance of every surface position of
+ * pred's object to the nearest surface position of truth's object; truth -> pred is the mirror.  Results, obj = b * K + k, all DEVICE:
+ *   surface_count [obj][2] int64; directed_hausdorff [obj][2], hausdorff [obj], directed_percentile [obj][2], hausdorff_percentile [obj]
+ *   (the percentile of the two sets pooled), mean_surface_distance [obj][2], assd [obj], surface_dice [obj][T]: float32.
+ * A direction without samples gives nan; both surfaces empty: nan in the symmetric results; exactly one empty: inf in hausdorff,
+ * hausdorff_percentile and assd and 0 in surface_dice.  percentile in [0, 100], interpolated linearly between the order statistics
+ * at (n - 1) * percentile / 100; tolerances: HOST, 1 <= T <= 8 values >= 0; spacing: as ptb_edt (NULL: exact int32 squared distances).
+ * Per chunk of classes_per_chunk classes: a border kernel per side, ONE ptb_edt over the [chunk * 2 * B] border maps, a sample kernel
+ * (maxima, tolerance counts, per-workgroup partial sums in double, first histogram), three more histogram passes of a radix select
+ * with a pick kernel after each, and a pass for the upper order statistic; then one finishing kernel.  Stream-ordered, nothing is
+ * read back, no workgroup waits for another one, every loop is bounded by the shape; the result is a function of the inputs alone and
+ * does not depend on the chunking.
+ * ptb_surface_plan: the largest chunk (at most 32 classes) whose workspace stays within max_workspace_bytes and whose transform stays
+ * within 2^31 - 2 positions.  min_workspace_bytes (written whenever the shape is supported) is the workspace of one class per chunk;
+ * PTB_EINVAL when max_workspace_bytes is below it, PTB_EUNSUPPORTED when 2 * B * D * H * W or the squared extents pass 2^31 - 2.
+ * partial_sums_per_map: the workgroups of the sample kernel per map, a function of D * H * W alone.
+ * workspace: DEVICE, 16-byte aligned, workspace_bytes as planned (ptb_surface_metrics plans again with workspace_bytes as the cap). */
+#define PTB_SURFACE_CLASSES 0
+#define PTB_SURFACE_NOT_BACKGROUND 1
+int ptb_surface_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W, int K, int64_t max_workspace_bytes, int* classes_per_chunk,
+                     int64_t* workspace_bytes, int64_t* min_workspace_bytes, int* partial_sums_per_map);
+int ptb_surface_metrics(const void* pred, int pred_elem_bytes, const void* truth, int truth_elem_bytes, int dims, int64_t B, int64_t D, int64_t H,
+                        int64_t W, const int64_t* class_values, int K, int object_rule, int connectivity, const double* spacing, double percentile,
+                        const double* tolerances, int T, int64_t* surface_count, float* directed_hausdorff, float* hausdorff,
+                        float* directed_percentile, float* hausdorff_percentile, float* mean_surface_distance, float* assd, float* surface_dice,
+                        void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,3 +4,4 @@ from .rle import *  # noqa: F401,F403
 from .metrics import *  # noqa: F401,F403
 from .components import *  # noqa: F401,F403
 from .distance import *  # noqa: F401,F403
+from .surface import *  # noqa: F401,F403
