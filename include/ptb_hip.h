@@ -967,6 +967,43 @@ int ptb_surface_metrics(const void* pred, int pred_elem_bytes, const void* truth
                         float* directed_percentile, float* hausdorff_percentile, float* mean_surface_distance, float* assd, float* surface_dice,
                         void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Overlap table, IoU matching and panoptic quality of two instance maps (no counterpart in the reference) ---------
+ * pred, truth = int32 instance maps of `positions` elements each, contiguous, compared position by position (any shape is one entry),
+ * read where they lie (16-byte loads when both bases are 16-byte aligned, element loads otherwise and for the tail).  Ids 1 .. n_pred /
+ * 1 .. n_truth are instances; an id <= 0 or above that side's n is background.  1 <= positions <= 2^31 - 2, n_pred, n_truth <=
+ * 2^31 - 2, max_pairs <= 2^28 (PTB_EUNSUPPORTED above).  A PAIR is a (pred id, truth id) that occurs at some position, both >= 1.
+ *   ptb_inst_plan      host only: the slots of the global table (the power of two >= 2 * max_pairs, at least 2), the workspace bytes
+ *                      and the layout of the output block: out_offsets[17] = byte offsets, each a multiple of 16, of
+ *                        0 num_pairs int64      1 pred_area int64[n_pred]   2 truth_area int64[n_truth]
+ *                        3 pairs int32[rows][2] 4 intersection int64[rows]                       (rows = max_pairs; T >= 1: 0)
+ *                        5 pred_match int32[n_pred]  6 truth_match int32[n_truth]  7 pred_iou double[n_pred]  8 truth_iou double[n_truth]
+ *                        9 tp  10 fp  11 fn  int64[KK][T];  12 sum_iou  13 sq  14 rq  15 pq  16 ap  double[KK][T]   (KK = max(K, 1))
+ *                      T = 0 plans ptb_inst_overlaps (K must be 0), T = 1 .. 16 ptb_inst_match with K classes (0: none; <= 65535).
+ *                      workspace = 16 + up16(8 S) + up16(4 S) [key, count] + up16(4 S) [first position] with S slots, plus
+ *                        overlaps: W = ceil(positions / 32) bitmap words: up16(4 W) + up16(4 (W + 1)) + up16(8 (W + 1)) + the scan's sums;
+ *                        match: (up16(4 x) + up16(8 x)) with x = ceil(n_pred / 1024) * KK * T, + up16(4 ceil(n_pred / 1024) KK)
+ *                        + up16(4 ceil(n_truth / 1024) KK).
+ *   ptb_inst_overlaps  rows in the order of each pair's FIRST position (row-major); rows past the real count stay zero.
+ *   ptb_inst_match     thresholds: HOST, 1 <= T <= 16 increasing doubles in [0.5, 1).  A pair matches at tau iff
+ *                      IoU = I / (A_p + A_t - I) > tau (one double division of exact integers) and, with classes (pred_class[n_pred],
+ *                      truth_class[n_truth], DEVICE, elem bytes 1 = bool / uint8, 2 / 4 / 8 signed; K >= 1), both classes are equal and
+ *                      in 0 .. K - 1.  pred_match / truth_match / pred_iou / truth_iou: the partner at thresholds[0] and its IoU, 0 if
+ *                      none.  Present = area > 0 (with classes: and of that class).  tp = matches, fp = present preds - tp, fn =
+ *                      present truths - tp, sum_iou = sum of the matched IoUs (partial sums per 1024 predictions from a fixed tree,
+ *                      added in block order), sq = sum_iou / tp, rq = tp / (tp + fp / 2 + fn / 2), pq = sum_iou / (tp + fp / 2 + fn / 2),
+ *                      ap = tp / (tp + fp + fn); nan where the denominator is 0.
+ * num_pairs = the number of distinct pairs, or -1 iff the input has more than max_pairs of them (then every score is nan and the other
+ * outputs are unspecified).  The whole output block is zeroed first.  Stream-ordered; nothing is read back; no workgroup waits for
+ * another one; every probe loop is capped at its table's slot count; the result is a function of the inputs alone.
+ * out, workspace: DEVICE, 16-byte aligned, at least the plan's bytes (PTB_EINVAL otherwise). */
+int ptb_inst_plan(int64_t positions, int64_t n_pred, int64_t n_truth, int64_t max_pairs, int T, int64_t K, int64_t* slots, int64_t* workspace_bytes,
+                  int64_t* out_offsets, int64_t* out_bytes);
+int ptb_inst_overlaps(const int32_t* pred, const int32_t* truth, int64_t positions, int64_t n_pred, int64_t n_truth, int64_t max_pairs, void* out,
+                      int64_t out_bytes, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+int ptb_inst_match(const int32_t* pred, const int32_t* truth, int64_t positions, int64_t n_pred, int64_t n_truth, int64_t max_pairs,
+                   const double* thresholds, int T, const void* pred_class, int pred_class_elem_bytes, const void* truth_class,
+                   int truth_class_elem_bytes, int64_t K, void* out, int64_t out_bytes, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,10 @@ SIGNATURES = {
     "ptb_surface_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _ip, _i64p, _i64p, _ip]),
     "ptb_surface_metrics": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, ctypes.POINTER(_c_d), _c_d,
                                      ctypes.POINTER(_c_d), _c_int] + [_vp] * 8 + [_vp, _c_i64, _vp]),
+    "ptb_inst_plan": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _i64p, _i64p, _i64p, _i64p]),
+    "ptb_inst_overlaps": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "ptb_inst_match": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_d), _c_int, _vp, _c_int, _vp, _c_int, _c_i64, _vp, _c_i64,
+                                _vp, _c_i64, _vp]),
 }
 
 _lib = None
