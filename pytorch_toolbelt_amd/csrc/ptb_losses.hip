@@ -940,6 +940,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((PIX == 4 &
                     for (int k = 0; k < PIX; ++k) if (G.ok && !G.ign[k]) {
                         const float p = fexp(xv[k] - mx[k]) * inv[k];
                         const float t = a.labels ? (G.lab[k] == c ? 1.f : 0.f) : tv[k];
+                        if (!a.labels && ignf && t == a.ignore_value) continue;   // a dense target masks single elements: p * mask, t * mask
                         dot[k] += (gI[c] * t + gP[c]) * p;
                     }
                 }
@@ -955,12 +956,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((PIX == 4 &
                     const float t = a.labels ? (G.lab[k] == c ? 1.f : 0.f) : tv[k];
                     bool ig = G.ign[k];
                     if (!a.labels && ignf && t == a.ignore_value) ig = true;
-                    if (!ig) {
-                        const float Gc = gI[c] * t + gP[c];
-                        if (a.prob == PROB_SOFTMAX) out[k] = fexp(xv[k] - mx[k]) * inv[k] * (Gc - dot[k]);
-                        else if (a.prob == PROB_SIGMOID) { const float p = sigmoid_parts(xv[k]).p; out[k] = Gc * p * (1.f - p); }
-                        else out[k] = Gc;
-                    }
+                    // an ignored element of a dense target still moves the other classes of its pixel through the softmax
+                    // denominator: G_c = 0, not gradient 0 (an ignored label masks the whole pixel: dot = 0 as well)
+                    const float Gc = ig ? 0.f : gI[c] * t + gP[c];
+                    if (a.prob == PROB_SOFTMAX) out[k] = fexp(xv[k] - mx[k]) * inv[k] * (Gc - dot[k]);
+                    else if (a.prob == PROB_SIGMOID) { const float p = sigmoid_parts(xv[k]).p; out[k] = Gc * p * (1.f - p); }
+                    else out[k] = Gc;
                 }
                 store_px_nt<PIX>(grad + base + (long long)c * a.HW, out, G.ok);
             }
