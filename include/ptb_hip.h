@@ -935,6 +935,41 @@ int ptb_edt_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W, int is_si
 int ptb_edt(const void* labels, int elem_bytes, int dims, int64_t B, int64_t D, int64_t H, int64_t W, int site_rule, int64_t value,
             const double* spacing, int flags, void* out, int out_kind, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Nearest-site feature transform and label expansion (no counterpart in the reference) ----------------------------
+ * labels, elem_bytes, dims, B, D, H, W, site_rule, value, spacing: as ptb_edt, with the same limits.  One entry point; `flags` says
+ * what it leaves, any combination that asks for something (PTB_EINVAL for none, for an unknown bit, for PTB_NEAREST_MAX_SQ without
+ * PTB_NEAREST_GATHER, and when a pointer below is set without its flag or missing with it):
+ *   PTB_NEAREST_INDEX    index_out [B, D, H, W] int32: the linear index (z * H + y) * W + x, within the position's own entry, of the
+ *                        nearest site; a site gets its own index; -1 everywhere in an entry without a site.  Among the sites at the
+ *                        minimum distance the one with the SMALLEST index: every pass prefers the smaller coordinate of its axis on a
+ *                        tie and the axes are passed from the fastest to the slowest.  With spacing the maps are float32 (as ptb_edt):
+ *                        the rule holds with respect to the stored values, bit for bit wherever they are exact.
+ *   PTB_NEAREST_SQUARED  squared_out [B, D, H, W]: the squared distance to that site, int32 with spacing == NULL (2^31 - 1 without a
+ *                        site) and float32 otherwise (+inf): the bits of ptb_edt with PTB_EDT_SQUARED on the same arguments.
+ *   PTB_NEAREST_GATHER   label expansion.  labels are the markers, site_rule must be PTB_EDT_SITES_NOT_EQUAL and value the background:
+ *                        the labelled positions are the sites.  gather_out [B, D, H, W] of elem_bytes: a labelled position keeps its
+ *                        value; another one takes the value at its nearest labelled position if (mask == NULL or mask[p] != 0) and
+ *                        (without PTB_NEAREST_MAX_SQ, or its squared distance <= max_sq), else `value`.  gather_out must not overlap
+ *                        labels.  mask: [B, D, H, W] bytes.
+ *   PTB_NEAREST_MAX_SQ   max_sq >= 0 limits the expansion.  spacing == NULL: the kernel compares int32 with (int)max_sq, clipped to
+ *                        2^31 - 1 -- pass floor(distance^2); otherwise the float32 squared distance, widened, with max_sq in double.
+ * Launches on `stream`: the row pass, a line pass along H and for dims = 3 along D (the passes of ptb_edt, each carrying a second
+ * 32-bit map with the site), then for PTB_NEAREST_GATHER one gather kernel.  No workgroup waits for another one, there are no
+ * atomics, every loop is capped by the extent of its axis; nothing is read back and the result is a function of the inputs alone.
+ * workspace: DEVICE, 16-byte aligned, ptb_nearest_plan's bytes for the same shape and flags.  Per position: 8 (the two 32-bit stack
+ * words) + 4 per distance map + 4 per feature map that is not a caller's tensor.  There are two maps of each kind (a pass never reads
+ * the map it writes); the one the last pass writes is index_out / squared_out where given, and the last distance map of a dims = 2
+ * call does not exist when nobody reads it.  So: INDEX 16 (dims = 3: 20), INDEX | SQUARED 16, GATHER 20 (dims = 3: 24),
+ * GATHER | MAX_SQ 24; each map rounded up to 16 bytes.  index_out, squared_out and gather_out 16-byte aligned. */
+#define PTB_NEAREST_INDEX 1
+#define PTB_NEAREST_SQUARED 2
+#define PTB_NEAREST_GATHER 4
+#define PTB_NEAREST_MAX_SQ 8
+int ptb_nearest_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W, int flags, int64_t* workspace_bytes);
+int ptb_nearest(const void* labels, int elem_bytes, int dims, int64_t B, int64_t D, int64_t H, int64_t W, int site_rule, int64_t value,
+                const double* spacing, int flags, int32_t* index_out, void* squared_out, void* gather_out, const void* mask, double max_sq,
+                void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+
 /* ---- Surface metrics of two label maps (no counterpart in the reference) ---------------------------------------------
  * pred, truth = [B, D, H, W] contiguous label maps (dims = 2: D == 1), each with its own elem_bytes (1 = bool / uint8, 2 / 4 / 8
  * signed), read where they lie.  Object k of an entry is, with PTB_SURFACE_CLASSES, the positions that hold class_values[k] (HOST, K

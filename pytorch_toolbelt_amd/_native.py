@@ -188,6 +188,9 @@ SIGNATURES = {
     "ptb_cc_stats": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_int, _vp, _vp, _vp, _vp]),
     "ptb_edt_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _i64p]),
     "ptb_edt": (_c_int, [_vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, ctypes.POINTER(_c_d), _c_int, _vp, _c_int, _vp, _c_i64, _vp]),
+    "ptb_nearest_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _i64p]),
+    "ptb_nearest": (_c_int, [_vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, ctypes.POINTER(_c_d), _c_int, _vp, _vp, _vp, _vp, _c_d,
+                             _vp, _c_i64, _vp]),
     "ptb_surface_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _ip, _i64p, _i64p, _ip]),
     "ptb_surface_metrics": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, ctypes.POINTER(_c_d), _c_d,
                                      ctypes.POINTER(_c_d), _c_int] + [_vp] * 8 + [_vp, _c_i64, _vp]),

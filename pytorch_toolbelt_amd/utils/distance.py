@@ -1,6 +1,6 @@
 """Exact Euclidean distance transform of label maps, on the device the tensors are on: the step behind ``merge_crop(argmax=True)`` and
 ``connected_components`` that boundary / distance-map losses (the signed distance of the ground truth), the splitting of touching
-instances (seeds are the maxima of the interior distance) and every surface metric need.
+instances (seeds are the maxima of the interior distance; ``utils/nearest.py`` grows them back) and every surface metric need.
 
 The reference has no counterpart, so the names and meanings below are this library's; ``scipy.ndimage.distance_transform_edt`` is
 the yardstick.  CUDA tensors run the HIP kernels of ``csrc/ptb_distance.hip`` (a missing kernel is an error, never a silent host
