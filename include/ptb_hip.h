@@ -1039,6 +1039,53 @@ int ptb_inst_match(const int32_t* pred, const int32_t* truth, int64_t positions,
                    const double* thresholds, int T, const void* pred_class, int pred_class_elem_bytes, const void* truth_class,
                    int truth_class_elem_bytes, int64_t K, void* out, int64_t out_bytes, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Distance-map losses: boundary loss and Hausdorff-DT loss (no counterpart in the reference) ----------------------
+ * logits = fp32 [B, C, S], S = (D *) H * W positions; the target is labels int64 [B, S] or dense fp32 [B, C, S] (object: > 0.5), exactly
+ * one of them; prob = PTB_PROB_* turns logits into p.  K maps per sample: classes HOST int[K], distinct channels in [0, C), together with
+ * class_table DEVICE int[K + C] (the K channels, then for every channel its map or -1); both NULL: K == C, map k is channel k.
+ * has_ignore: positions that hold ignore_label (elements of dense equal to ignore_value) belong to no object, add nothing and are not
+ * counted.  A MAP is the signed distance ptb_edt leaves for the object as non-sites (> 0 outside, < 0 inside), [B, K, S]:
+ * PTB_DLOSS_MAPS_I32_SQUARED (sign * d^2, unit spacing) or PTB_DLOSS_MAPS_F32 (the distance).  An infinite value (+-inf, +-(2^31 - 1): an
+ * entry whose object is empty or fills it) counts as 0.
+ *   ptb_dloss_plan   host only.  The planes * B * K object maps are transformed in chunks of neighbouring ENTRIES (an entry is one [S] map;
+ *                    classes are not contiguous in [R, B, K, S], entries are), one ptb_edt call each: the largest chunk whose ptb_edt
+ *                    workspace (signed) stays within max_workspace_bytes and whose positions stay within 2^31 - 2, a multiple of
+ *                    4 / gcd(S, 4) unless it is everything (a chunk's output starts 16-byte aligned).  min_workspace_bytes: the smallest
+ *                    accepted cap (PTB_EINVAL below it).  partial_slots: the workgroups of ptb_dloss_fwd, B * ceil(S / 1024).
+ *   ptb_dloss_masks  one launch writes the uint8 object maps [R, B, K, S]: PTB_DLOSS_PLANE_TRUTH (labels == class_k / dense > 0.5; logits
+ *                    may be NULL when it is the only plane) and / or PTB_DLOSS_PLANE_PRED (p_k > 0.5), the truth first.
+ *   ptb_dloss_fwd    PTB_DLOSS_BOUNDARY: term = p_k * phi_k.  PTB_DLOSS_HAUSDORFF: term = (p_k - g_k)^2 * (|phi_pred,k|^alpha +
+ *                    |phi_truth,k|^alpha), g the 0 / 1 target; alpha == 2 on squared maps takes no root.  pred_maps NULL for the boundary
+ *                    loss.  loss[r] = sum of the terms / number of (map, position) elements that are not ignored, over everything
+ *                    (per_sample = 0, one result) or per sample (B results); inv_count[r] = 1 / that number.  No atomics: every
+ *                    workgroup writes an fp64 sum and an int64 count to its slot of the workspace (16 bytes per slot, 16-byte aligned),
+ *                    a second kernel adds the slots of a result in index order.  error_flag DEVICE int: zeroed, then set by a label
+ *                    outside [0, C) that is not ignore_label, which also turns the loss into NaN.
+ *   ptb_dloss_bwd    grad [B, C, S] = coef[r] * d(sum of the terms) / d logits; coef DEVICE float[1] (float[B] with per_sample):
+ *                    upstream gradient times inv_count.  The maps are constants.  Zeros at ignored positions.
+ * Stream-ordered, nothing is read back; the grids depend on the shape alone and the result is a function of the inputs alone.  16-byte
+ * loads where S % 4 == 0 and the bases are 16-byte aligned (masks: 4), element accesses otherwise.  PTB_EINVAL before any launch for
+ * null pointers, K < 1, K > C, a class outside [0, C) or named twice, a misaligned or short workspace, alpha <= 0. */
+#define PTB_DLOSS_BOUNDARY 0
+#define PTB_DLOSS_HAUSDORFF 1
+#define PTB_DLOSS_PLANE_TRUTH 1
+#define PTB_DLOSS_PLANE_PRED 2
+#define PTB_DLOSS_MAPS_I32_SQUARED 0
+#define PTB_DLOSS_MAPS_F32 1
+int ptb_dloss_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W, int K, int planes, int64_t max_workspace_bytes,
+                   int64_t* entries_per_chunk, int64_t* workspace_bytes, int64_t* min_workspace_bytes, int64_t* partial_slots);
+int ptb_dloss_masks(const float* logits, const int64_t* labels, const float* dense, const int* classes, const int* class_table, int planes,
+                    int B, int C, int K, int64_t S, int prob, int has_ignore, int64_t ignore_label, float ignore_value, uint8_t* masks,
+                    ptb_stream_t stream);
+int ptb_dloss_fwd(int kind, const float* logits, const int64_t* labels, const float* dense, const int* classes, const int* class_table,
+                  const void* truth_maps, const void* pred_maps, int maps_kind, int B, int C, int K, int64_t S, int prob, int has_ignore,
+                  int64_t ignore_label, float ignore_value, float alpha, int per_sample, void* workspace, int64_t workspace_bytes,
+                  float* loss, float* inv_count, int* error_flag, ptb_stream_t stream);
+int ptb_dloss_bwd(int kind, const float* logits, const int64_t* labels, const float* dense, const int* classes, const int* class_table,
+                  const void* truth_maps, const void* pred_maps, int maps_kind, int B, int C, int K, int64_t S, int prob, int has_ignore,
+                  int64_t ignore_label, float ignore_value, float alpha, int per_sample, const float* coef, float* grad,
+                  ptb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,12 @@ SIGNATURES = {
     "ptb_inst_overlaps": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp]),
     "ptb_inst_match": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_d), _c_int, _vp, _c_int, _vp, _c_int, _c_i64, _vp, _c_i64,
                                 _vp, _c_i64, _vp]),
+    "ptb_dloss_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _i64p, _i64p, _i64p, _i64p]),
+    "ptb_dloss_masks": (_c_int, [_vp, _vp, _vp, _ip, _vp, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_f, _vp, _vp]),
+    "ptb_dloss_fwd": (_c_int, [_c_int, _vp, _vp, _vp, _ip, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_f, _c_f,
+                               _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp]),
+    "ptb_dloss_bwd": (_c_int, [_c_int, _vp, _vp, _vp, _ip, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_f, _c_f,
+                               _c_int, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -2,6 +2,7 @@
 from .balanced_bce import *  # noqa: F401,F403
 from .bitempered_loss import *  # noqa: F401,F403
 from .dice import *  # noqa: F401,F403
+from .distance_losses import *  # noqa: F401,F403
 from .focal import *  # noqa: F401,F403
 from .focal_cosine import *  # noqa: F401,F403
 from .functional import *  # noqa: F401,F403

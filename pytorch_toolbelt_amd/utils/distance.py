@@ -15,7 +15,7 @@ import torch
 from .. import _native as N
 from .components import _ELEM_BYTES, MAX_POSITIONS, _check_int, _fits
 
-__all__ = ["distance_transform"]
+__all__ = ["distance_transform", "class_distance_maps"]
 
 MAX_SQUARED = (1 << 31) - 2          # D^2 + H^2 + W^2 of one call: every squared index distance is an int32
 INT_INF = (1 << 31) - 1              # the int32 form of "no site in this entry"
@@ -23,6 +23,8 @@ _SITES_EQUAL, _SITES_NOT_EQUAL = 0, 1
 _SQUARED, _SIGNED = 1, 2
 _OUT_F32, _OUT_I32 = 0, 1
 _HOST_INF = 1 << 62
+PLANE_TRUTH, PLANE_PRED = 1, 2       # PTB_DLOSS_PLANE_*
+DEFAULT_WORKSPACE_CAP = 4 << 30
 
 
 # ---------------------------------------------------------------------------------------------------------------- validation
@@ -190,3 +192,151 @@ def distance_transform(labels, background=0, foreground=None, dims=2, spacing=No
     if res is not out:
         out.copy_(res)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- per-class signed maps
+_table_cache = {}
+
+
+def class_table(what, classes, C, device=None):
+    """``(K, classes tuple | None, host int array | None, device int32 [K + C] | None)`` of a class selection: the channel of every map, then
+    for every channel its map or -1.  ``classes=None`` is all ``C`` channels in order and needs no table.  The device copy is made once
+    per (classes, C, device), not per call."""
+    if classes is None:
+        return C, None, None, None
+    try:
+        cls = tuple(_check_int(what, "classes", int(c) if isinstance(c, torch.Tensor) else c) for c in classes)
+    except TypeError:
+        raise TypeError(f"{what}: classes must be None or a sequence of ints, got {classes!r}") from None
+    if not cls:
+        raise ValueError(f"{what}: classes must name at least one class")
+    if len(set(cls)) != len(cls):
+        raise ValueError(f"{what}: classes must be distinct, got {list(cls)}")
+    if min(cls) < 0 or max(cls) >= C:
+        raise ValueError(f"{what}: classes must lie in [0, {C}), got {list(cls)}")
+    host = N.int_array(list(cls))
+    if device is None or device.type != "cuda":
+        return len(cls), cls, host, None
+    key = (cls, C, str(device))
+    dev = _table_cache.get(key)
+    if dev is None:
+        slot = [-1] * C
+        for k, c in enumerate(cls):
+            slot[c] = k
+        if len(_table_cache) > 64:
+            _table_cache.clear()
+        dev = _table_cache[key] = torch.tensor(list(cls) + slot, dtype=torch.int32).to(device)
+    return len(cls), cls, host, dev
+
+
+def plan_maps(what, lib, dims, B, D, H, W, K, planes, cap):
+    """``(entries per chunk, workspace bytes, partial slots)`` of ``ptb_dloss_plan``"""
+    chunk, nbytes, least, slots = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    rc = lib.ptb_dloss_plan(dims, B, D, H, W, K, planes, cap, ctypes.byref(chunk), ctypes.byref(nbytes), ctypes.byref(least), ctypes.byref(slots))
+    if rc == -1 and least.value > cap:
+        raise ValueError(f"{what}: max_workspace_bytes={cap} is below the {least.value} bytes the transform of the smallest chunk of maps takes")
+    if rc == N.PTB_EUNSUPPORTED:
+        raise ValueError(f"{what}: a sample of {D * H * W} positions (or its squared extents) passes what one transform takes, 2^31 - 2")
+    N.check(rc, what)
+    return chunk.value, nbytes.value, slots.value
+
+
+def signed_maps_device(what, x, labels, dense, C, table, planes, prob, has_ignore, ignore_label, ignore_value, dims, D, H, W, sp, squared, cap):
+    """The signed maps ``[R, B, K, S]`` of the object maps one ``ptb_dloss_masks`` launch writes -- the truth plane, the thresholded
+    prediction, or both (``planes``) -- by one ``ptb_edt`` call per chunk of entries.  ``x`` fp32 ``[B, C, S]`` (None for the truth plane
+    alone); exactly one of ``labels`` int64 ``[B, S]`` / ``dense`` fp32 ``[B, C, S]``; ``C`` channels.  int32 with ``squared`` and unit spacing.  ``(maps, chunks)``."""
+    lib = N.load()
+    K, _, host, dev_table = table
+    src = labels if labels is not None else dense
+    B, S = src.shape[0], src.shape[-1]
+    R = (planes & 1) + (planes >> 1)
+    chunk, nbytes, _ = plan_maps(what, lib, dims, B, D, H, W, K, R, cap)
+    E = R * B * K
+    device = src.device
+    as_int = squared and sp is None
+    with N.on_device(device):
+        masks = torch.empty(E * S, dtype=torch.uint8, device=device)
+        maps = torch.empty((R, B, K, S), dtype=torch.int32 if as_int else torch.float32, device=device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        stream = N.stream_ptr(device)
+        N.bump()
+        N.check(lib.ptb_dloss_masks(x.data_ptr() if x is not None else None, labels.data_ptr() if labels is not None else None,
+                                    dense.data_ptr() if dense is not None else None, host, dev_table.data_ptr() if dev_table is not None else None,
+                                    planes, B, C, K, S, prob, int(has_ignore), ignore_label, ignore_value, masks.data_ptr(), stream), what)
+        spacing = (ctypes.c_double * 3)(*sp) if sp is not None else None
+        flags = _SIGNED | (_SQUARED if squared else 0)
+        chunks = 0
+        for e0 in range(0, E, chunk):
+            n = min(chunk, E - e0)
+            N.bump()
+            N.check(lib.ptb_edt(masks.data_ptr() + e0 * S, 1, dims, n, D, H, W, _SITES_EQUAL, 0, spacing, flags, maps.data_ptr() + 4 * e0 * S,
+                                _OUT_I32 if as_int else _OUT_F32, ws.data_ptr(), nbytes, stream), what)
+            chunks += 1
+    return maps, chunks
+
+
+def signed_maps_host(objects, sp, squared):
+    """The same maps of the boolean numpy array ``objects`` ``[E, D, H, W]``: what ``distance_transform(signed=True)`` gives with the
+    positions outside an object as its sites"""
+    E, D, H, W = objects.shape
+    return _host(torch.from_numpy(np.ascontiguousarray(objects).astype(np.uint8)), E, D, H, W, True, 0, sp, squared, True)
+
+
+def class_distance_maps(labels, num_classes=None, classes=None, dims=2, spacing=None, ignore_index=None, squared=False,
+                        max_workspace_bytes=DEFAULT_WORKSPACE_CAP):
+    """The SIGNED distance map of every class of a batch of label maps: what the distance-map losses (``losses.BoundaryLoss``,
+    ``losses.HausdorffDTLoss``) take as ``dist_maps=`` -- computed once per dataset, on the device, instead of once per step.
+
+    ``labels``: an integer tensor ``[B, H, W]`` (``dims=2``) or ``[B, D, H, W]`` (``dims=3``).  The K maps of a sample are those of
+    ``classes`` (distinct ints in ``[0, num_classes)``, in that order), or of all ``num_classes`` classes; ``num_classes=None`` takes
+    ``max(classes) + 1``.  Returns ``[B, K, *spatial]``: map ``k`` is ``distance_transform(labels, foreground=classes[k], signed=True,
+    spacing=..., squared=...)``, bit for bit -- positive outside the object, negative inside (the boundary positions inside hold -1, not
+    0), float32, or exact int32 with ``squared=True`` and unit spacing.  Positions that hold ``ignore_index`` belong to no class.
+
+    THE INFINITIES STAY: a sample without class ``k`` has ``+inf`` (int32: 2^31 - 1) in all of map ``k``, a sample that is class ``k``
+    everywhere ``-inf``.  The losses count such a map as 0 (it has no boundary); anything else that reads the maps must decide itself.
+
+    One launch writes all ``B * K`` object maps (uint8), then one distance transform runs per chunk of them; the chunks keep the
+    transform's workspace (12 bytes per position, 16 for ``dims=3``) within ``max_workspace_bytes`` and change no bit.  Stream-ordered,
+    nothing is read back.  CPU tensors take the numpy form with the same results.  For the losses pass ``squared=True`` with unit
+    spacing (the exact integers they use internally) and the distances themselves with ``spacing``."""
+    what = "class_distance_maps"
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in _ELEM_BYTES:
+        raise TypeError(f"{what}: labels must be an integer tensor (bool, uint8, int16, int32 or int64)")
+    if dims not in (2, 3):
+        raise ValueError(f"{what}: dims must be 2 or 3, got {dims!r}")
+    if labels.dim() != dims + 1:
+        raise ValueError(f"{what}: labels must be [B, {'D, ' if dims == 3 else ''}H, W] for dims={dims}, got {tuple(labels.shape)}")
+    num_classes = _check_int(what, "num_classes", num_classes, allow_none=True)
+    if num_classes is None:
+        if classes is None:
+            raise ValueError(f"{what}: give num_classes= or classes=")
+        num_classes = max(int(c) for c in classes) + 1 if len(classes) else 1
+    if not 1 <= num_classes < (1 << 31):
+        raise ValueError(f"{what}: num_classes must be positive, got {num_classes}")
+    ignore_index = _check_int(what, "ignore_index", ignore_index, allow_none=True)
+    cap = _check_int(what, "max_workspace_bytes", max_workspace_bytes)
+    if cap < 0:
+        raise ValueError(f"{what}: max_workspace_bytes must not be negative, got {cap}")
+    sp = _spacing(what, spacing, dims)
+    squared = bool(squared)
+    table = class_table(what, classes, num_classes, labels.device)
+    K, cls = table[0], table[1] if table[1] is not None else tuple(range(num_classes))
+    B = labels.shape[0]
+    spatial = tuple(labels.shape[1:])
+    D = spatial[0] if dims == 3 else 1
+    H, W = spatial[-2], spatial[-1]
+    _geometry(what, labels[:1] if B else labels, dims)
+    dtype = torch.int32 if squared and sp is None else torch.float32
+    if B * D * H * W == 0:
+        return torch.empty((B, K) + spatial, dtype=dtype, device=labels.device)
+    lab = labels.reshape(B, -1).to(torch.int64).contiguous()
+    if not labels.is_cuda:
+        a = lab.numpy().reshape(B, 1, D, H, W)
+        objects = a == np.asarray(cls, dtype=np.int64).reshape(1, K, 1, 1, 1)
+        if ignore_index is not None:
+            objects &= a != ignore_index
+        return torch.from_numpy(signed_maps_host(objects.reshape(B * K, D, H, W), sp, squared)).reshape((B, K) + spatial)
+    maps, _ = signed_maps_device(what, None, lab, None, num_classes, table, PLANE_TRUTH, 2, ignore_index is not None, ignore_index or 0, 0.0, dims, D, H, W, sp,
+                                 squared, cap)
+    return maps.reshape((B, K) + spatial)
