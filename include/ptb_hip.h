@@ -1086,6 +1086,37 @@ int ptb_dloss_bwd(int kind, const float* logits, const int64_t* labels, const fl
                   int64_t ignore_label, float ignore_value, float alpha, int per_sample, const float* coef, float* grad,
                   ptb_stream_t stream);
 
+/* ---- Hard-example mining: top-k % and OHEM cross-entropy on a device-side radix select (no counterpart in the reference) ----
+ * logits = fp32 [B, C, S]; the target is labels int64 [B, S] (softmax cross-entropy, one ELEMENT per position) or dense fp32 [B, C, S]
+ * targets in [0, 1] (sigmoid cross-entropy, one element per (channel, position)), exactly one of them.  The element loss is fp32 and
+ * >= +0; elements whose label equals ignore_label (whose target equals ignore_value) are in no set.  A SELECTION SET is every element
+ * (per_sample = 0, one result) or the elements of a sample (B results); n its size, counted on the device.
+ *   PTB_HARDCE_TOPK  kept = max(1, floor((double)n * k_percent / 100)), 0 < k_percent <= 100
+ *   PTB_HARDCE_OHEM  with t0 > 0 and m = min(min_kept, n): kept = (number of losses > t0) if that is at least m, else m
+ * and the loss is the mean of the kept largest element losses: (sum of the losses above thr + (kept - gt) * thr) / kept, thr the
+ * smallest kept value, gt the number of losses above it.  The eq elements that equal thr by bits share the kept - gt places: weight
+ * (kept - gt) / eq each in the gradient.  kept == 0 (an empty set; OHEM with min_kept == 0 and nothing above t0): loss 0, thr +inf.
+ *   ptb_hardce_workspace_bytes  host only: the workspace of ptb_hardce_fwd (16-byte aligned), or a negative error code.
+ *   ptb_hardce_fwd   writes map (fp32 [B, S] or [B, C, S]: the element losses, all-ones bits where ignored -- the backward reads it),
+ *                    loss, threshold, kept, inv_kept (1 / kept, 0 for kept == 0) of every set and select (8 bytes per set: the bits of
+ *                    thr and of the tie weight).  error_flag DEVICE int: zeroed, then set by a label outside [0, C) that is not
+ *                    ignore_label, which also turns the loss into NaN.
+ *   ptb_hardce_bwd   grad [B, C, S] = coef[r] * weight * d(element loss) / d logits, coef DEVICE float[sets]: upstream gradient times
+ *                    inv_kept.  The decision is read from the saved map; exact zeros at ignored and unkept elements.
+ * Stream-ordered, nothing is read back; the grids depend on the shape alone; histograms and counts are integer atomics, floating-point
+ * sums are added in a fixed order, so the result is a function of the inputs alone.  PTB_EINVAL before any launch for null pointers, a
+ * shape below 1, an unknown rule, k_percent outside (0, 100], t0 <= 0 or not finite, min_kept < 0, a misaligned or short workspace;
+ * PTB_EUNSUPPORTED for a selection set of 2^31 or more elements. */
+#define PTB_HARDCE_TOPK 0
+#define PTB_HARDCE_OHEM 1
+int64_t ptb_hardce_workspace_bytes(int dense, int B, int C, int64_t S, int per_sample);
+int ptb_hardce_fwd(const float* logits, const int64_t* labels, const float* dense, int B, int C, int64_t S, int has_ignore,
+                   int64_t ignore_label, float ignore_value, int per_sample, int rule, double k_percent, float t0, int64_t min_kept,
+                   float* map, void* workspace, int64_t workspace_bytes, float* loss, float* threshold, int64_t* kept, float* inv_kept,
+                   void* select, int* error_flag, ptb_stream_t stream);
+int ptb_hardce_bwd(const float* logits, const int64_t* labels, const float* dense, const float* map, int B, int C, int64_t S,
+                   int per_sample, const float* coef, const void* select, float* grad, ptb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

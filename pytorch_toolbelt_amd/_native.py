@@ -204,6 +204,10 @@ SIGNATURES = {
                                _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp]),
     "ptb_dloss_bwd": (_c_int, [_c_int, _vp, _vp, _vp, _ip, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_f, _c_f,
                                _c_int, _vp, _vp, _vp]),
+    "ptb_hardce_workspace_bytes": (_c_i64, [_c_int, _c_int, _c_int, _c_i64, _c_int]),
+    "ptb_hardce_fwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_i64, _c_int, _c_i64, _c_f, _c_int, _c_int, _c_d, _c_f, _c_i64] + [_vp] * 2 + [_c_i64]
+                       + [_vp] * 7),
+    "ptb_hardce_bwd": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_i64, _c_int, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

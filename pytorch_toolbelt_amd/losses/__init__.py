@@ -7,6 +7,7 @@ from .focal import *  # noqa: F401,F403
 from .focal_cosine import *  # noqa: F401,F403
 from .functional import *  # noqa: F401,F403
 from .fused import *  # noqa: F401,F403
+from .hard_mining import *  # noqa: F401,F403
 from .jaccard import *  # noqa: F401,F403
 from .lovasz import *  # noqa: F401,F403
 from .logcosh import *  # noqa: F401,F403
