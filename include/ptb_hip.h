@@ -970,6 +970,37 @@ int ptb_nearest(const void* labels, int elem_bytes, int dims, int64_t B, int64_t
                 const double* spacing, int flags, int32_t* index_out, void* squared_out, void* gather_out, const void* mask, double max_sq,
                 void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Marker-controlled watershed (no counterpart in the reference) ---------------------------------------------------
+ * height [B, D, H, W] contiguous of height_dtype (PTB_F32, PTB_F16, PTB_BF16, PTB_U8, PTB_I16: widened to float32 on load, -0 counts as
+ * +0), markers [B, D, H, W] of marker_bytes (1 = bool / uint8, 2 / 4 / 8 signed), mask [B, D, H, W] bytes or NULL; dims = 2 (D == 1) or 3;
+ * connectivity 4 | 8 (dims = 2), 6 | 26 (dims = 3); B * D * H * W <= 2^31 - 2 (PTB_EUNSUPPORTED above).  All read where they lie.
+ * The flooded set M: mask != 0 (all positions without a mask) and height neither NaN nor +inf.  Seeds: the positions of M whose marker
+ * is not `background` (a background the element type cannot hold occurs nowhere: every position of M is a seed).  Per entry,
+ *   C(p)      the pass height: min over paths of neighbouring positions of M from a seed to p of the max height on the path;
+ *   D(p)      the fewest ADMISSIBLE steps (q -> p with C(q) <= C(p)) from a seed to p;
+ *   sigma(p)  the smallest linear index (z * H + y) * W + x among the seeds with an admissible path of D(p) steps to p.
+ * labels_out [B, D, H, W] of marker_bytes = markers[sigma(p)], and `fill` (the background as the element type holds it) outside M and
+ * where no path exists; it must not overlap markers.  `flags`: PTB_WATERSHED_COST -> cost_out float32 = C (+inf where unreached),
+ * PTB_WATERSHED_SEED -> seed_out int32 = sigma (-1 where unreached); a pointer without its flag, or a flag without its pointer, is
+ * PTB_EINVAL, as an unknown bit is.  The result is a function of the inputs alone.
+ * Launches on `stream`: an init kernel, then SWEEPS of the cost kernel until nothing changes, sweeps of the path kernel likewise (the
+ * phases cannot be fused), then a gather kernel.  A workgroup relaxes one tile in LDS; only the owning tile writes a position; no
+ * workgroup waits for another one, there are no atomic read-modify-writes, every loop is capped.  Sweeps are launched eight at a time;
+ * after each batch ONE 4-BYTE WORD IS READ BACK on `stream` and the stream is synchronised -- so the call CANNOT BE CAPTURED into a graph.
+ * More than max_sweeps (>= 1) sweeps in a phase, the one that finds nothing to do included -> PTB_ENOTCONVERGED; labels_out is then
+ * unwritten.  sweeps_out: HOST, two ints or NULL: the sweeps each phase took (-1: the phase was not reached; with PTB_ENOTCONVERGED the
+ * failing phase holds the sweeps it ran).
+ * workspace: DEVICE, 16-byte aligned, ptb_watershed_plan's bytes: per position 16 (height key 4, cost key 4, path key 8), per tile
+ * (2-D: 64 x 64 positions; 3-D: 8 x 8 x 32) 12, and 16 more; each array rounded up to 16 bytes.  labels_out, cost_out and seed_out
+ * 16-byte aligned. */
+#define PTB_ENOTCONVERGED (-7) /* ptb_watershed: a phase took more than max_sweeps sweeps */
+#define PTB_WATERSHED_COST 1
+#define PTB_WATERSHED_SEED 2
+int ptb_watershed_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W, int flags, int64_t* workspace_bytes);
+int ptb_watershed(const void* height, int height_dtype, const void* markers, int marker_bytes, const void* mask, int dims, int64_t B, int64_t D,
+                  int64_t H, int64_t W, int connectivity, int64_t background, int64_t fill, int flags, int max_sweeps, void* labels_out,
+                  float* cost_out, int32_t* seed_out, int32_t* sweeps_out, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+
 /* ---- Surface metrics of two label maps (no counterpart in the reference) ---------------------------------------------
  * pred, truth = [B, D, H, W] contiguous label maps (dims = 2: D == 1), each with its own elem_bytes (1 = bool / uint8, 2 / 4 / 8
  * signed), read where they lie.  Object k of an entry is, with PTB_SURFACE_CLASSES, the positions that hold class_values[k] (HOST, K

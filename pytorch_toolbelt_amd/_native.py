@@ -45,7 +45,9 @@ PTB_EHELD = -6
 PTB_EUNSUPPORTED = -2
 _ERR = {-1: "invalid argument", -2: "unsupported configuration", -3: "HIP launch failed", -4: "tile rectangle outside the accumulator",
         -5: "a cell straddles written and never-written accumulator blocks (zero-fill the accumulators, then call without the first-touch bitmap)",
-        -6: "the batch overlaps memory of an earlier batch that a later launch still reads"}
+        -6: "the batch overlaps memory of an earlier batch that a later launch still reads",
+        -7: "the relaxation did not converge within max_sweeps sweeps"}
+PTB_ENOTCONVERGED = -7
 
 _c_int = ctypes.c_int
 _c_f = ctypes.c_float
@@ -191,6 +193,9 @@ SIGNATURES = {
     "ptb_nearest_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _i64p]),
     "ptb_nearest": (_c_int, [_vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, ctypes.POINTER(_c_d), _c_int, _vp, _vp, _vp, _vp, _c_d,
                              _vp, _c_i64, _vp]),
+    "ptb_watershed_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _i64p]),
+    "ptb_watershed": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _ip,
+                               _vp, _c_i64, _vp]),
     "ptb_surface_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _ip, _i64p, _i64p, _ip]),
     "ptb_surface_metrics": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, ctypes.POINTER(_c_d), _c_d,
                                      ctypes.POINTER(_c_d), _c_int] + [_vp] * 8 + [_vp, _c_i64, _vp]),
