@@ -1001,6 +1001,41 @@ int ptb_watershed(const void* height, int height_dtype, const void* markers, int
                   int64_t H, int64_t W, int connectivity, int64_t background, int64_t fill, int flags, int max_sweeps, void* labels_out,
                   float* cost_out, int32_t* seed_out, int32_t* sweeps_out, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Morphological reconstruction, regional and h-extrema, hole filling (no counterpart in the reference) ------------
+ * mask (and, for PTB_RECONSTRUCT_VALUES, seed) [B, D, H, W] contiguous of dtype (PTB_F32, PTB_F16, PTB_BF16, PTB_U8, PTB_I16: widened to
+ * float32 on load, -0 counts as +0), domain [B, D, H, W] bytes or NULL; dims = 2 (D == 1) or 3; connectivity 4 | 8 (dims = 2), 6 | 26
+ * (dims = 3); B * D * H * W <= 2^31 - 2 (PTB_EUNSUPPORTED above).  All read where they lie.
+ * THE DOMAIN: domain != 0 (all positions without one) and mask not NaN.  Positions outside it are nobody's neighbour.  Per entry, R is
+ * the least fixed point of R(p) <- max(R(p), min(R(q), mask(p))) over the neighbours q in the domain, from min(start, mask); with
+ * erosion = 1 the mirror image (min and max exchanged, from max(start, mask)), computed on complemented keys.  `op` names the start
+ * and the result:
+ *   PTB_RECONSTRUCT_VALUES     start = seed (a NaN counts as -inf; erosion: +inf).  out of dtype = R; outside the domain the mask's element.
+ *   PTB_RECONSTRUCT_EXTREMA    start = mask one step of the ordered 32-bit key down (erosion: up).  out bytes = R < mask (erosion: R > mask):
+ *                              the regional maxima (minima); 0 outside the domain.
+ *   PTB_RECONSTRUCT_H_EXTREMA  start = float32(mask) - h (erosion: + h), h >= 0 finite; when that has converged, its R becomes the mask
+ *                              of a second PTB_RECONSTRUCT_EXTREMA phase.  out bytes as there.
+ *   PTB_RECONSTRUCT_FILL       erosion must be 1: start = mask on the faces of the entry, +inf elsewhere.  out of dtype = min(R, top)
+ *                              (top: what a domain position that no face reaches holds; the highest value of the caller's type).
+ * h must be 0 and top +inf where they have no meaning; seed NULL except for PTB_RECONSTRUCT_VALUES, out != seed.  out may be mask
+ * itself but must not overlap it otherwise.  The result is a function of the inputs alone.
+ * Launches on `stream`: an init kernel, SWEEPS of the relaxation kernel until nothing changes (h-extrema: a restage kernel and a second
+ * run of sweeps), then a gather or a compare kernel.  A workgroup relaxes one tile in LDS; only the owning tile writes a position; no
+ * workgroup waits for another one, there are no atomic read-modify-writes, every loop is capped.  Sweeps are launched eight at a time;
+ * after each batch ONE 4-BYTE WORD IS READ BACK on `stream` and the stream is synchronised -- so the call CANNOT BE CAPTURED into a graph.
+ * More than max_sweeps (>= 1) sweeps in a phase, the one that finds nothing to do included -> PTB_ENOTCONVERGED; out is then unwritten.
+ * sweeps_out: HOST, two ints or NULL: the sweeps each phase took (-1: the phase was not reached or does not exist; with
+ * PTB_ENOTCONVERGED the failing phase holds the sweeps it ran).
+ * workspace: DEVICE, 16-byte aligned, ptb_reconstruct_plan's bytes -- the only place that knows the layout: per position 8 (mask key 4,
+ * R 4), per tile (2-D: 64 x 64 positions; 3-D: 8 x 8 x 32) 12, and 16 more; each array rounded up to 16 bytes.  out 16-byte aligned. */
+#define PTB_RECONSTRUCT_VALUES 0
+#define PTB_RECONSTRUCT_EXTREMA 1
+#define PTB_RECONSTRUCT_H_EXTREMA 2
+#define PTB_RECONSTRUCT_FILL 3
+int ptb_reconstruct_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W, int op, int64_t* workspace_bytes);
+int ptb_reconstruct(const void* seed, const void* mask, int dtype, const void* domain, int dims, int64_t B, int64_t D, int64_t H, int64_t W,
+                    int connectivity, int op, int erosion, float h, float top, int max_sweeps, void* out, int32_t* sweeps_out, void* workspace,
+                    int64_t workspace_bytes, ptb_stream_t stream);
+
 /* ---- Surface metrics of two label maps (no counterpart in the reference) ---------------------------------------------
  * pred, truth = [B, D, H, W] contiguous label maps (dims = 2: D == 1), each with its own elem_bytes (1 = bool / uint8, 2 / 4 / 8
  * signed), read where they lie.  Object k of an entry is, with PTB_SURFACE_CLASSES, the positions that hold class_values[k] (HOST, K

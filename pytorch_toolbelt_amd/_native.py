@@ -196,6 +196,9 @@ SIGNATURES = {
     "ptb_watershed_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _i64p]),
     "ptb_watershed": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _ip,
                                _vp, _c_i64, _vp]),
+    "ptb_reconstruct_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _i64p]),
+    "ptb_reconstruct": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_f, _c_f, _c_int, _vp, _ip, _vp, _c_i64,
+                                 _vp]),
     "ptb_surface_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _ip, _i64p, _i64p, _ip]),
     "ptb_surface_metrics": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, ctypes.POINTER(_c_d), _c_d,
                                      ctypes.POINTER(_c_d), _c_int] + [_vp] * 8 + [_vp, _c_i64, _vp]),

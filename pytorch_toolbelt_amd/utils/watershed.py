@@ -21,8 +21,8 @@ THE DEFINITION.  A sequential priority flood decides ties by the order of its qu
 The result is ``markers[sigma(p)]``.  Where exactly one marker label attains ``C(p)`` every flooding watershed gives that label, and so
 does this one; on ties other implementations' answers depend on their queues and are not comparable bit for bit.
 
-Left out: watershed lines, compactness, seed finders (h-maxima, ``min_distance`` peaks), anisotropic spacing (steps are counted, not
-measured), gradients, multi-GPU forms, graph capture, int32 / float64 landscapes.
+Left out: watershed lines, compactness, ``min_distance`` peaks as seeds (h-maxima: ``utils/reconstruct.py``), anisotropic spacing (steps are
+counted, not measured), gradients, multi-GPU forms, graph capture, int32 / float64 landscapes.
 """
 import ctypes
 import heapq
