@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/ptb_hip.h"
 
 namespace ptb {
@@ -42,6 +44,29 @@ __device__ __forceinline__ void out_store4(float* p, const float4 v) {
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline long long up16(long long v) { return (v + 15) & ~15LL; }
+
+// label maps: the element sizes a call accepts, the integer type of a size, and whether that type holds a value
+inline bool bad_elem_bytes(int eb) { return eb != 1 && eb != 2 && eb != 4 && eb != 8; }
+template <int EB>
+using label_t = std::conditional_t<EB == 1, unsigned char, std::conditional_t<EB == 2, short, std::conditional_t<EB == 4, int, long long>>>;
+inline bool holds(int elem_bytes, long long v) {
+    switch (elem_bytes) {
+        case 1: return v >= 0 && v <= 255;
+        case 2: return v >= -32768 && v <= 32767;
+        case 4: return v >= -2147483648LL && v <= 2147483647LL;
+        default: return true;
+    }
+}
+
+// the shape of a call over [B] entries of D x H x W positions, all indexed in 32 bits: PTB_EINVAL for what is no shape,
+// PTB_EUNSUPPORTED above the limit
+constexpr long long MAX_POS = 0x7fffffffLL - 1;
+inline int check_shape(int dims, long long B, long long D, long long H, long long W) {
+    if ((dims != 2 && dims != 3) || B < 1 || D < 1 || H < 1 || W < 1 || (dims == 2 && D != 1)) return PTB_EINVAL;
+    if (D > MAX_POS || H > MAX_POS || W > MAX_POS || H * W > MAX_POS || D * H * W > MAX_POS || B > MAX_POS / (D * H * W)) return PTB_EUNSUPPORTED;
+    return PTB_OK;
+}
 
 // tunables: ptb_set_tunable(key, value) -- the key, the values it takes, what it selects
 extern int g_chunk_rows;         //  0: 16 | 32 | 64, chunk rows of the view / accumulate kernels

@@ -42,7 +42,6 @@ constexpr int CC_THREADS = 256;
 constexpr int CC_TILE = 1024;                   // positions of a tile (phases 1, 2) and of a chunk (phases 3, 4; statistics)
 constexpr int CC_LOCAL_CAP = 8 * CC_TILE;       // steps of one union inside a tile: both ends only move down, fewer than CC_TILE links each
 constexpr int CC_CAP = 1 << 24;                 // steps of one union / find on the global map (its links are tile-local roots only)
-constexpr long long CC_MAX_POS = 0x7fffffffLL - 1;
 constexpr int CC_SEAM_BLOCKS = 1 << 16;
 
 template <bool DIM3>
@@ -509,11 +508,9 @@ struct CcPlan {
     long long off_root, remove_bytes;
 };
 
-static long long cc_up16(long long v) { return (v + 15) & ~15LL; }
-
 static int cc_plan(int dims, long long B, long long D, long long H, long long W, CcPlan& p) {
     if ((dims != 2 && dims != 3) || B < 1 || D < 1 || H < 1 || W < 1 || (dims == 2 && D != 1)) return PTB_EINVAL;
-    if (D > CC_MAX_POS || H > CC_MAX_POS || W > CC_MAX_POS || H * W > CC_MAX_POS || D * H * W > CC_MAX_POS || B > CC_MAX_POS / (D * H * W)) return PTB_EUNSUPPORTED;
+    if (D > MAX_POS || H > MAX_POS || W > MAX_POS || H * W > MAX_POS || D * H * W > MAX_POS || B > MAX_POS / (D * H * W)) return PTB_EUNSUPPORTED;
     p.dims = dims; p.D = (int)D; p.H = (int)H; p.W = (int)W; p.B = B;
     p.TZ = dims == 3 ? CcTile<true>::TZ : CcTile<false>::TZ;
     p.TY = dims == 3 ? CcTile<true>::TY : CcTile<false>::TY;
@@ -523,24 +520,20 @@ static int cc_plan(int dims, long long B, long long D, long long H, long long W,
     p.tiles = B * p.tz * p.ty * p.tx;
     p.cpe = (p.n + CC_TILE - 1) / CC_TILE;
     p.chunks = B * p.cpe;
-    if (p.tiles > CC_MAX_POS || p.chunks > CC_MAX_POS) return PTB_EUNSUPPORTED;
+    if (p.tiles > MAX_POS || p.chunks > MAX_POS) return PTB_EUNSUPPORTED;
     p.levels = scan_levels(p.chunks + 1, p.cnt);
     long long o = 0;
-    p.off_err = o; o += cc_up16(4 * B);
-    p.off_parent = o; o += cc_up16(4 * p.total);
-    p.off_root = o; p.remove_bytes = o + cc_up16(4 * p.total);
-    p.off_counts = o; o += cc_up16(4 * (p.chunks + 1));
-    p.off_excl = o; o += cc_up16(8 * (p.chunks + 1));
-    for (int l = 0; l < p.levels; ++l) { p.off_sums[l] = o; o += cc_up16(8 * p.cnt[l]); }
+    p.off_err = o; o += up16(4 * B);
+    p.off_parent = o; o += up16(4 * p.total);
+    p.off_root = o; p.remove_bytes = o + up16(4 * p.total);
+    p.off_counts = o; o += up16(4 * (p.chunks + 1));
+    p.off_excl = o; o += up16(8 * (p.chunks + 1));
+    for (int l = 0; l < p.levels; ++l) { p.off_sums[l] = o; o += up16(8 * p.cnt[l]); }
     p.label_bytes = o;
     return PTB_OK;
 }
 
-static bool cc_bad_elem(int eb) { return eb != 1 && eb != 2 && eb != 4 && eb != 8; }
 static bool cc_bad_conn(int dims, int c) { return dims == 2 ? (c != 4 && c != 8) : (c != 6 && c != 26); }
-
-template <int EB>
-using cc_label_t = std::conditional_t<EB == 1, unsigned char, std::conditional_t<EB == 2, short, std::conditional_t<EB == 4, int, long long>>>;
 
 // phases 1 - 3: the roots of every position into `root`; the roots per chunk into counts when given
 static int cc_roots(const void* labels, int elem_bytes, const CcPlan& p, int connectivity, int has_bg, long long bg, char* ws, int* root, unsigned* counts,
@@ -548,12 +541,12 @@ static int cc_roots(const void* labels, int elem_bytes, const CcPlan& p, int con
     CcArgs a{};
     a.labels = labels; a.parent = reinterpret_cast<int*>(ws + p.off_parent); a.err = reinterpret_cast<int*>(ws + p.off_err);
     a.bg = bg; a.has_bg = has_bg != 0; a.n = (unsigned)p.n; a.total = (unsigned)p.total; a.D = p.D; a.H = p.H; a.W = p.W; a.tz = p.tz; a.ty = p.ty; a.tx = p.tx;
-    if (hipError_t e = hipMemsetAsync(a.err, 0, (size_t)cc_up16(4 * p.B), s); e != hipSuccess) { set_hip_error(e); return PTB_ELAUNCH; }
+    if (hipError_t e = hipMemsetAsync(a.err, 0, (size_t)up16(4 * p.B), s); e != hipSuccess) { set_hip_error(e); return PTB_ELAUNCH; }
     const bool full = connectivity == 8 || connectivity == 26;
     const bool wide = p.W % 4 == 0 && reinterpret_cast<uintptr_t>(labels) % std::min(4 * elem_bytes, 16) == 0;
     const unsigned seam_blocks = (unsigned)std::min<long long>((p.total + CC_THREADS - 1) / CC_THREADS, CC_SEAM_BLOCKS);
     with_value<1, 2, 4, 8>(elem_bytes, [&](auto eb) {
-        using T = cc_label_t<eb()>;
+        using T = label_t<eb()>;
         with_bool(p.dims == 3, [&](auto d3) {
             with_bool(full, [&](auto f) {
                 with_bool(wide, [&](auto w) {
@@ -588,7 +581,7 @@ extern "C" int ptb_cc_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t W,
 
 extern "C" int ptb_cc_label(const void* labels, int elem_bytes, int dims, int64_t B, int64_t D, int64_t H, int64_t W, int connectivity, int has_background,
                             int64_t background, int32_t* cc, int64_t* count, void* workspace, int64_t workspace_bytes, ptb_stream_t stream) {
-    if (!labels || !cc || !count || !workspace || cc_bad_elem(elem_bytes) || (dims != 2 && dims != 3) || cc_bad_conn(dims, connectivity)) return PTB_EINVAL;
+    if (!labels || !cc || !count || !workspace || bad_elem_bytes(elem_bytes) || (dims != 2 && dims != 3) || cc_bad_conn(dims, connectivity)) return PTB_EINVAL;
     CcPlan p;
     if (int rc = cc_plan(dims, B, D, H, W, p)) return rc;
     if (workspace_bytes < p.label_bytes || !aligned16(workspace) || !aligned16(cc)) return PTB_EINVAL;
@@ -612,7 +605,7 @@ extern "C" int ptb_cc_label(const void* labels, int elem_bytes, int dims, int64_
 extern "C" int ptb_cc_remove_small(const void* labels, int elem_bytes, int dims, int64_t B, int64_t D, int64_t H, int64_t W, int connectivity,
                                    int has_background, int64_t background, int64_t min_area, int64_t fill, void* out, void* workspace,
                                    int64_t workspace_bytes, ptb_stream_t stream) {
-    if (!labels || !out || !workspace || cc_bad_elem(elem_bytes) || (dims != 2 && dims != 3) || cc_bad_conn(dims, connectivity)) return PTB_EINVAL;
+    if (!labels || !out || !workspace || bad_elem_bytes(elem_bytes) || (dims != 2 && dims != 3) || cc_bad_conn(dims, connectivity)) return PTB_EINVAL;
     CcPlan p;
     if (int rc = cc_plan(dims, B, D, H, W, p)) return rc;
     if (workspace_bytes < p.remove_bytes || !aligned16(workspace)) return PTB_EINVAL;
@@ -626,7 +619,7 @@ extern "C" int ptb_cc_remove_small(const void* labels, int elem_bytes, int dims,
     const dim3 grid((unsigned)((p.total + CC_THREADS - 1) / CC_THREADS));
     const int* err = reinterpret_cast<const int*>(ws + p.off_err);
     with_value<1, 2, 4, 8>(elem_bytes, [&](auto eb) {
-        using U = std::make_unsigned_t<cc_label_t<eb()>>;
+        using U = std::make_unsigned_t<label_t<eb()>>;
         hipLaunchKernelGGL((cc_rewrite_kernel<U>), grid, dim3(CC_THREADS), 0, s, reinterpret_cast<const U*>(labels), reinterpret_cast<U*>(out), (const int*)root,
                            (const unsigned*)area, err, (unsigned)p.n, (unsigned)p.total, (long long)min_area, (U)fill);
     });
@@ -635,10 +628,10 @@ extern "C" int ptb_cc_remove_small(const void* labels, int elem_bytes, int dims,
 
 extern "C" int ptb_cc_stats(const int32_t* cc, int dims, int64_t D, int64_t H, int64_t W, int64_t max_components, const void* values, int values_elem_bytes,
                             int64_t* area, int64_t* bbox, void* value, ptb_stream_t stream) {
-    if (!cc || !area || !bbox || max_components < 1 || (values != nullptr) != (value != nullptr) || (values && cc_bad_elem(values_elem_bytes))) return PTB_EINVAL;
+    if (!cc || !area || !bbox || max_components < 1 || (values != nullptr) != (value != nullptr) || (values && bad_elem_bytes(values_elem_bytes))) return PTB_EINVAL;
     CcPlan p;
     if (int rc = cc_plan(dims, 1, D, H, W, p)) return rc;
-    if (max_components > CC_MAX_POS) return PTB_EUNSUPPORTED;
+    if (max_components > MAX_POS) return PTB_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     CcStatsArgs a{};
     a.cc = cc; a.values = values; a.area = reinterpret_cast<long long*>(area); a.bbox = reinterpret_cast<long long*>(bbox); a.value = value;

@@ -199,11 +199,6 @@ static int conf_grid_x(long long items, long long ch, long long groups, const Co
     return PTB_OK;
 }
 
-static bool bad_elem(int eb) { return eb != 1 && eb != 2 && eb != 4 && eb != 8; }
-
-template <int EB>
-using conf_label_t = std::conditional_t<EB == 1, unsigned char, std::conditional_t<EB == 2, short, std::conditional_t<EB == 4, int, long long>>>;
-
 constexpr long long CONF_MAX_ELEMS = 1LL << 60;
 constexpr int CONF_MAX_Z = 65535;
 
@@ -221,7 +216,7 @@ extern "C" int ptb_confusion_plan(int K, int* row_blocks, int* lds_bytes) {
 
 extern "C" int ptb_confusion_labels(const void* pred, int pred_elem_bytes, const void* target, int target_elem_bytes, int64_t B, int64_t n_per_sample,
                                     int K, int has_ignore, int64_t ignore_index, int64_t* out, int64_t* invalid, ptb_stream_t stream) {
-    if (!pred || !target || !out || !invalid || bad_elem(pred_elem_bytes) || bad_elem(target_elem_bytes) || B < 1 || n_per_sample < 1) return PTB_EINVAL;
+    if (!pred || !target || !out || !invalid || bad_elem_bytes(pred_elem_bytes) || bad_elem_bytes(target_elem_bytes) || B < 1 || n_per_sample < 1) return PTB_EINVAL;
     if (B > 0x7fffffffLL) return PTB_EUNSUPPORTED;
     ConfPlan p;
     if (int rc = conf_plan(K, p)) return rc;
@@ -241,7 +236,7 @@ extern "C" int ptb_confusion_labels(const void* pred, int pred_elem_bytes, const
         const dim3 grid(gx, (unsigned)p.row_blocks, (unsigned)groups);
         with_value<1, 2, 4, 8>(pred_elem_bytes, [&](auto pe) {
             with_value<1, 2, 4, 8>(target_elem_bytes, [&](auto te) {
-                hipLaunchKernelGGL((confusion_labels_kernel<conf_label_t<pe()>, conf_label_t<te()>>), grid, dim3(CONF_THREADS), (size_t)p.lds_bytes, s, a);
+                hipLaunchKernelGGL((confusion_labels_kernel<label_t<pe()>, label_t<te()>>), grid, dim3(CONF_THREADS), (size_t)p.lds_bytes, s, a);
             });
         });
         if (int rc = check_launch()) return rc;
@@ -251,7 +246,7 @@ extern "C" int ptb_confusion_labels(const void* pred, int pred_elem_bytes, const
 
 extern "C" int ptb_confusion_logits(const void* logits, int dtype, int64_t N, int C, int64_t S, float threshold, const void* target, int target_elem_bytes,
                                     int per_sample, int has_ignore, int64_t ignore_index, int64_t* out, int64_t* invalid, ptb_stream_t stream) {
-    if (!logits || !target || !out || !invalid || bad_elem(target_elem_bytes) || N < 1 || C < 1 || S < 1) return PTB_EINVAL;
+    if (!logits || !target || !out || !invalid || bad_elem_bytes(target_elem_bytes) || N < 1 || C < 1 || S < 1) return PTB_EINVAL;
     if (dtype != PTB_F32 && dtype != PTB_F16 && dtype != PTB_BF16) return PTB_EINVAL;
     if (C > CONF_MAX_K) return PTB_EUNSUPPORTED;
     ConfPlan p;
@@ -275,7 +270,7 @@ extern "C" int ptb_confusion_logits(const void* logits, int dtype, int64_t N, in
         const dim3 grid(gx, (unsigned)p.row_blocks, (unsigned)groups);
         with_src_dtype(dtype, [&](auto ld) {
             with_value<1, 2, 4, 8>(target_elem_bytes, [&](auto te) {
-                hipLaunchKernelGGL((confusion_logits_kernel<ld(), conf_label_t<te()>>), grid, dim3(CONF_THREADS), (size_t)p.lds_bytes, s, a);
+                hipLaunchKernelGGL((confusion_logits_kernel<ld(), label_t<te()>>), grid, dim3(CONF_THREADS), (size_t)p.lds_bytes, s, a);
             });
         });
         if (int rc = check_launch()) return rc;

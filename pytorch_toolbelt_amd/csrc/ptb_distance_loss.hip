@@ -470,7 +470,7 @@ static int dl_common(const float* logits, bool need_logits, const int64_t* label
                 if (classes[i] == classes[k]) return PTB_EINVAL;
         }
     }
-    if (S > EDT_MAX_POS || (long long)B * dl_blocks_per_sample(S) > 0x7fffffffLL) return PTB_EUNSUPPORTED;
+    if (S > MAX_POS || (long long)B * dl_blocks_per_sample(S) > 0x7fffffffLL) return PTB_EUNSUPPORTED;
     a.x = logits; a.labels = reinterpret_cast<const long long*>(labels); a.dense = dense;
     a.cls = class_table; a.slot = class_table ? class_table + K : nullptr;
     a.S = (unsigned)S; a.bps = (unsigned)dl_blocks_per_sample(S); a.C = C; a.K = K; a.act = prob;
@@ -505,7 +505,7 @@ extern "C" int ptb_dloss_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t
     // a chunk starts where its int32 / float32 output is 16-byte aligned: every `step` entries
     const long long step = S % 4 == 0 ? 1 : S % 2 == 0 ? 2 : 4;
     const long long least = std::min(E, step);
-    if (least > EDT_MAX_POS / S) return PTB_EUNSUPPORTED;
+    if (least > MAX_POS / S) return PTB_EUNSUPPORTED;
     auto bytes_of = [&](long long entries) {
         int64_t n = 0;
         ptb_edt_plan(dims, entries, D, H, W, 1, &n);
@@ -514,7 +514,7 @@ extern "C" int ptb_dloss_plan(int dims, int64_t B, int64_t D, int64_t H, int64_t
     if (min_workspace_bytes) *min_workspace_bytes = bytes_of(least);
     if (bytes_of(least) > max_workspace_bytes) return PTB_EINVAL;
     // the workspace grows with the entries: the largest count within the cap and ptb_edt's 2^31 - 2 positions, by bisection
-    long long lo = least, hi = std::min(E, (long long)(EDT_MAX_POS / S));
+    long long lo = least, hi = std::min(E, (long long)(MAX_POS / S));
     while (lo < hi) {
         const long long mid = lo + (hi - lo + 1) / 2;
         if (bytes_of(mid) <= max_workspace_bytes) lo = mid;

@@ -41,7 +41,6 @@ namespace ptb {
 constexpr int IN_THREADS = 256;
 constexpr int IN_CHUNK = 1024;                  // positions of a chunk of the pair kernel, instances of a block of the count kernel
 constexpr int IN_HASH = 1024;                   // slots of the LDS tables: a chunk has at most IN_CHUNK distinct keys
-constexpr long long IN_MAX_POS = 0x7fffffffLL - 1;
 constexpr long long IN_MAX_PAIRS = 1LL << 28;
 constexpr int IN_MAX_T = 16;
 constexpr int IN_OUTPUTS = 17;
@@ -407,12 +406,10 @@ struct InstPlan {
 enum { IN_NUM_PAIRS, IN_PRED_AREA, IN_TRUTH_AREA, IN_PAIRS, IN_INTERSECTION, IN_PRED_MATCH, IN_TRUTH_MATCH, IN_PRED_IOU, IN_TRUTH_IOU, IN_TP, IN_FP, IN_FN,
        IN_SUM_IOU, IN_SQ, IN_RQ, IN_PQ, IN_AP };
 
-static long long in_up16(long long v) { return (v + 15) & ~15LL; }
-
 // T == 0: the overlap table (rows = max_pairs); T >= 1: the matching (no rows)
 static int inst_plan(long long n, long long np, long long nt, long long m, int T, long long K, InstPlan& p) {
     if (n < 1 || np < 0 || nt < 0 || m < 0 || T < 0 || T > IN_MAX_T || K < 0 || (T == 0 && K != 0)) return PTB_EINVAL;
-    if (n > IN_MAX_POS || np > IN_MAX_POS || nt > IN_MAX_POS || m > IN_MAX_PAIRS || K > 65535) return PTB_EUNSUPPORTED;
+    if (n > MAX_POS || np > MAX_POS || nt > MAX_POS || m > IN_MAX_PAIRS || K > 65535) return PTB_EUNSUPPORTED;
     p.n = n; p.np = np; p.nt = nt; p.m = m; p.T = T; p.K = std::max<long long>(K, 1);
     p.slots = 2; p.shift = 63;
     while (p.slots < 2 * m) { p.slots *= 2; --p.shift; }
@@ -422,24 +419,24 @@ static int inst_plan(long long n, long long np, long long nt, long long m, int T
     p.levels = T == 0 ? scan_levels(p.words + 1, p.cnt) : 0;
     long long o = 0;
     p.off_hdr = o; o += 16;
-    p.off_key = o; o += in_up16(8 * p.slots);
-    p.off_cnt = o; o += in_up16(4 * p.slots);
-    p.off_bitmap = o; o += in_up16(4 * p.words);
-    p.off_counts = o; o += T == 0 ? in_up16(4 * (p.words + 1)) : 0;
+    p.off_key = o; o += up16(8 * p.slots);
+    p.off_cnt = o; o += up16(4 * p.slots);
+    p.off_bitmap = o; o += up16(4 * p.words);
+    p.off_counts = o; o += T == 0 ? up16(4 * (p.words + 1)) : 0;
     p.zero_bytes = o;
-    p.off_pos = o; o += in_up16(4 * p.slots);
-    p.off_excl = o; o += T == 0 ? in_up16(8 * (p.words + 1)) : 0;
-    for (int l = 0; l < p.levels; ++l) { p.off_sums[l] = o; o += in_up16(8 * p.cnt[l]); }
+    p.off_pos = o; o += up16(4 * p.slots);
+    p.off_excl = o; o += T == 0 ? up16(8 * (p.words + 1)) : 0;
+    for (int l = 0; l < p.levels; ++l) { p.off_sums[l] = o; o += up16(8 * p.cnt[l]); }
     const long long kt = p.K * T;
-    p.off_ptp = o; o += in_up16(4 * p.gp * kt);
-    p.off_psum = o; o += in_up16(8 * p.gp * kt);
-    p.off_ppp = o; o += T ? in_up16(4 * p.gp * p.K) : 0;
-    p.off_ppt = o; o += T ? in_up16(4 * p.gt * p.K) : 0;
+    p.off_ptp = o; o += up16(4 * p.gp * kt);
+    p.off_psum = o; o += up16(8 * p.gp * kt);
+    p.off_ppp = o; o += T ? up16(4 * p.gp * p.K) : 0;
+    p.off_ppt = o; o += T ? up16(4 * p.gt * p.K) : 0;
     p.ws_bytes = o;
     const long long sizes[IN_OUTPUTS] = {8, 8 * np, 8 * nt, 8 * p.rows, 8 * p.rows, T ? 4 * np : 0, T ? 4 * nt : 0, T ? 8 * np : 0, T ? 8 * nt : 0,
                                          8 * kt, 8 * kt, 8 * kt, 8 * kt, 8 * kt, 8 * kt, 8 * kt, 8 * kt};
     o = 0;
-    for (int i = 0; i < IN_OUTPUTS; ++i) { p.out[i] = o; o += in_up16(sizes[i]); }
+    for (int i = 0; i < IN_OUTPUTS; ++i) { p.out[i] = o; o += up16(sizes[i]); }
     p.out_bytes = o;
     return PTB_OK;
 }
@@ -465,8 +462,6 @@ static int inst_pairs(const int32_t* pred, const int32_t* truth, const InstPlan&
     });
     return PTB_OK;
 }
-
-static bool in_bad_elem(int eb) { return eb != 1 && eb != 2 && eb != 4 && eb != 8; }
 
 }  // namespace ptb
 
@@ -517,7 +512,7 @@ extern "C" int ptb_inst_match(const int32_t* pred, const int32_t* truth, int64_t
     const bool classes = K > 0;
     if (!classes && (pred_class || truth_class)) return PTB_EINVAL;
     if (classes && ((!pred_class && n_pred > 0) || (!truth_class && n_truth > 0))) return PTB_EINVAL;      // (a side without instances needs no classes)
-    if (classes && (in_bad_elem(pred_class_elem_bytes) || in_bad_elem(truth_class_elem_bytes))) return PTB_EINVAL;
+    if (classes && (bad_elem_bytes(pred_class_elem_bytes) || bad_elem_bytes(truth_class_elem_bytes))) return PTB_EINVAL;
     for (int j = 0; j < T; ++j)
         if (!(thresholds[j] >= 0.5 && thresholds[j] < 1.0) || (j > 0 && !(thresholds[j] > thresholds[j - 1]))) return PTB_EINVAL;
     InstPlan p;

@@ -230,8 +230,6 @@ struct RlePlan {
     long long off_enc, off_offsets, off_sums[SCAN_MAX_LEVELS], off_counts, bytes;
 };
 
-static long long up16(long long v) { return (v + 15) & ~15LL; }
-
 static int make_plan(int B, int K, int H, int W, RlePlan& p) {
     if (B < 1 || K < 0 || H < 1 || W < 1) return PTB_EINVAL;
     if ((long long)H * W > RLE_MAX_PIXELS) return PTB_EUNSUPPORTED;
@@ -281,7 +279,7 @@ static int launch_pass(const void* mask, int elem_bytes, int B, int H, int W, co
 }
 
 static bool bad_labels(int elem_bytes, const int64_t* labels, int K) {
-    return (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) || (K > 0 && !labels);
+    return bad_elem_bytes(elem_bytes) || (K > 0 && !labels);
 }
 
 }  // namespace ptb

@@ -42,7 +42,6 @@ constexpr int SURF_MAX_TOL = 8;
 constexpr int SURF_SEG_MIN = 4096;              // positions a workgroup of the sample kernel owns at least ...
 constexpr int SURF_MAX_SLOTS = 256;             // ... and workgroups (partial sums) per map at most
 constexpr unsigned SURF_INT_INF = 0x7fffffffu;  // ptb_edt's int32 "no site"
-constexpr long long SURF_MAX_POS = 0x7fffffffLL - 1;
 constexpr long long SURF_MAX_GRID = 0x7fffffffLL; // workgroups of one launch at most
 
 enum { SURF_IN_EQ = 0, SURF_IN_NE = 1, SURF_IN_NONE = 2, SURF_IN_ALL = 3 };   // a position belongs to the object iff label ==, != value; never; always
@@ -450,8 +449,6 @@ struct SurfPlan {
     long long off_border, off_dist, off_edt, edt_bytes, bytes, min_bytes;
 };
 
-static long long surf_up16(long long v) { return (v + 15) & ~15LL; }
-
 // bytes of the maps of a chunk of c classes; -1: past the transform's position limit or a launch's grid limit.  EVERY grid of
 // ptb_surface_metrics is decided here, so that the plan refuses (or shrinks the chunk) and no launch loop does.  The sample kernels take a
 // workgroup per map and segment: slots <= P, so maps * slots <= maps * P, which the position limit bounds.  The border kernel takes B
@@ -459,18 +456,18 @@ static long long surf_up16(long long v) { return (v + 15) & ~15LL; }
 // than 2^31 / 3 maps of a single position.
 static long long surf_chunk_bytes(const SurfPlan& p, int dims, long long D, long long H, long long W, int c, long long* edt_bytes) {
     const long long maps = 2LL * c * p.B;
-    if (maps > SURF_MAX_POS / p.P || maps / 2 > SURF_MAX_GRID / 3) return -1;
+    if (maps > MAX_POS / p.P || maps / 2 > SURF_MAX_GRID / 3) return -1;
     int64_t e = 0;
     if (ptb_edt_plan(dims, maps, D, H, W, 0, &e) != PTB_OK) return -1;
     if (edt_bytes) *edt_bytes = e;
-    return surf_up16(maps * p.P) + surf_up16(4 * maps * p.P) + e;
+    return up16(maps * p.P) + up16(4 * maps * p.P) + e;
 }
 
 static int surf_plan(int dims, long long B, long long D, long long H, long long W, int K, long long cap, SurfPlan& p) {
     if ((dims != 2 && dims != 3) || B < 1 || D < 1 || H < 1 || W < 1 || K < 1 || (dims == 2 && D != 1) || cap < 0) return PTB_EINVAL;
-    if (D > SURF_MAX_POS || H > SURF_MAX_POS || W > SURF_MAX_POS || H * W > SURF_MAX_POS || D * H * W > SURF_MAX_POS) return PTB_EUNSUPPORTED;
+    if (D > MAX_POS || H > MAX_POS || W > MAX_POS || H * W > MAX_POS || D * H * W > MAX_POS) return PTB_EUNSUPPORTED;
     p.B = B; p.P = D * H * W;
-    if (B > SURF_MAX_POS / p.P / 2 || K > SURF_MAX_POS / B) return PTB_EUNSUPPORTED;
+    if (B > MAX_POS / p.P / 2 || K > MAX_POS / B) return PTB_EUNSUPPORTED;
     p.objects = B * K;
     // the sample kernel's geometry: a function of P alone
     long long seg = std::max<long long>(SURF_SEG_MIN, (p.P + SURF_MAX_SLOTS - 1) / SURF_MAX_SLOTS);
@@ -479,8 +476,8 @@ static int surf_plan(int dims, long long B, long long D, long long H, long long 
     p.slots = (int)((p.P + seg - 1) / seg);
     const long long words[9] = {2, 2, SURF_MAX_TOL, 3, 3, 3, 3, 3, 3 * 256};
     long long o = 0;
-    for (int i = 0; i < 9; ++i) { p.off_state[i] = o; o += surf_up16(4 * words[i] * p.objects); }
-    p.off_state[9] = o; o += surf_up16(8LL * 2 * p.slots * p.objects);
+    for (int i = 0; i < 9; ++i) { p.off_state[i] = o; o += up16(4 * words[i] * p.objects); }
+    p.off_state[9] = o; o += up16(8LL * 2 * p.slots * p.objects);
     p.state_bytes = o;
     long long e = 0;
     const long long one = surf_chunk_bytes(p, dims, D, H, W, 1, &e);
@@ -493,8 +490,8 @@ static int surf_plan(int dims, long long B, long long D, long long H, long long 
             p.chunk = c; p.edt_bytes = e;
             const long long maps = 2LL * c * B;
             p.off_border = p.state_bytes;
-            p.off_dist = p.off_border + surf_up16(maps * p.P);
-            p.off_edt = p.off_dist + surf_up16(4 * maps * p.P);
+            p.off_dist = p.off_border + up16(maps * p.P);
+            p.off_edt = p.off_dist + up16(4 * maps * p.P);
             p.bytes = p.state_bytes + need;
             break;
         }
@@ -517,20 +514,6 @@ static SurfState surf_state(const SurfPlan& p, char* ws) {
     return s;
 }
 
-template <int EB>
-using surf_label_t = std::conditional_t<EB == 1, unsigned char, std::conditional_t<EB == 2, short, std::conditional_t<EB == 4, int, long long>>>;
-
-static bool surf_holds(int elem_bytes, long long v) {
-    switch (elem_bytes) {
-        case 1: return v >= 0 && v <= 255;
-        case 2: return v >= -32768 && v <= 32767;
-        case 4: return v >= -2147483648LL && v <= 2147483647LL;
-        default: return true;
-    }
-}
-
-static bool surf_bad_elem(int eb) { return eb != 1 && eb != 2 && eb != 4 && eb != 8; }
-
 }  // namespace ptb
 
 using namespace ptb;
@@ -552,7 +535,7 @@ extern "C" int ptb_surface_metrics(const void* pred, int pred_elem_bytes, const 
                                    const double* tolerances, int T, int64_t* surface_count, float* directed_hausdorff, float* hausdorff,
                                    float* directed_percentile, float* hausdorff_percentile, float* mean_surface_distance, float* assd, float* surface_dice,
                                    void* workspace, int64_t workspace_bytes, ptb_stream_t stream) {
-    if (!pred || !truth || !class_values || !tolerances || !workspace || surf_bad_elem(pred_elem_bytes) || surf_bad_elem(truth_elem_bytes)) return PTB_EINVAL;
+    if (!pred || !truth || !class_values || !tolerances || !workspace || bad_elem_bytes(pred_elem_bytes) || bad_elem_bytes(truth_elem_bytes)) return PTB_EINVAL;
     if (!surface_count || !directed_hausdorff || !hausdorff || !directed_percentile || !hausdorff_percentile || !mean_surface_distance || !assd || !surface_dice)
         return PTB_EINVAL;
     if (object_rule != PTB_SURFACE_CLASSES && object_rule != PTB_SURFACE_NOT_BACKGROUND) return PTB_EINVAL;
@@ -605,17 +588,17 @@ extern "C" int ptb_surface_metrics(const void* pred, int pred_elem_bytes, const 
             ba.full = full; ba.dims3 = dims == 3;
             for (int k = 0; k < C; ++k) {                                      // a value the element type cannot hold occurs nowhere
                 const long long v = class_values[k0 + k];
-                const bool holds = surf_holds(eb, v);
+                const bool held = holds(eb, v);
                 ba.values[k] = v;
-                if (object_rule == PTB_SURFACE_CLASSES) ba.modes[k] = holds ? SURF_IN_EQ : SURF_IN_NONE;
-                else ba.modes[k] = holds ? SURF_IN_NE : SURF_IN_ALL;
+                if (object_rule == PTB_SURFACE_CLASSES) ba.modes[k] = held ? SURF_IN_EQ : SURF_IN_NONE;
+                else ba.modes[k] = held ? SURF_IN_NE : SURF_IN_ALL;
             }
             ba.object_mode = object_rule == PTB_SURFACE_CLASSES ? SURF_IN_EQ : ba.modes[0];
             ba.object_value = class_values[0];
             // (the border maps of a chunk start at multiples of P: packed stores need P % 4 == 0, which W % 4 == 0 gives)
             const bool wide = W % 4 == 0 && reinterpret_cast<uintptr_t>(labels) % std::min(4 * eb, 16) == 0;
             with_value<1, 2, 4, 8>(eb, [&](auto e) {
-                using T_ = surf_label_t<e()>;
+                using T_ = label_t<e()>;
                 with_bool(wide, [&](auto w) {
                     hipLaunchKernelGGL((surf_border_kernel<T_, w()>), dim3(bpe * (unsigned)B), dim3(SURF_THREADS), 0, s, ba);
                 });

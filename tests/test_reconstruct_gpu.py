@@ -14,7 +14,7 @@ from test_reconstruct_cpu import call
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-BATCH = 8                                  # RC_BATCH of csrc/ptb_reconstruct.hip: the sweeps between two read-backs
+BATCH = 8                                  # RELAX_BATCH of csrc/ptb_relax_device.h: the sweeps between two read-backs
 DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.uint8, torch.int16)
 
 

@@ -13,7 +13,7 @@ from pytorch_toolbelt_amd.utils import watershed
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-BATCH = 8                                  # WS_BATCH of csrc/ptb_watershed.hip: the sweeps between two read-backs
+BATCH = 8                                  # RELAX_BATCH of csrc/ptb_relax_device.h: the sweeps between two read-backs
 HEIGHT_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.uint8, torch.int16)
 MARKER_DTYPES = (torch.bool, torch.uint8, torch.int16, torch.int32, torch.int64)
 
