@@ -26,6 +26,7 @@ from torch import Tensor
 from torch.nn.modules.loss import _Loss
 
 from .. import _native as N
+from ..utils import _maps as M
 from ..utils import distance as _distance
 from . import _kernels as K
 from ._region import BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE
@@ -71,7 +72,7 @@ def _problem(what, y_pred, y_true, mode, classes, from_logits, ignore_index, spa
         dense = y_true.float().contiguous().reshape(B, C, S)
         prob = K.PROB_SIGMOID if from_logits else K.PROB_IDENTITY
     table = _distance.class_table(what, classes, C, x.device)
-    sp = _distance._spacing(what, spacing, dims)
+    sp = M.spacing(what, spacing, dims)
     D = spatial[0] if dims == 3 else 1
     geometry = (dims, D, spatial[-2], spatial[-1])
     if dist_maps is not None:
@@ -115,7 +116,7 @@ class DistanceMapLoss(torch.autograd.Function):
         _, _, slots = _distance.plan_maps(what, lib, dims, B, D, H, W, Kn, 1, 1 << 62)
         results = B if per_sample else 1
         with N.on_device(x.device):
-            ws = torch.empty(16 * slots, dtype=torch.uint8, device=x.device)
+            ws = M.scratch(16 * slots, x.device)
             loss = torch.empty(results, dtype=torch.float32, device=x.device)
             inv = torch.empty(results, dtype=torch.float32, device=x.device)
             flag = torch.empty(1, dtype=torch.int32, device=x.device)

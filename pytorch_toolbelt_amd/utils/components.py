@@ -16,58 +16,23 @@ import numpy as np
 import torch
 
 from .. import _native as N
+from . import _maps as M
 
 __all__ = ["connected_components", "component_stats", "remove_small_components"]
 
-_ELEM_BYTES = {torch.bool: 1, torch.uint8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
-_CONNECTIVITIES = {2: (4, 8), 3: (6, 26)}
-MAX_POSITIONS = (1 << 31) - 2
+MAX_POSITIONS = M.MAX_POSITIONS
 
 
 # ---------------------------------------------------------------------------------------------------------------- validation
-def _fits(c, dtype):
-    if dtype == torch.bool:
-        return c in (0, 1)
-    info = torch.iinfo(dtype)
-    return info.min <= c <= info.max
-
-
-def _check_int(what, name, v, allow_none=False):
-    if v is None and allow_none:
-        return None
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise TypeError(f"{what}: {name} must be an int{' or None' if allow_none else ''}, got {v!r}")
-    v = int(v)
-    if not -(1 << 63) <= v < (1 << 63):
-        raise ValueError(f"{what}: {name} {v} does not fit int64")
-    return v
-
-
 def _geometry(what, labels, connectivity, background, dims):
     """Validated ``(stack, B, D, H, W, full, background)`` of a labelling call."""
-    if not isinstance(labels, torch.Tensor):
-        raise TypeError(f"{what}: labels must be a tensor, got {type(labels).__name__}")
-    if labels.dtype not in _ELEM_BYTES:
-        raise TypeError(f"{what}: labels must hold integer labels (bool, uint8, int16, int32 or int64), got {labels.dtype}")
-    if dims not in _CONNECTIVITIES:
-        raise ValueError(f"{what}: dims must be 2 or 3, got {dims!r}")
-    if isinstance(connectivity, bool) or connectivity not in _CONNECTIVITIES[dims]:
-        a, b = _CONNECTIVITIES[dims]
-        raise ValueError(f"{what}: connectivity must be {a} or {b} for dims={dims}, got {connectivity!r}")
-    background = _check_int(what, "background", background, allow_none=True)
-    if labels.dim() < dims:
-        raise ValueError(f"{what}: labels must be [*stack, {'D, ' if dims == 3 else ''}H, W] for dims={dims}, got {tuple(labels.shape)}")
-    stack = tuple(labels.shape[:-dims])
-    D = labels.shape[-3] if dims == 3 else 1
-    H, W = labels.shape[-2], labels.shape[-1]
-    B = 1
-    for s in stack:
-        B *= s
-    if B * D * H * W > MAX_POSITIONS:
-        raise ValueError(f"{what}: {B * D * H * W} positions in one call; at most 2^31 - 2 = {MAX_POSITIONS} (component numbers are int32): split the stack")
-    if background is not None and not _fits(background, labels.dtype):
+    M.check_labels(what, "labels", labels)
+    connectivity, full = M.check_connectivity(what, connectivity, dims)
+    background = M.check_int(what, "background", background, allow_none=True)
+    stack, B, D, H, W = M.extent(what, "labels", labels, dims, note=" (component numbers are int32)")
+    if background is not None and not M.fits(background, labels.dtype):
         background = None                                     # a value the dtype cannot hold occurs nowhere
-    return stack, B, D, H, W, connectivity in (8, 26), background
+    return stack, B, D, H, W, full, background
 
 
 def _workspace(lib, what, dims, B, D, H, W, remove):
@@ -172,9 +137,9 @@ def connected_components(labels, connectivity=8, background=0, dims=2):
     with N.on_device(dev):
         cc = torch.empty(x.shape, dtype=torch.int32, device=dev)
         count = torch.empty(stack, dtype=torch.int64, device=dev)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = M.scratch(nbytes, dev)
         N.bump()
-        N.check(lib.ptb_cc_label(x.data_ptr(), _ELEM_BYTES[x.dtype], dims, B, D, H, W, connectivity, int(background is not None), background or 0,
+        N.check(lib.ptb_cc_label(x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, connectivity, int(background is not None), background or 0,
                                  cc.data_ptr(), count.data_ptr(), ws.data_ptr(), nbytes, N.stream_ptr(dev)), what)
     return cc, count
 
@@ -198,13 +163,13 @@ def component_stats(cc, count=None, values=None, max_components=None):
                          "loop over the entries of a stack")
     dims = cc.dim()
     if values is not None:
-        if not isinstance(values, torch.Tensor) or values.dtype not in _ELEM_BYTES:
+        if not isinstance(values, torch.Tensor) or values.dtype not in M.ELEM_BYTES:
             raise TypeError(f"{what}: values must be an integer label tensor (bool, uint8, int16, int32 or int64)")
         if values.shape != cc.shape or values.device != cc.device:
             raise ValueError(f"{what}: values {tuple(values.shape)} on {values.device} does not match cc {tuple(cc.shape)} on {cc.device}")
     if cc.numel() > MAX_POSITIONS:
         raise ValueError(f"{what}: {cc.numel()} positions; at most 2^31 - 2")
-    max_components = _check_int(what, "max_components", max_components, allow_none=True)
+    max_components = M.check_int(what, "max_components", max_components, allow_none=True)
     if max_components is not None:
         if max_components < 0:
             raise ValueError(f"{what}: max_components must be >= 0, got {max_components}")
@@ -232,7 +197,7 @@ def component_stats(cc, count=None, values=None, max_components=None):
     with N.on_device(dev):
         N.bump()
         N.check(lib.ptb_cc_stats(x.data_ptr(), dims, D, x.shape[-2], x.shape[-1], n, v.data_ptr() if v is not None else None,
-                                 _ELEM_BYTES[v.dtype] if v is not None else 0, out["area"].data_ptr(), out["bbox"].data_ptr(),
+                                 M.ELEM_BYTES[v.dtype] if v is not None else 0, out["area"].data_ptr(), out["bbox"].data_ptr(),
                                  out["value"].data_ptr() if v is not None else None, N.stream_ptr(dev)), what)
     return out
 
@@ -265,20 +230,15 @@ def remove_small_components(labels, min_area, connectivity=8, background=0, dims
     Needs no consecutive numbering, so it runs without the scan: no read-back, no synchronisation."""
     what = "remove_small_components"
     stack, B, D, H, W, full, bg = _geometry(what, labels, connectivity, background, dims)
-    min_area = _check_int(what, "min_area", min_area)
-    fill = _check_int(what, "fill", fill, allow_none=True)
+    min_area = M.check_int(what, "min_area", min_area)
+    fill = M.check_int(what, "fill", fill, allow_none=True)
     if fill is None:
         if background is None:
             raise ValueError(f"{what}: fill is required with background=None (there is no background to fill with)")
         fill = int(background)
-    if not _fits(fill, labels.dtype):
+    if not M.fits(fill, labels.dtype):
         raise ValueError(f"{what}: fill {fill} cannot be held by {labels.dtype}")
-    if out is not None:
-        if not isinstance(out, torch.Tensor):
-            raise TypeError(f"{what}: out must be a tensor, got {type(out).__name__}")
-        if out.dtype != labels.dtype or out.shape != labels.shape or out.device != labels.device:
-            raise ValueError(f"{what}: out must be a {labels.dtype} tensor of shape {tuple(labels.shape)} on {labels.device}, "
-                             f"got {out.dtype} {tuple(out.shape)} on {out.device}")
+    M.check_out(what, out, labels.dtype, labels)
     dev = labels.device
     if B * D * H * W == 0:
         return out if out is not None else labels.clone()
@@ -296,12 +256,8 @@ def remove_small_components(labels, min_area, connectivity=8, background=0, dims
         nbytes = _workspace(lib, what, dims, B, D, H, W, remove=True)
         with N.on_device(dev):
             res = out if out is not None and out.is_contiguous() else torch.empty_like(x)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws = M.scratch(nbytes, dev)
             N.bump()
-            N.check(lib.ptb_cc_remove_small(x.data_ptr(), _ELEM_BYTES[x.dtype], dims, B, D, H, W, connectivity, int(bg is not None), bg or 0, min_area,
+            N.check(lib.ptb_cc_remove_small(x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, connectivity, int(bg is not None), bg or 0, min_area,
                                             fill, res.data_ptr(), ws.data_ptr(), nbytes, N.stream_ptr(dev)), what)
-    if out is None:
-        return res
-    if res is not out:
-        out.copy_(res)
-    return out
+    return M.finish_out(out, res)

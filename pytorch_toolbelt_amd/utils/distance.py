@@ -7,103 +7,27 @@ the yardstick.  CUDA tensors run the HIP kernels of ``csrc/ptb_distance.hip`` (a
 computation), CPU tensors take the numpy form below with the same results -- the device the caller names decides.
 """
 import ctypes
-import math
 
 import numpy as np
 import torch
 
 from .. import _native as N
-from .components import _ELEM_BYTES, MAX_POSITIONS, _check_int, _fits
+from . import _maps as M
 
 __all__ = ["distance_transform", "class_distance_maps"]
 
-MAX_SQUARED = (1 << 31) - 2          # D^2 + H^2 + W^2 of one call: every squared index distance is an int32
-INT_INF = (1 << 31) - 1              # the int32 form of "no site in this entry"
-_SITES_EQUAL, _SITES_NOT_EQUAL = 0, 1
+MAX_POSITIONS, MAX_SQUARED, INT_INF = M.MAX_POSITIONS, M.MAX_SQUARED, M.INT_INF
 _SQUARED, _SIGNED = 1, 2
 _OUT_F32, _OUT_I32 = 0, 1
-_HOST_INF = 1 << 62
 PLANE_TRUTH, PLANE_PRED = 1, 2       # PTB_DLOSS_PLANE_*
 DEFAULT_WORKSPACE_CAP = 4 << 30
 
 
-# ---------------------------------------------------------------------------------------------------------------- validation
-def _geometry(what, labels, dims):
-    if not isinstance(labels, torch.Tensor):
-        raise TypeError(f"{what}: labels must be a tensor, got {type(labels).__name__}")
-    if labels.dtype not in _ELEM_BYTES:
-        raise TypeError(f"{what}: labels must hold integer labels (bool, uint8, int16, int32 or int64), got {labels.dtype}")
-    if dims not in (2, 3):
-        raise ValueError(f"{what}: dims must be 2 or 3, got {dims!r}")
-    if labels.dim() < dims:
-        raise ValueError(f"{what}: labels must be [*stack, {'D, ' if dims == 3 else ''}H, W] for dims={dims}, got {tuple(labels.shape)}")
-    D = labels.shape[-3] if dims == 3 else 1
-    H, W = labels.shape[-2], labels.shape[-1]
-    B = 1
-    for s in labels.shape[:-dims]:
-        B *= s
-    if B * D * H * W > MAX_POSITIONS:
-        raise ValueError(f"{what}: {B * D * H * W} positions in one call; at most 2^31 - 2 = {MAX_POSITIONS}: split the stack")
-    squares = (D * D if dims == 3 else 0) + H * H + W * W
-    if squares > MAX_SQUARED:
-        raise ValueError(f"{what}: {'D^2 + ' if dims == 3 else ''}H^2 + W^2 = {squares}; at most 2^31 - 2 = {MAX_SQUARED} (squared index distances are int32)")
-    return B, D, H, W
-
-
-def _spacing(what, spacing, dims):
-    if spacing is None:
-        return None
-    try:
-        sp = [float(v) for v in spacing]
-    except TypeError:
-        raise TypeError(f"{what}: spacing must be None or {dims} floats in {'z, ' if dims == 3 else ''}y, x order, got {spacing!r}") from None
-    if len(sp) != dims:
-        raise ValueError(f"{what}: spacing must have {dims} entries ({'z, ' if dims == 3 else ''}y, x) for dims={dims}, got {len(sp)}")
-    if not all(math.isfinite(v) and v > 0 for v in sp):
-        raise ValueError(f"{what}: spacing must be positive and finite, got {sp}")
-    return [1.0] * (3 - dims) + sp
-
-
 # ---------------------------------------------------------------------------------------------------------------- host form
-def _envelope_host(f, weight, inf):
-    """``g[l, i] = min_j f[l, j] + weight * (i - j)^2`` of every line ``l`` of ``f`` ([lines, n]; ``inf`` marks "no value").  Correct rather than
-    fast: the minimum is taken shift by shift, ``k = |i - j|`` = 1, 2, ... on both sides at once, over the lines that hold a value at all,
-    and ends when ``weight * k^2`` is no smaller than the largest value that could still improve (an unreached position counts as ``inf``,
-    so the shifts go on until every position of those lines is reached)."""
-    live = (f != inf).any(axis=1)
-    if not live.any():
-        return f
-    fl = f[live]
-    gl = fl.copy()
-    for k in range(1, f.shape[1]):
-        c = weight * (k * k)
-        if c >= gl.max():
-            break
-        np.minimum(gl[:, k:], fl[:, :-k] + c, out=gl[:, k:])
-        np.minimum(gl[:, :-k], fl[:, k:] + c, out=gl[:, :-k])
-    g = f.copy()
-    g[live] = gl
-    return g
-
-
 def _squared_host(sites, sp):
-    """squared distances to the sites of every entry of ``sites`` (bool [B, D, H, W]): int64 with ``_HOST_INF`` for unit spacing, float64 with
+    """squared distances to the sites of every entry of ``sites`` (bool [B, D, H, W]): int64 with ``HOST_INF`` for unit spacing, float64 with
     ``inf`` otherwise"""
-    if sp is None:
-        inf = _HOST_INF
-        f = np.where(sites, 0, inf).astype(np.int64)
-        weights = (1, 1, 1)
-    else:
-        inf = np.inf
-        f = np.where(sites, 0.0, inf)
-        weights = tuple(s * s for s in sp)
-    for axis in (3, 2, 1):
-        if f.shape[axis] == 1:
-            continue
-        lines = np.ascontiguousarray(np.moveaxis(f, axis, -1))
-        g = _envelope_host(lines.reshape(-1, lines.shape[-1]), weights[axis - 1], inf).reshape(lines.shape)
-        f = np.moveaxis(g, -1, axis)
-    return np.minimum(f, inf)
+    return M.edt_host(sites, sp)[0]
 
 
 def _host(labels, B, D, H, W, sites_equal, value, sp, squared, signed):
@@ -117,7 +41,7 @@ def _host(labels, B, D, H, W, sites_equal, value, sp, squared, signed):
         if sp is None and squared:
             return np.minimum(sq, INT_INF)
         if sp is None:
-            sq = np.where(sq >= _HOST_INF, np.inf, sq.astype(np.float64)).astype(np.float32)
+            sq = np.where(sq >= M.HOST_INF, np.inf, sq.astype(np.float64)).astype(np.float32)
         return sq if squared else np.sqrt(sq)
 
     res = final(_squared_host(sites, sp))
@@ -154,44 +78,35 @@ def distance_transform(labels, background=0, foreground=None, dims=2, spacing=No
     than 2^31 - 2 positions per call, or ``D^2 + H^2 + W^2 > 2^31 - 2``, raise ``ValueError`` before anything is launched; empty inputs
     return without a launch."""
     what = "distance_transform"
-    B, D, H, W = _geometry(what, labels, dims)
-    background = _check_int(what, "background", background, allow_none=True)
-    foreground = _check_int(what, "foreground", foreground, allow_none=True)
+    M.check_labels(what, "labels", labels)
+    _, B, D, H, W = M.extent(what, "labels", labels, dims, squares=True)
+    background = M.check_int(what, "background", background, allow_none=True)
+    foreground = M.check_int(what, "foreground", foreground, allow_none=True)
     if foreground is None and background is None:
         raise ValueError(f"{what}: background=None needs foreground= (there would be no site to measure to)")
     sites_equal = foreground is None
     value = background if sites_equal else foreground
-    sp = _spacing(what, spacing, dims)
+    sp = M.spacing(what, spacing, dims)
     squared, signed = bool(squared), bool(signed)
     dtype = torch.int32 if squared and sp is None else torch.float32
     dev = labels.device
-    if out is not None:
-        if not isinstance(out, torch.Tensor):
-            raise TypeError(f"{what}: out must be a tensor, got {type(out).__name__}")
-        if out.dtype != dtype or out.shape != labels.shape or out.device != dev:
-            raise ValueError(f"{what}: out must be a {dtype} tensor of shape {tuple(labels.shape)} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    M.check_out(what, out, dtype, labels)
     if B * D * H * W == 0:
         return out if out is not None else torch.empty(labels.shape, dtype=dtype, device=dev)
     if not labels.is_cuda:
-        res = torch.from_numpy(_host(labels.contiguous(), B, D, H, W, sites_equal, value if _fits(value, labels.dtype) else None, sp, squared, signed))
+        res = torch.from_numpy(_host(labels.contiguous(), B, D, H, W, sites_equal, value if M.fits(value, labels.dtype) else None, sp, squared, signed))
         res = res.reshape(labels.shape)
     else:
         lib = N.load()
         x = labels.contiguous()
-        nbytes = ctypes.c_int64()
-        N.check(lib.ptb_edt_plan(dims, B, D, H, W, int(signed), ctypes.byref(nbytes)), what)
         with N.on_device(dev):
-            res = out if out is not None and out.is_contiguous() and out.data_ptr() % 16 == 0 else torch.empty(x.shape, dtype=dtype, device=dev)
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            res = out if M.direct_out(out) else torch.empty(x.shape, dtype=dtype, device=dev)
+            ws, nbytes = M.workspace(lib.ptb_edt_plan, what, dev, dims, B, D, H, W, int(signed))
             N.bump()
-            N.check(lib.ptb_edt(x.data_ptr(), _ELEM_BYTES[x.dtype], dims, B, D, H, W, _SITES_EQUAL if sites_equal else _SITES_NOT_EQUAL, value,
+            N.check(lib.ptb_edt(x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, M.SITES_EQUAL if sites_equal else M.SITES_NOT_EQUAL, value,
                                 (ctypes.c_double * 3)(*sp) if sp is not None else None, (_SQUARED if squared else 0) | (_SIGNED if signed else 0),
-                                res.data_ptr(), _OUT_I32 if dtype == torch.int32 else _OUT_F32, ws.data_ptr(), nbytes.value, N.stream_ptr(dev)), what)
-    if out is None:
-        return res
-    if res is not out:
-        out.copy_(res)
-    return out
+                                res.data_ptr(), _OUT_I32 if dtype == torch.int32 else _OUT_F32, ws.data_ptr(), nbytes, N.stream_ptr(dev)), what)
+    return M.finish_out(out, res)
 
 
 # ---------------------------------------------------------------------------------------------------------------- per-class signed maps
@@ -205,7 +120,7 @@ def class_table(what, classes, C, device=None):
     if classes is None:
         return C, None, None, None
     try:
-        cls = tuple(_check_int(what, "classes", int(c) if isinstance(c, torch.Tensor) else c) for c in classes)
+        cls = tuple(M.check_int(what, "classes", int(c) if isinstance(c, torch.Tensor) else c) for c in classes)
     except TypeError:
         raise TypeError(f"{what}: classes must be None or a sequence of ints, got {classes!r}") from None
     if not cls:
@@ -257,7 +172,7 @@ def signed_maps_device(what, x, labels, dense, C, table, planes, prob, has_ignor
     with N.on_device(device):
         masks = torch.empty(E * S, dtype=torch.uint8, device=device)
         maps = torch.empty((R, B, K, S), dtype=torch.int32 if as_int else torch.float32, device=device)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        ws = M.scratch(nbytes, device)
         stream = N.stream_ptr(device)
         N.bump()
         N.check(lib.ptb_dloss_masks(x.data_ptr() if x is not None else None, labels.data_ptr() if labels is not None else None,
@@ -269,7 +184,7 @@ def signed_maps_device(what, x, labels, dense, C, table, planes, prob, has_ignor
         for e0 in range(0, E, chunk):
             n = min(chunk, E - e0)
             N.bump()
-            N.check(lib.ptb_edt(masks.data_ptr() + e0 * S, 1, dims, n, D, H, W, _SITES_EQUAL, 0, spacing, flags, maps.data_ptr() + 4 * e0 * S,
+            N.check(lib.ptb_edt(masks.data_ptr() + e0 * S, 1, dims, n, D, H, W, M.SITES_EQUAL, 0, spacing, flags, maps.data_ptr() + 4 * e0 * S,
                                 _OUT_I32 if as_int else _OUT_F32, ws.data_ptr(), nbytes, stream), what)
             chunks += 1
     return maps, chunks
@@ -301,24 +216,23 @@ def class_distance_maps(labels, num_classes=None, classes=None, dims=2, spacing=
     nothing is read back.  CPU tensors take the numpy form with the same results.  For the losses pass ``squared=True`` with unit
     spacing (the exact integers they use internally) and the distances themselves with ``spacing``."""
     what = "class_distance_maps"
-    if not isinstance(labels, torch.Tensor) or labels.dtype not in _ELEM_BYTES:
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in M.ELEM_BYTES:
         raise TypeError(f"{what}: labels must be an integer tensor (bool, uint8, int16, int32 or int64)")
-    if dims not in (2, 3):
-        raise ValueError(f"{what}: dims must be 2 or 3, got {dims!r}")
+    M.check_dims(what, dims)
     if labels.dim() != dims + 1:
         raise ValueError(f"{what}: labels must be [B, {'D, ' if dims == 3 else ''}H, W] for dims={dims}, got {tuple(labels.shape)}")
-    num_classes = _check_int(what, "num_classes", num_classes, allow_none=True)
+    num_classes = M.check_int(what, "num_classes", num_classes, allow_none=True)
     if num_classes is None:
         if classes is None:
             raise ValueError(f"{what}: give num_classes= or classes=")
         num_classes = max(int(c) for c in classes) + 1 if len(classes) else 1
     if not 1 <= num_classes < (1 << 31):
         raise ValueError(f"{what}: num_classes must be positive, got {num_classes}")
-    ignore_index = _check_int(what, "ignore_index", ignore_index, allow_none=True)
-    cap = _check_int(what, "max_workspace_bytes", max_workspace_bytes)
+    ignore_index = M.check_int(what, "ignore_index", ignore_index, allow_none=True)
+    cap = M.check_int(what, "max_workspace_bytes", max_workspace_bytes)
     if cap < 0:
         raise ValueError(f"{what}: max_workspace_bytes must not be negative, got {cap}")
-    sp = _spacing(what, spacing, dims)
+    sp = M.spacing(what, spacing, dims)
     squared = bool(squared)
     table = class_table(what, classes, num_classes, labels.device)
     K, cls = table[0], table[1] if table[1] is not None else tuple(range(num_classes))
@@ -326,7 +240,7 @@ def class_distance_maps(labels, num_classes=None, classes=None, dims=2, spacing=
     spatial = tuple(labels.shape[1:])
     D = spatial[0] if dims == 3 else 1
     H, W = spatial[-2], spatial[-1]
-    _geometry(what, labels[:1] if B else labels, dims)
+    M.extent(what, "labels", labels[:1] if B else labels, dims, squares=True)
     dtype = torch.int32 if squared and sp is None else torch.float32
     if B * D * H * W == 0:
         return torch.empty((B, K) + spatial, dtype=dtype, device=labels.device)

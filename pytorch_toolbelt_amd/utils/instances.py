@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from .components import _ELEM_BYTES, MAX_POSITIONS, _check_int
+from . import _maps as M
 
 __all__ = ["instance_overlaps", "match_instances"]
 
@@ -45,8 +45,8 @@ def _maps(what, pred, truth):
         raise ValueError(f"{what}: pred and truth must have the same shape, got {tuple(pred.shape)} and {tuple(truth.shape)}")
     if pred.device != truth.device:
         raise ValueError(f"{what}: pred and truth must be on the same device, got {pred.device} and {truth.device}")
-    if pred.numel() > MAX_POSITIONS:
-        raise ValueError(f"{what}: {pred.numel()} positions; at most 2^31 - 2 = {MAX_POSITIONS}")
+    if pred.numel() > M.MAX_POSITIONS:
+        raise ValueError(f"{what}: {pred.numel()} positions; at most 2^31 - 2 = {M.MAX_POSITIONS}")
 
 
 def _count(what, name, v, ids):
@@ -58,15 +58,15 @@ def _count(what, name, v, ids):
     elif v is None:
         n = max(int(ids.max().item()), 0) if ids.numel() else 0
     else:
-        n = _check_int(what, name, v)
+        n = M.check_int(what, name, v)
     if n < 0:
         raise ValueError(f"{what}: {name} is {n}{': the labelling failed' if isinstance(v, torch.Tensor) else '; it must be >= 0'}")
-    return min(n, MAX_POSITIONS)
+    return min(n, M.MAX_POSITIONS)
 
 
 def _pairs_cap(what, max_pairs, positions, n_p, n_t):
     """``(m, given)``: the rows the table is sized for"""
-    max_pairs = _check_int(what, "max_pairs", max_pairs, allow_none=True)
+    max_pairs = M.check_int(what, "max_pairs", max_pairs, allow_none=True)
     if max_pairs is None:
         return min(positions, n_p * n_t, DEFAULT_MAX_PAIRS), False       # (a pair needs a position, and an id of each side)
     if not 0 <= max_pairs <= MAX_PAIRS:
@@ -96,11 +96,11 @@ def _classes(what, pred_class, truth_class, num_classes, n_p, n_t, dev):
         return 0
     if not all(given):
         raise ValueError(f"{what}: pred_class, truth_class and num_classes are given together or not at all")
-    K = _check_int(what, "num_classes", num_classes)
+    K = M.check_int(what, "num_classes", num_classes)
     if not 1 <= K <= MAX_CLASSES:
         raise ValueError(f"{what}: num_classes must lie in 1 .. {MAX_CLASSES}, got {K}")
     for name, c, n in (("pred_class", pred_class, n_p), ("truth_class", truth_class, n_t)):
-        if not isinstance(c, torch.Tensor) or c.dtype not in _ELEM_BYTES:
+        if not isinstance(c, torch.Tensor) or c.dtype not in M.ELEM_BYTES:
             raise TypeError(f"{what}: {name} must be an integer tensor (bool, uint8, int16, int32 or int64)")
         if tuple(c.shape) != (n,) or c.device != dev:
             raise ValueError(f"{what}: {name} must be of shape ({n},) on {dev} (one class per instance), got {tuple(c.shape)} on {c.device}")
@@ -190,8 +190,8 @@ def _device(what, pred, truth, n_p, n_t, m, taus, K, pred_class, truth_class):
     N.check(rc, what)
     p, t = pred.contiguous(), truth.contiguous()
     with N.on_device(dev):
-        out = torch.empty(out_bytes.value, dtype=torch.uint8, device=dev)
-        ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device=dev)
+        out = M.scratch(out_bytes.value, dev)
+        ws = M.scratch(ws_bytes.value, dev)
         N.bump()
         if T == 0:
             rc = lib.ptb_inst_overlaps(p.data_ptr(), t.data_ptr(), positions, n_p, n_t, m, out.data_ptr(), out_bytes.value, ws.data_ptr(), ws_bytes.value,
@@ -200,8 +200,8 @@ def _device(what, pred, truth, n_p, n_t, m, taus, K, pred_class, truth_class):
             pc = pred_class.contiguous() if K else None
             tc = truth_class.contiguous() if K else None
             rc = lib.ptb_inst_match(p.data_ptr(), t.data_ptr(), positions, n_p, n_t, m, (ctypes.c_double * T)(*taus), T,
-                                    pc.data_ptr() if K else None, _ELEM_BYTES[pc.dtype] if K else 0, tc.data_ptr() if K else None,
-                                    _ELEM_BYTES[tc.dtype] if K else 0, K, out.data_ptr(), out_bytes.value, ws.data_ptr(), ws_bytes.value, N.stream_ptr(dev))
+                                    pc.data_ptr() if K else None, M.ELEM_BYTES[pc.dtype] if K else 0, tc.data_ptr() if K else None,
+                                    M.ELEM_BYTES[tc.dtype] if K else 0, K, out.data_ptr(), out_bytes.value, ws.data_ptr(), ws_bytes.value, N.stream_ptr(dev))
         N.check(rc, what)
     rows = m if T == 0 else 0
     shapes = {"num_pairs": (), "pred_area": (n_p,), "truth_area": (n_t,), "pairs": (rows, 2), "intersection": (rows,), "pred_match": (n_p,) if T else (0,),

@@ -10,21 +10,14 @@ tensors take torch ops with the same results -- the device the caller names deci
 import torch
 
 from .. import _native as N
+from . import _maps as M
 
 __all__ = ["confusion_matrix", "confusion_matrix_from_logits", "segmentation_scores"]
 
-_ELEM_BYTES = {torch.bool: 1, torch.uint8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
 MAX_NATIVE_CLASSES = 256
 
 
 # ---------------------------------------------------------------------------------------------------------------- validation
-def _check_labels(what, name, t):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-    if t.dtype not in _ELEM_BYTES:
-        raise TypeError(f"{what}: {name} must hold integer labels (bool, uint8, int16, int32 or int64), got {t.dtype}")
-
-
 def _check_ignore(what, ignore_index):
     if ignore_index is None:
         return None
@@ -93,8 +86,8 @@ def confusion_matrix(pred, target, num_classes, ignore_index=None, per_sample=Fa
     ``K <= 256`` is served natively; a larger ``K`` on a CUDA tensor raises ``NotImplementedError``.  Empty inputs give zeros (or ``out``
     unchanged) without a launch."""
     what = "confusion_matrix"
-    _check_labels(what, "pred", pred)
-    _check_labels(what, "target", target)
+    M.check_labels(what, "pred", pred)
+    M.check_labels(what, "target", target)
     if pred.shape != target.shape:
         raise ValueError(f"{what}: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
     if pred.device != target.device:
@@ -136,7 +129,7 @@ def _labels_native(pred, target, B, n, K, ignore_index, out):
     with N.on_device(dev):
         invalid = torch.zeros(1, dtype=torch.int64, device=dev)
         N.bump()
-        N.check(lib.ptb_confusion_labels(pred.data_ptr(), _ELEM_BYTES[pred.dtype], target.data_ptr(), _ELEM_BYTES[target.dtype], B, n, K,
+        N.check(lib.ptb_confusion_labels(pred.data_ptr(), M.ELEM_BYTES[pred.dtype], target.data_ptr(), M.ELEM_BYTES[target.dtype], B, n, K,
                                          int(ignore_index is not None), ignore_index or 0, out.data_ptr(), invalid.data_ptr(), N.stream_ptr(dev)),
                 "confusion_matrix")
     return invalid
@@ -159,7 +152,7 @@ def confusion_matrix_from_logits(logits, target, ignore_index=None, threshold=0.
         raise TypeError(f"{what}: logits must be a tensor, got {type(logits).__name__}")
     if logits.dtype not in N.DTYPE_CODES:
         raise TypeError(f"{what}: logits must be float32, float16 or bfloat16, got {logits.dtype}")
-    _check_labels(what, "target", target)
+    M.check_labels(what, "target", target)
     if logits.dim() < 2:
         raise ValueError(f"{what}: logits must be [N, C, *S], got {tuple(logits.shape)}")
     if tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
@@ -189,7 +182,7 @@ def confusion_matrix_from_logits(logits, target, ignore_index=None, threshold=0.
         with N.on_device(dev):
             invalid = torch.zeros(1, dtype=torch.int64, device=dev)
             N.bump()
-            N.check(lib.ptb_confusion_logits(dense.data_ptr(), N.DTYPE_CODES[dense.dtype], Nb, C, S, threshold, tgt.data_ptr(), _ELEM_BYTES[tgt.dtype],
+            N.check(lib.ptb_confusion_logits(dense.data_ptr(), N.DTYPE_CODES[dense.dtype], Nb, C, S, threshold, tgt.data_ptr(), M.ELEM_BYTES[tgt.dtype],
                                              int(bool(per_sample)), int(ignore_index is not None), ignore_index or 0, out.data_ptr(), invalid.data_ptr(),
                                              N.stream_ptr(dev)), what)
         if strict:

@@ -20,8 +20,7 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from .components import _ELEM_BYTES, _check_int, _fits
-from .distance import _HOST_INF, _SITES_EQUAL, _SITES_NOT_EQUAL, INT_INF, _geometry, _spacing
+from . import _maps as M
 
 __all__ = ["nearest_site", "expand_labels"]
 
@@ -29,55 +28,10 @@ _INDEX, _SQUARED, _GATHER, _MAX_SQ = 1, 2, 4, 8
 
 
 # ---------------------------------------------------------------------------------------------------------------- host form
-def _envelope_host(f, feat, weight, inf):
-    """``g[l, i] = min_j f[l, j] + weight * (i - j)^2`` of every line of ``f`` ([lines, n]; ``inf``: no value) and ``feat[l, j]`` at the
-    minimising ``j``, the SMALLEST such ``j``.  The minimum is taken shift by shift, ``k = |i - j|`` = 1, 2, ... on both sides at once: the
-    left candidate ``j = i - k`` is smaller than every ``j`` tried before it and so wins a tie, the right one is larger and loses it.  Ends
-    when ``weight * k^2`` exceeds every value (an equal one could still tie)."""
-    live = (f != inf).any(axis=1)
-    if not live.any():
-        return f, feat
-    fl, tl = f[live], feat[live]
-    gl, hl = fl.copy(), tl.copy()
-    for k in range(1, f.shape[1]):
-        c = weight * (k * k)
-        if c > gl.max():
-            break
-        cand = fl[:, :-k] + c
-        take = cand <= gl[:, k:]
-        gl[:, k:][take] = cand[take]
-        hl[:, k:][take] = tl[:, :-k][take]
-        cand = fl[:, k:] + c
-        take = cand < gl[:, :-k]
-        gl[:, :-k][take] = cand[take]
-        hl[:, :-k][take] = tl[:, k:][take]
-    g, h = f.copy(), feat.copy()
-    g[live], h[live] = gl, hl
-    return g, h
-
-
 def _feature_host(sites, sp):
     """``(squared distance, index of the nearest site within the entry)`` of every position of ``sites`` (bool [B, D, H, W]): int64 with
-    ``_HOST_INF`` for unit spacing, float64 with ``inf`` otherwise; int64 indices, -1 without a site"""
-    B, D, H, W = sites.shape
-    if sp is None:
-        inf = _HOST_INF
-        f = np.where(sites, 0, inf).astype(np.int64)
-        weights = (1, 1, 1)
-    else:
-        inf = np.inf
-        f = np.where(sites, 0.0, inf)
-        weights = tuple(s * s for s in sp)
-    feat = np.where(sites, np.arange(D * H * W, dtype=np.int64).reshape(1, D, H, W), -1)
-    for axis in (3, 2, 1):
-        if f.shape[axis] == 1:
-            continue
-        lines = np.ascontiguousarray(np.moveaxis(f, axis, -1))
-        flines = np.ascontiguousarray(np.moveaxis(feat, axis, -1))
-        g, h = _envelope_host(lines.reshape(-1, lines.shape[-1]), flines.reshape(-1, lines.shape[-1]), weights[axis - 1], inf)
-        f = np.moveaxis(g.reshape(lines.shape), -1, axis)
-        feat = np.moveaxis(h.reshape(lines.shape), -1, axis)
-    return np.minimum(f, inf), np.where(f >= inf, -1, feat)
+    ``HOST_INF`` for unit spacing, float64 with ``inf`` otherwise; int64 indices, -1 without a site"""
+    return M.edt_host(sites, sp, index=True)
 
 
 def _sites_host(labels, B, D, H, W, sites_equal, value):
@@ -89,34 +43,18 @@ def _sites_host(labels, B, D, H, W, sites_equal, value):
 
 def _squared_form(sq, sp):
     """the stored form of the squared distances: int32 with INT_INF for unit spacing, float32 otherwise"""
-    return np.minimum(sq, INT_INF).astype(np.int32) if sp is None else sq.astype(np.float32)
+    return np.minimum(sq, M.INT_INF).astype(np.int32) if sp is None else sq.astype(np.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------------- native call
-def _check_out(what, out, dtype, like):
-    if out is None:
-        return
-    if not isinstance(out, torch.Tensor):
-        raise TypeError(f"{what}: out must be a tensor, got {type(out).__name__}")
-    if out.dtype != dtype or out.shape != like.shape or out.device != like.device:
-        raise ValueError(f"{what}: out must be a {dtype} tensor of shape {tuple(like.shape)} on {like.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-
-
-def _usable(out, x=None):
-    """can the kernels write ``out`` directly?  (contiguous, aligned, and not the memory they gather from)"""
-    return out is not None and out.is_contiguous() and out.data_ptr() % 16 == 0 and (x is None or out.untyped_storage().data_ptr() != x.untyped_storage().data_ptr())
-
-
 def _native(what, x, dims, B, D, H, W, sites_equal, value, sp, flags, index=None, squared=None, gather=None, mask=None, max_sq=0.0):
     lib = N.load()
-    nbytes = ctypes.c_int64()
-    N.check(lib.ptb_nearest_plan(dims, B, D, H, W, flags, ctypes.byref(nbytes)), what)
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None       # noqa: E731
+    ws, nbytes = M.workspace(lib.ptb_nearest_plan, what, x.device, dims, B, D, H, W, flags)
+    ptr = M.opt_ptr
     N.bump()
-    N.check(lib.ptb_nearest(x.data_ptr(), _ELEM_BYTES[x.dtype], dims, B, D, H, W, _SITES_EQUAL if sites_equal else _SITES_NOT_EQUAL, value,
+    N.check(lib.ptb_nearest(x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, M.SITES_EQUAL if sites_equal else M.SITES_NOT_EQUAL, value,
                             (ctypes.c_double * 3)(*sp) if sp is not None else None, flags, ptr(index), ptr(squared), ptr(gather), ptr(mask), max_sq,
-                            ws.data_ptr(), nbytes.value, N.stream_ptr(x.device)), what)
+                            ws.data_ptr(), nbytes, N.stream_ptr(x.device)), what)
 
 
 # ---------------------------------------------------------------------------------------------------------------- public
@@ -141,36 +79,35 @@ def nearest_site(labels, background=0, foreground=None, dims=2, spacing=None, re
     The result is a function of the input alone: the same bits on every run.  The limits raise ``ValueError`` before anything is
     launched; empty inputs return without a launch."""
     what = "nearest_site"
-    B, D, H, W = _geometry(what, labels, dims)
-    background = _check_int(what, "background", background, allow_none=True)
-    foreground = _check_int(what, "foreground", foreground, allow_none=True)
+    M.check_labels(what, "labels", labels)
+    _, B, D, H, W = M.extent(what, "labels", labels, dims, squares=True)
+    background = M.check_int(what, "background", background, allow_none=True)
+    foreground = M.check_int(what, "foreground", foreground, allow_none=True)
     if foreground is None and background is None:
         raise ValueError(f"{what}: background=None needs foreground= (there would be no site to measure to)")
     sites_equal = foreground is None
     value = background if sites_equal else foreground
-    sp = _spacing(what, spacing, dims)
+    sp = M.spacing(what, spacing, dims)
     return_distance = bool(return_distance)
     sq_dtype = torch.int32 if sp is None else torch.float32
     dev = labels.device
-    _check_out(what, out, torch.int32, labels)
+    M.check_out(what, out, torch.int32, labels)
     sq = None
     if B * D * H * W == 0:
         index = out if out is not None else torch.empty(labels.shape, dtype=torch.int32, device=dev)
         sq = torch.empty(labels.shape, dtype=sq_dtype, device=dev)
     elif not labels.is_cuda:
-        sites = _sites_host(labels.contiguous(), B, D, H, W, sites_equal, value if _fits(value, labels.dtype) else None)
+        sites = _sites_host(labels.contiguous(), B, D, H, W, sites_equal, value if M.fits(value, labels.dtype) else None)
         d, feat = _feature_host(sites, sp)
         index = torch.from_numpy(feat.astype(np.int32)).reshape(labels.shape)
         sq = torch.from_numpy(_squared_form(d, sp)).reshape(labels.shape)
     else:
         x = labels.contiguous()
         with N.on_device(dev):
-            index = out if _usable(out) else torch.empty(x.shape, dtype=torch.int32, device=dev)
+            index = out if M.direct_out(out) else torch.empty(x.shape, dtype=torch.int32, device=dev)
             sq = torch.empty(x.shape, dtype=sq_dtype, device=dev) if return_distance else None
             _native(what, x, dims, B, D, H, W, sites_equal, value, sp, _INDEX | (_SQUARED if return_distance else 0), index=index, squared=sq)
-    if out is not None and index is not out:
-        out.copy_(index)
-        index = out
+    index = M.finish_out(out, index)
     return (index, sq) if return_distance else index
 
 
@@ -195,13 +132,10 @@ def expand_labels(markers, distance=None, mask=None, background=0, dims=2, spaci
     the inputs alone: the same bits on every run.  The limits raise ``ValueError`` before anything is launched; empty inputs return
     without a launch."""
     what = "expand_labels"
-    if not isinstance(markers, torch.Tensor):
-        raise TypeError(f"{what}: markers must be a tensor, got {type(markers).__name__}")
-    if markers.dtype not in _ELEM_BYTES:
-        raise TypeError(f"{what}: markers must hold integer labels (bool, uint8, int16, int32 or int64), got {markers.dtype}")
-    B, D, H, W = _geometry(what, markers, dims)
-    background = _check_int(what, "background", background)
-    sp = _spacing(what, spacing, dims)
+    M.check_labels(what, "markers", markers)
+    _, B, D, H, W = M.extent(what, "labels", markers, dims, squares=True)      # (the rank message has always said "labels")
+    background = M.check_int(what, "background", background)
+    sp = M.spacing(what, spacing, dims)
     if distance is not None:
         if isinstance(distance, (bool, np.bool_)) or not isinstance(distance, (int, float, np.integer, np.floating)):
             raise TypeError(f"{what}: distance must be None or a float, got {distance!r}")
@@ -210,23 +144,18 @@ def expand_labels(markers, distance=None, mask=None, background=0, dims=2, spaci
             raise ValueError(f"{what}: distance must be finite and >= 0, got {distance}")
     dev = markers.device
     if mask is not None:
-        if not isinstance(mask, torch.Tensor):
-            raise TypeError(f"{what}: mask must be a tensor, got {type(mask).__name__}")
-        if mask.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"{what}: mask must be bool or uint8, got {mask.dtype}")
-        if mask.shape != markers.shape or mask.device != dev:
-            raise ValueError(f"{what}: mask must have shape {tuple(markers.shape)} on {dev}, got {tuple(mask.shape)} on {mask.device}")
-    _check_out(what, out, markers.dtype, markers)
+        M.check_like(what, "mask", mask, markers, (torch.bool, torch.uint8))
+    M.check_out(what, out, markers.dtype, markers)
     if B * D * H * W == 0:
         return out if out is not None else torch.empty(markers.shape, dtype=markers.dtype, device=dev)
     max_sq = 0.0
     if distance is not None:
         max_sq = distance * distance
         if sp is None:
-            max_sq = float(min(math.floor(max_sq), INT_INF))
+            max_sq = float(min(math.floor(max_sq), M.INT_INF))
     if not markers.is_cuda:
         x = markers.contiguous()
-        fits = _fits(background, markers.dtype)
+        fits = M.fits(background, markers.dtype)
         d, feat = _feature_host(_sites_host(x, B, D, H, W, False, background if fits else None), sp)
         a = x.reshape(B, -1).numpy()
         feat = feat.reshape(B, -1)
@@ -245,10 +174,6 @@ def expand_labels(markers, distance=None, mask=None, background=0, dims=2, spaci
         x = markers.contiguous()
         m = mask.contiguous() if mask is not None else None
         with N.on_device(dev):
-            res = out if _usable(out, x) else torch.empty(x.shape, dtype=x.dtype, device=dev)
+            res = out if M.direct_out(out, x) else torch.empty(x.shape, dtype=x.dtype, device=dev)
             _native(what, x, dims, B, D, H, W, False, background, sp, _GATHER | (_MAX_SQ if distance is not None else 0), gather=res, mask=m, max_sq=max_sq)
-    if out is None:
-        return res
-    if res is not out:
-        out.copy_(res)
-    return out
+    return M.finish_out(out, res)

@@ -50,15 +50,13 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from .components import MAX_POSITIONS, _check_int
-from .nearest import _check_out
+from . import _maps as M
 
 __all__ = ["reconstruction", "regional_maxima", "regional_minima", "h_maxima", "h_minima", "fill_holes"]
 
 _VALUES, _EXTREMA, _H_EXTREMA, _FILL = range(4)             # PTB_RECONSTRUCT_*
-_CODES = {torch.float32: N.F32, torch.float16: N.F16, torch.bfloat16: N.BF16, torch.uint8: N.U8, torch.int16: N.I16, torch.bool: N.U8}
+_CODES = {**M.VALUE_CODES, torch.bool: N.U8}
 _TOP = {torch.float32: math.inf, torch.float16: math.inf, torch.bfloat16: math.inf, torch.uint8: 255.0, torch.int16: 32767.0, torch.bool: 1.0}
-_CONNECTIVITIES = {2: (4, 8), 3: (6, 26)}
 DEFAULT_MAX_SWEEPS = 1 << 16         # per phase; a sweep carries a value at least one tile on, so only a path that winds through more tiles gets here
 _PHASES = {_VALUES: ("reconstruction",), _EXTREMA: ("regional-extrema",), _H_EXTREMA: ("h-reconstruction", "regional-extrema"), _FILL: ("hole-filling",)}
 _LOWEST = 0x007FFFFF                 # the smallest key of a value; 0 is the key of a position outside the domain
@@ -144,39 +142,18 @@ def _host(op, erosion, seed, mask, domain, h, dims, full, shape3, out_dtype):
 
 
 # ---------------------------------------------------------------------------------------------------------------- public
-def _check_values(what, name, t, fill=False):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-    if t.dtype not in _CODES or (t.dtype == torch.bool and not fill):
-        raise TypeError(f"{what}: {name} must be float32, float16, bfloat16, uint8 or int16{' or bool' if fill else ''}, got {t.dtype}: "
-                        f"pass {name}.float() if every value is exact in float32")
-
-
 def _run(what, op, erosion, seed, mask, name, h, connectivity, domain, dims, out, max_sweeps, return_sweeps, default_full=True):
-    _check_values(what, name, mask, fill=op == _FILL)
-    if dims not in _CONNECTIVITIES:
-        raise ValueError(f"{what}: dims must be 2 or 3, got {dims!r}")
-    if connectivity is None:
-        connectivity = _CONNECTIVITIES[dims][1 if default_full else 0]
-    if isinstance(connectivity, bool) or connectivity not in _CONNECTIVITIES[dims]:
-        a, b = _CONNECTIVITIES[dims]
-        raise ValueError(f"{what}: connectivity must be {a} or {b} for dims={dims} (or None), got {connectivity!r}")
-    if mask.dim() < dims:
-        raise ValueError(f"{what}: {name} must be [*stack, {'D, ' if dims == 3 else ''}H, W] for dims={dims}, got {tuple(mask.shape)}")
+    M.check_values(what, name, mask, or_bool=op == _FILL)
+    connectivity, full = M.check_connectivity(what, connectivity, dims, default=1 if default_full else 0, note=" (or None)")
+    _, B, D, H, W = M.extent(what, name, mask, dims)
     dev = mask.device
     if seed is not None:
-        _check_values(what, "seed", seed)
+        M.check_values(what, "seed", seed)
         if seed.dtype != mask.dtype:
             raise TypeError(f"{what}: seed and mask must have the same dtype, got {seed.dtype} and {mask.dtype}")
-        if seed.shape != mask.shape or seed.device != dev:
-            raise ValueError(f"{what}: seed must have shape {tuple(mask.shape)} on {dev}, got {tuple(seed.shape)} on {seed.device}")
+        M.check_like(what, "seed", seed, mask)
     if domain is not None:
-        if not isinstance(domain, torch.Tensor):
-            raise TypeError(f"{what}: domain must be a tensor, got {type(domain).__name__}")
-        if domain.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"{what}: domain must be bool or uint8, got {domain.dtype}")
-        if domain.shape != mask.shape or domain.device != dev:
-            raise ValueError(f"{what}: domain must have shape {tuple(mask.shape)} on {dev}, got {tuple(domain.shape)} on {domain.device}")
+        M.check_like(what, "domain", domain, mask, (torch.bool, torch.uint8))
     if op == _H_EXTREMA:
         if isinstance(h, (bool, np.bool_)) or not isinstance(h, (int, float, np.integer, np.floating)):
             raise TypeError(f"{what}: h must be a number, got {h!r}")
@@ -184,53 +161,32 @@ def _run(what, op, erosion, seed, mask, name, h, connectivity, domain, dims, out
             h = float(np.float32(h))
         if not (h >= 0.0 and math.isfinite(h)):
             raise ValueError(f"{what}: h must be finite and >= 0 in float32, got {h!r}")
-    if max_sweeps is None:
-        max_sweeps = DEFAULT_MAX_SWEEPS
-    else:
-        max_sweeps = _check_int(what, "max_sweeps", max_sweeps)
-        if not 1 <= max_sweeps < (1 << 31):
-            raise ValueError(f"{what}: max_sweeps must be in [1, 2^31 - 1], got {max_sweeps}")
+    max_sweeps = M.check_max_sweeps(what, max_sweeps, DEFAULT_MAX_SWEEPS)
     out_dtype = torch.bool if op in (_EXTREMA, _H_EXTREMA) else mask.dtype
-    _check_out(what, out, out_dtype, mask)
-    D = mask.shape[-3] if dims == 3 else 1
-    H, W = mask.shape[-2], mask.shape[-1]
-    B = 1
-    for s in mask.shape[:-dims]:
-        B *= s
-    if B * D * H * W > MAX_POSITIONS:
-        raise ValueError(f"{what}: {B * D * H * W} positions in one call; at most 2^31 - 2 = {MAX_POSITIONS}: split the stack")
-    full = connectivity == _CONNECTIVITIES[dims][1]
+    M.check_out(what, out, out_dtype, mask)
     sweeps = (0, 0)
     if B * D * H * W == 0:
         res = out if out is not None else torch.empty(mask.shape, dtype=out_dtype, device=dev)
     elif not mask.is_cuda:
         res = _host(op, erosion, seed, mask, domain, h, dims, full, (B,) + tuple(mask.shape[mask.dim() - dims:]), out_dtype).reshape(mask.shape)
     else:
-        as_bytes = lambda t: t.view(torch.uint8) if t.dtype == torch.bool else t       # noqa: E731
         m = mask.contiguous()
         s = seed.contiguous() if seed is not None else None
         k = domain.contiguous() if domain is not None else None
-        inputs = [t.untyped_storage().data_ptr() for t in (m, s, k) if t is not None]
-        direct = out is not None and out.is_contiguous() and out.data_ptr() % 16 == 0 and out.untyped_storage().data_ptr() not in inputs
         with N.on_device(dev):
-            res = out if direct else torch.empty(m.shape, dtype=out_dtype, device=dev)
+            res = out if M.direct_out(out, m, s, k) else torch.empty(m.shape, dtype=out_dtype, device=dev)
             lib = N.load()
-            nbytes = ctypes.c_int64()
-            N.check(lib.ptb_reconstruct_plan(dims, B, D, H, W, op, ctypes.byref(nbytes)), what)
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-            ptr = lambda t: as_bytes(t).data_ptr() if t is not None else None          # noqa: E731
+            ws, nbytes = M.workspace(lib.ptb_reconstruct_plan, what, dev, dims, B, D, H, W, op)
+            ptr = M.opt_ptr                                             # (a bool tensor's bytes are the uint8 the kernels read)
             took = (ctypes.c_int * 2)(-1, -1)
             N.bump()
             rc = lib.ptb_reconstruct(ptr(s), ptr(m), _CODES[m.dtype], ptr(k), dims, B, D, H, W, connectivity, op, int(erosion), h if op == _H_EXTREMA else 0.0,
-                                     _TOP[m.dtype] if op == _FILL else math.inf, max_sweeps, ptr(res), took, ws.data_ptr(), nbytes.value, N.stream_ptr(dev))
+                                     _TOP[m.dtype] if op == _FILL else math.inf, max_sweeps, ptr(res), took, ws.data_ptr(), nbytes, N.stream_ptr(dev))
             if rc == N.PTB_ENOTCONVERGED:
-                phase = 0 if took[1] < 0 else 1
-                raise RuntimeError(f"{what}: phase {phase + 1} (the {_PHASES[op][phase]} relaxation) did not converge within max_sweeps={max_sweeps}: {took[phase]} sweeps run")
+                M.raise_not_converged(what, _PHASES[op], took, max_sweeps)
             N.check(rc, what)
             sweeps = (int(took[0]), max(int(took[1]), 0))
-    if out is not None and res is not out:
-        out.copy_(res)
-        res = out
+    res = M.finish_out(out, res)
     return (res, sweeps) if return_sweeps else res
 
 

@@ -13,10 +13,10 @@ import numpy as np
 import torch
 
 from .. import _native as N
+from . import _maps as M
 
 __all__ = ["rle_decode", "rle_encode", "rle_to_string", "rle_encode_device", "rle_decode_device"]
 
-_ELEM_BYTES = {torch.bool: 1, torch.uint8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
 _DECODE_DTYPES = (torch.bool, torch.uint8)
 
 
@@ -124,7 +124,7 @@ def rle_encode_device(mask: torch.Tensor, labels=None):
         raise TypeError("rle_encode_device: mask must be a tensor (rle_encode takes numpy arrays)")
     if mask.dim() not in (2, 3):
         raise ValueError(f"rle_encode_device: mask must be [H, W] or [B, H, W], got {tuple(mask.shape)}")
-    if mask.dtype not in _ELEM_BYTES:
+    if mask.dtype not in M.ELEM_BYTES:
         raise NotImplementedError(f"rle_encode_device: mask dtype {mask.dtype} (bool, uint8, int16, int32 and int64 are encoded)")
     label_list = None if labels is None else _label_list(labels)
     stack = mask if mask.dim() == 3 else mask[None]
@@ -137,17 +137,10 @@ def rle_encode_device(mask: torch.Tensor, labels=None):
     else:
         flat = []
         for b in range(B):
-            fgs = [stack[b] != 0] if label_list is None else [stack[b] == c if _fits(c, mask.dtype) else torch.zeros((H, W), dtype=torch.bool) for c in label_list]
+            fgs = [stack[b] != 0] if label_list is None else [stack[b] == c if M.fits(c, mask.dtype) else torch.zeros((H, W), dtype=torch.bool) for c in label_list]
             flat.append([_encode_host(fg) for fg in fgs])
     per_slice = [row[0] for row in flat] if label_list is None else flat
     return per_slice if mask.dim() == 3 else per_slice[0]
-
-
-def _fits(c, dtype):
-    if dtype == torch.bool:
-        return c in (0, 1)
-    info = torch.iinfo(dtype)
-    return info.min <= c <= info.max
 
 
 def _encode_native(stack, label_list):
@@ -159,10 +152,10 @@ def _encode_native(stack, label_list):
     if nbytes < 0:
         N.check(int(nbytes), "rle_encode_device")
     dev = stack.device
-    eb = _ELEM_BYTES[stack.dtype]
+    eb = M.ELEM_BYTES[stack.dtype]
     lab = N.i64_array(label_list) if K else None
     with N.on_device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = M.scratch(nbytes, dev)
         stream = N.stream_ptr(dev)
         N.bump()
         N.check(lib.ptb_rle_count(stack.data_ptr(), eb, B, H, W, lab, K, ws.data_ptr(), nbytes, stream), "rle_encode_device (count)")
@@ -219,7 +212,7 @@ def rle_decode_device(runs, shape, dtype=torch.uint8, device=None):
     if nbytes < 0:
         N.check(int(nbytes), "rle_decode_device")
     with N.on_device(device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        ws = M.scratch(nbytes, device)
         N.bump()
         N.check(lib.ptb_rle_decode(dev_runs.data_ptr(), dev_runs.numel() // 2, H, W, mask.data_ptr(), ws.data_ptr(), nbytes, N.stream_ptr(device)),
                 "rle_decode_device")

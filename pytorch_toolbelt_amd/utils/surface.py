@@ -15,8 +15,7 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from . import distance as _distance
-from .components import _CONNECTIVITIES, _ELEM_BYTES, _check_int, _fits
+from . import _maps as M
 
 __all__ = ["surface_metrics"]
 
@@ -43,26 +42,16 @@ def _floats(what, name, v, lo, hi, most):
 
 def _arguments(what, pred, truth, labels, background, dims, spacing, connectivity, percentile, tolerance, max_workspace_bytes):
     for name, t in (("pred", pred), ("truth", truth)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-        if t.dtype not in _ELEM_BYTES:
-            raise TypeError(f"{what}: {name} must hold integer labels (bool, uint8, int16, int32 or int64), got {t.dtype}")
-    if dims not in _CONNECTIVITIES:
-        raise ValueError(f"{what}: dims must be 2 or 3, got {dims!r}")
+        M.check_labels(what, name, t)
+    M.check_dims(what, dims)
     if pred.shape != truth.shape:
         raise ValueError(f"{what}: pred and truth must have the same shape, got {tuple(pred.shape)} and {tuple(truth.shape)}")
     if pred.device != truth.device:
         raise ValueError(f"{what}: pred and truth must be on the same device, got {pred.device} and {truth.device}")
-    if pred.dim() < dims:
-        raise ValueError(f"{what}: pred and truth must be [*stack, {'D, ' if dims == 3 else ''}H, W] for dims={dims}, got {tuple(pred.shape)}")
-    B, D, H, W = _distance._geometry(what, pred, dims)     # (its errors from here on name the positions, not a parameter)
-    if connectivity is None:
-        connectivity = _CONNECTIVITIES[dims][0]
-    if isinstance(connectivity, bool) or connectivity not in _CONNECTIVITIES[dims]:
-        a, b = _CONNECTIVITIES[dims]
-        raise ValueError(f"{what}: connectivity must be {a} or {b} for dims={dims}, got {connectivity!r}")
+    stack, B, D, H, W = M.extent(what, "pred and truth", pred, dims, squares=True)
+    connectivity, full = M.check_connectivity(what, connectivity, dims, default=0)
     if labels is None:
-        values, rule = [_check_int(what, "background", background)], _NOT_BACKGROUND
+        values, rule = [M.check_int(what, "background", background)], _NOT_BACKGROUND
     else:
         try:
             values = list(labels)
@@ -70,17 +59,17 @@ def _arguments(what, pred, truth, labels, background, dims, spacing, connectivit
             raise TypeError(f"{what}: labels must be None or a sequence of class values, got {labels!r}") from None
         if not values:
             raise ValueError(f"{what}: labels must name at least one class")
-        values, rule = [_check_int(what, "labels", v) for v in values], _CLASSES
-    sp = _distance._spacing(what, spacing, dims)
+        values, rule = [M.check_int(what, "labels", v) for v in values], _CLASSES
+    sp = M.spacing(what, spacing, dims)
     pct = _floats(what, "percentile", percentile, 0.0, 100.0, 1)[0]
     tols = _floats(what, "tolerance", tolerance, 0.0, math.inf, MAX_TOLERANCES)
     if max_workspace_bytes is None:
         cap = DEFAULT_WORKSPACE_BYTES
     else:
-        cap = _check_int(what, "max_workspace_bytes", max_workspace_bytes)
+        cap = M.check_int(what, "max_workspace_bytes", max_workspace_bytes)
         if cap < 1:
             raise ValueError(f"{what}: max_workspace_bytes must be positive, got {cap}")
-    return B, D, H, W, connectivity, values, rule, sp, pct, tols, cap
+    return stack, B, D, H, W, connectivity, full, values, rule, sp, pct, tols, cap
 
 
 def _plan(what, lib, dims, B, D, H, W, K, cap):
@@ -101,11 +90,11 @@ def _workspace_plan(shape, classes=1, dims=2, max_workspace_bytes=None):
     workspace it allocates and the smallest cap that is accepted (one class per chunk).  Not part of the interface: the tests and
     tools/bench_surface.py ask it what ``surface_metrics`` will do; the arguments are checked as that function checks its own."""
     what = "surface_metrics"
-    probe = torch.empty(tuple(_check_int(what, "shape", s) for s in shape), dtype=torch.uint8, device="meta")
-    classes = _check_int(what, "classes", classes)
+    probe = torch.empty(tuple(M.check_int(what, "shape", s) for s in shape), dtype=torch.uint8, device="meta")
+    classes = M.check_int(what, "classes", classes)
     if classes < 1:
         raise ValueError(f"{what}: classes must be positive, got {classes}")
-    B, D, H, W, *_, cap = _arguments(what, probe, probe, None, 0, dims, None, None, 95.0, 1.0, max_workspace_bytes)
+    _, B, D, H, W, *_, cap = _arguments(what, probe, probe, None, 0, dims, None, None, 95.0, 1.0, max_workspace_bytes)
     if B * D * H * W == 0:
         raise ValueError(f"{what}: empty maps of shape {tuple(probe.shape)} take no workspace")
     chunk, nbytes, least = _plan(what, N.load(), dims, B, D, H, W, classes, cap)
@@ -158,23 +147,23 @@ def _host(pred, truth, B, D, H, W, dims, full, values, rule, sp, pct, tols):
 
     def member(a, dtype, v):
         if rule == _CLASSES:
-            return (a == v) if _fits(v, dtype) else np.zeros(a.shape, bool)
-        return (a != v) if _fits(v, dtype) else np.ones(a.shape, bool)
+            return (a == v) if M.fits(v, dtype) else np.zeros(a.shape, bool)
+        return (a != v) if M.fits(v, dtype) else np.ones(a.shape, bool)
 
     q = pct / 100.0
     for b in range(B):
         for k, v in enumerate(values):
             border = np.stack([_border_host(member(p[b], pred.dtype, v), shifts), _border_host(member(t[b], truth.dtype, v), shifts)])
-            sq = _distance._squared_host(border, sp)                           # [2, D, H, W]: squared distances to pred's, truth's surface
+            sq = M.edt_host(border, sp)[0]                                   # [2, D, H, W]: squared distances to pred's, truth's surface
             n = border.reshape(2, -1).sum(axis=1)
             res["surface_count"][b, k] = n
             sets, within = [], np.zeros(T, np.int64)
             for side in range(2):
                 key = sq[1 - side][border[side]]
                 if sp is None:
-                    d = np.where(key >= _distance._HOST_INF, np.inf, np.sqrt(np.minimum(key, _distance._HOST_INF - 1).astype(np.float64)))
+                    d = np.where(key >= M.HOST_INF, np.inf, np.sqrt(np.minimum(key, M.HOST_INF - 1).astype(np.float64)))
                     for i, tol in enumerate(tols):
-                        within[i] += int((key <= math.floor(min(tol * tol, float(_distance.INT_INF - 1)))).sum())
+                        within[i] += int((key <= math.floor(min(tol * tol, float(M.INT_INF - 1)))).sum())
                 else:
                     d = np.sqrt(key)
                     for i, tol in enumerate(tols):
@@ -238,12 +227,10 @@ def surface_metrics(pred, truth, labels=None, *, background=0, dims=2, spacing=N
     neither does a second run.  The call is stream-ordered and reads nothing back; contiguous CUDA inputs are read where they lie (no
     ``labels == c``, widened or boolean copy).  Empty inputs return without a launch."""
     what = "surface_metrics"
-    B, D, H, W, connectivity, values, rule, sp, pct, tols, cap = _arguments(what, pred, truth, labels, background, dims, spacing, connectivity, percentile,
-                                                                            tolerance, max_workspace_bytes)
+    stack, B, D, H, W, connectivity, full, values, rule, sp, pct, tols, cap = _arguments(what, pred, truth, labels, background, dims, spacing, connectivity,
+                                                                                         percentile, tolerance, max_workspace_bytes)
     K, T = len(values), len(tols)
-    stack = tuple(pred.shape[:-dims])
     dev = pred.device
-    full = connectivity == _CONNECTIVITIES[dims][1]
     if B * D * H * W == 0:
         res = {"surface_count": torch.zeros((B, K, 2), dtype=torch.int64, device=dev), "surface_dice": torch.full((B, K, T), math.nan, device=dev)}
         res.update({key: torch.full((B, K, 2), math.nan, device=dev) for key in _KEYS2})
@@ -258,9 +245,9 @@ def surface_metrics(pred, truth, labels=None, *, background=0, dims=2, spacing=N
             res = {"surface_count": torch.empty((B, K, 2), dtype=torch.int64, device=dev), "surface_dice": torch.empty((B, K, T), dtype=torch.float32, device=dev)}
             res.update({key: torch.empty((B, K, 2), dtype=torch.float32, device=dev) for key in _KEYS2})
             res.update({key: torch.empty((B, K), dtype=torch.float32, device=dev) for key in _KEYS1})
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws = M.scratch(nbytes, dev)
             N.bump()
-            N.check(lib.ptb_surface_metrics(p.data_ptr(), _ELEM_BYTES[p.dtype], t.data_ptr(), _ELEM_BYTES[t.dtype], dims, B, D, H, W, N.i64_array(values), K, rule,
+            N.check(lib.ptb_surface_metrics(p.data_ptr(), M.ELEM_BYTES[p.dtype], t.data_ptr(), M.ELEM_BYTES[t.dtype], dims, B, D, H, W, N.i64_array(values), K, rule,
                                             connectivity, (ctypes.c_double * 3)(*sp) if sp is not None else None, pct, (ctypes.c_double * T)(*tols), T,
                                             res["surface_count"].data_ptr(), res["directed_hausdorff"].data_ptr(), res["hausdorff"].data_ptr(),
                                             res["directed_percentile"].data_ptr(), res["hausdorff_percentile"].data_ptr(),

@@ -31,14 +31,11 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from .components import _ELEM_BYTES, _check_int, _fits
-from .components import _geometry as _marker_geometry
-from .nearest import _check_out, _usable
+from . import _maps as M
 
 __all__ = ["watershed"]
 
 _COST, _SEED = 1, 2
-_HEIGHT_CODES = {torch.float32: N.F32, torch.float16: N.F16, torch.bfloat16: N.BF16, torch.uint8: N.U8, torch.int16: N.I16}
 DEFAULT_MAX_SWEEPS = 1 << 16         # per phase; a sweep moves a flood at least one tile on, so only a path that winds through more tiles gets here
 _PHASES = ("cost", "path")
 
@@ -94,7 +91,7 @@ def _host(height, markers, mask, B, D, H, W, dims, full, background, fill):
     if mask is not None:
         in_m &= mask.contiguous().reshape(B, D, H, W).numpy() != 0
     h = np.where(in_m, h, 0.0) + 0.0                            # (-0.0 + 0.0 is +0.0)
-    seed = (m != background) if _fits(background, markers.dtype) else np.ones(m.shape, bool)
+    seed = (m != background) if M.fits(background, markers.dtype) else np.ones(m.shape, bool)
     labels = np.empty_like(m)
     cost = np.empty(m.shape, np.float32)
     sigma = np.empty(m.shape, np.int32)
@@ -109,7 +106,7 @@ def _host(height, markers, mask, B, D, H, W, dims, full, background, fill):
 # ---------------------------------------------------------------------------------------------------------------- public
 def _fill_value(background, dtype):
     """``background`` as a tensor of ``dtype`` holds it (itself where it fits; else truncated like a C cast, ``bool``: ``!= 0``)"""
-    if _fits(background, dtype):
+    if M.fits(background, dtype):
         return background
     if dtype == torch.bool:
         return 1
@@ -145,33 +142,17 @@ def watershed(height, markers, mask=None, connectivity=8, background=0, dims=2, 
     function of the inputs alone: the same bits on every run.  Bad arguments raise before anything is launched; empty inputs return
     without a launch."""
     what = "watershed"
-    if not isinstance(height, torch.Tensor):
-        raise TypeError(f"{what}: height must be a tensor, got {type(height).__name__}")
-    if height.dtype not in _HEIGHT_CODES:
-        raise TypeError(f"{what}: height must be float32, float16, bfloat16, uint8 or int16, got {height.dtype}: pass height.float() if every value is exact in float32")
-    if not isinstance(markers, torch.Tensor):
-        raise TypeError(f"{what}: markers must be a tensor, got {type(markers).__name__}")
-    if markers.dtype not in _ELEM_BYTES:
-        raise TypeError(f"{what}: markers must hold integer labels (bool, uint8, int16, int32 or int64), got {markers.dtype}")
-    _stack, B, D, H, W, full, _ = _marker_geometry(what, markers, connectivity, 0, dims)
-    background = _check_int(what, "background", background)
+    M.check_values(what, "height", height)
+    M.check_labels(what, "markers", markers)
+    connectivity, full = M.check_connectivity(what, connectivity, dims)
+    _, B, D, H, W = M.extent(what, "labels", markers, dims, note=" (component numbers are int32)")      # (worded as connected_components words it)
+    background = M.check_int(what, "background", background)
     dev = markers.device
-    if height.shape != markers.shape or height.device != dev:
-        raise ValueError(f"{what}: height must have shape {tuple(markers.shape)} on {dev}, got {tuple(height.shape)} on {height.device}")
+    M.check_like(what, "height", height, markers)
     if mask is not None:
-        if not isinstance(mask, torch.Tensor):
-            raise TypeError(f"{what}: mask must be a tensor, got {type(mask).__name__}")
-        if mask.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"{what}: mask must be bool or uint8, got {mask.dtype}")
-        if mask.shape != markers.shape or mask.device != dev:
-            raise ValueError(f"{what}: mask must have shape {tuple(markers.shape)} on {dev}, got {tuple(mask.shape)} on {mask.device}")
-    if max_sweeps is None:
-        max_sweeps = DEFAULT_MAX_SWEEPS
-    else:
-        max_sweeps = _check_int(what, "max_sweeps", max_sweeps)
-        if not 1 <= max_sweeps < (1 << 31):
-            raise ValueError(f"{what}: max_sweeps must be in [1, 2^31 - 1], got {max_sweeps}")
-    _check_out(what, out, markers.dtype, markers)
+        M.check_like(what, "mask", mask, markers, (torch.bool, torch.uint8))
+    max_sweeps = M.check_max_sweeps(what, max_sweeps, DEFAULT_MAX_SWEEPS)
+    M.check_out(what, out, markers.dtype, markers)
     fill = _fill_value(background, markers.dtype)
     sweeps = (0, 0)
     if B * D * H * W == 0:
@@ -185,25 +166,20 @@ def watershed(height, markers, mask=None, connectivity=8, background=0, dims=2, 
         m = mask.contiguous() if mask is not None else None
         flags = (_COST if return_cost else 0) | (_SEED if return_seed else 0)
         with N.on_device(dev):
-            res = out if _usable(out, x) else torch.empty(x.shape, dtype=x.dtype, device=dev)
+            res = out if M.direct_out(out, x) else torch.empty(x.shape, dtype=x.dtype, device=dev)
             cost = torch.empty(x.shape, dtype=torch.float32, device=dev) if return_cost else None
             seed = torch.empty(x.shape, dtype=torch.int32, device=dev) if return_seed else None
             lib = N.load()
-            nbytes = ctypes.c_int64()
-            N.check(lib.ptb_watershed_plan(dims, B, D, H, W, flags, ctypes.byref(nbytes)), what)
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-            ptr = lambda t: t.data_ptr() if t is not None else None       # noqa: E731
+            ws, nbytes = M.workspace(lib.ptb_watershed_plan, what, dev, dims, B, D, H, W, flags)
+            ptr = M.opt_ptr
             took = (ctypes.c_int * 2)(-1, -1)
             N.bump()
-            rc = lib.ptb_watershed(h.data_ptr(), _HEIGHT_CODES[h.dtype], x.data_ptr(), _ELEM_BYTES[x.dtype], ptr(m), dims, B, D, H, W, connectivity, background, fill,
-                                   flags, max_sweeps, res.data_ptr(), ptr(cost), ptr(seed), took, ws.data_ptr(), nbytes.value, N.stream_ptr(dev))
+            rc = lib.ptb_watershed(h.data_ptr(), M.VALUE_CODES[h.dtype], x.data_ptr(), M.ELEM_BYTES[x.dtype], ptr(m), dims, B, D, H, W, connectivity, background, fill,
+                                   flags, max_sweeps, res.data_ptr(), ptr(cost), ptr(seed), took, ws.data_ptr(), nbytes, N.stream_ptr(dev))
             if rc == N.PTB_ENOTCONVERGED:
-                phase = 0 if took[1] < 0 else 1
-                raise RuntimeError(f"{what}: phase {phase + 1} (the {_PHASES[phase]} relaxation) did not converge within max_sweeps={max_sweeps}: {took[phase]} sweeps run")
+                M.raise_not_converged(what, _PHASES, took, max_sweeps)
             N.check(rc, what)
             sweeps = (int(took[0]), int(took[1]))
-    if out is not None and res is not out:
-        out.copy_(res)
-        res = out
+    res = M.finish_out(out, res)
     extra = ((cost,) if return_cost else ()) + ((seed,) if return_seed else ()) + ((sweeps,) if return_sweeps else ())
     return (res,) + extra if extra else res
