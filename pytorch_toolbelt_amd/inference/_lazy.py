@@ -43,6 +43,8 @@ from collections import OrderedDict
 import torch
 from torch.utils._pytree import tree_map
 
+from .. import _native as N
+
 _ENABLED = os.environ.get("PTB_LAZY_DEAUG", "1") != "0"
 _BUDGET = int(os.environ.get("PTB_LAZY_DEAUG_BYTES", str(4 << 30)))
 _pending = OrderedDict()      # id(handle) -> (weakref, bytes of its source), creation order
@@ -122,7 +124,6 @@ del _n, _p, _f
 
 
 _CONTAINERS = (list, tuple, dict)
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
 class LazyDeaugment(torch.Tensor):
@@ -145,7 +146,7 @@ class LazyDeaugment(torch.Tensor):
         self._compute = compute            # (source, views, code) -> tensor: the eager kernel
         self._value = None
         self._src_version = _source_version(source)
-        self._stream = _raw_stream(source.device.index) if (source.is_cuda and _raw_stream is not None) else None   # raw handle: 0.3 us
+        self._stream = N.raw_stream(source.device.index) if source.is_cuda else None   # raw handle: 0.3 us
         _admit(self, source.numel() * source.element_size())
 
     # ---------------------------------------------------------------- evaluation
@@ -159,7 +160,7 @@ class LazyDeaugment(torch.Tensor):
         caller that switched streams): that stream first waits for everything queued on the creating stream -- the producer of the
         source among it -- and the source is ``record_stream``-ed so that its memory outlives this read."""
         src = self._src
-        if self._stream is not None and _raw_stream(src.device.index) != self._stream:
+        if self._stream is not None and N.raw_stream(src.device.index) != self._stream:
             cur = torch.cuda.current_stream(src.device)
             cur.wait_stream(torch.cuda.ExternalStream(self._stream, device=src.device))
             src.record_stream(cur)

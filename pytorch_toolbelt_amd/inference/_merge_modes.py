@@ -27,7 +27,6 @@ import torch
 from .. import _native as N
 
 _current_device = torch._C._cuda_getDevice if hasattr(torch._C, "_cuda_getDevice") else torch.cuda.current_device
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
 
 FRESH_ROWS = 32  # rows of a first-touch block = default chunk rows of the view kernels (64 columns wide)
 LAZY_SRC = 0x10000  # host-only bit of a batch's `how` flags (next to N.ROUND_SRC): the batch is the source of a lazy de-augmentation handle --
@@ -193,13 +192,9 @@ class Plan:
             remaining = remaining.astype(np.uint8)
         xy = np.ascontiguousarray(crops[:, :2].T)
         norm_full = torch.zeros((1, H, W), device=merger.weight.device, dtype=torch.float32)
-        lib = N.load()
         dev = norm_full.device
-        with N.on_device(dev):
-            rc = lib.ptb_norm_accumulate(norm_full.data_ptr(), merger.weight.data_ptr(), xy[0].ctypes.data_as(N._i64p),
-                                         xy[1].ctypes.data_as(N._i64p), xy.shape[1], th, tw, H, W, None, 0, N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "TileMerger(crops=...)")
+        N.launch("ptb_norm_accumulate", dev, norm_full.data_ptr(), merger.weight.data_ptr(), xy[0].ctypes.data_as(N._i64p),
+                 xy[1].ctypes.data_as(N._i64p), xy.shape[1], th, tw, H, W, None, 0, what="TileMerger(crops=...)")
         plan = Plan(xy, remaining, norm_full)
         plan.crops4 = np.ascontiguousarray(crops, dtype=np.int64)
         return plan
@@ -276,10 +271,7 @@ class Bands:
         if nbytes < 0:
             return None
         table = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
-        with N.on_device(device):
-            rc = lib.ptb_band_plan_upload(handle, table.data_ptr(), N.stream_ptr(device))
-        N.bump()
-        N.check(rc, "TileMerger(defer=True)")
+        N.launch("ptb_band_plan_upload", device, handle, table.data_ptr(), what="TileMerger(defer=True)")
         ng, nb, ni = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
         lib.ptb_band_plan_info(handle, ctypes.byref(ng), ctypes.byref(nb), ctypes.byref(ni), None, None)
         last_group = np.zeros(n, dtype=np.int64)
@@ -448,15 +440,12 @@ class DeferredBands(_OfMerger):
             m._merged = torch.empty_like(m._image)
         per_tile = m.channels * int(m.weight.shape[1]) * int(m.weight.shape[2])
         dev = m._image.device
-        with N.on_device(dev):
-            if act is None:
-                rc = N.load().ptb_band_plan_submit(bands.handle, pos, B, batch.data_ptr(), per_tile, B * per_tile, dcode, n_views, varr, code,
-                                                   m._merged.data_ptr(), plan.norm_full.data_ptr(), m.weight.data_ptr(), N.stream_ptr(dev))
-            else:
-                rc = N.load().ptb_band_plan_submit_act(bands.handle, pos, B, batch.data_ptr(), per_tile, B * per_tile, dcode, n_views, varr, code,
-                                                       m._merged.data_ptr(), plan.norm_full.data_ptr(), m.weight.data_ptr(), act[0], act[1],
-                                                       N.stream_ptr(dev))
-        N.bump()
+        args = (bands.handle, pos, B, batch.data_ptr(), per_tile, B * per_tile, dcode, n_views, varr, code, m._merged.data_ptr(),
+                plan.norm_full.data_ptr(), m.weight.data_ptr())
+        if act is None:
+            rc = N.launch("ptb_band_plan_submit", dev, *args, raw=True)
+        else:
+            rc = N.launch("ptb_band_plan_submit_act", dev, *args, act[0], act[1], raw=True)
         if rc < 0:
             return rc
         lg = bands.last_group
@@ -508,7 +497,7 @@ class DeferredBands(_OfMerger):
                     # (the full contract check words the refusal: a batch in a held batch's memory first -- a static output buffer
                     # moves the counter of every slice of it too --, then the in-place edit)
                     check_held(held.rows, batch, (p0, p0 + B * s[7], version), True, held.what, held.hint)
-        rc = s[6](bands.handle, p0, B, _raw_stream(s[5]))
+        rc = s[6](bands.handle, p0, B, N.raw_stream(s[5]))
         N.calls += 1
         if rc < 0:
             if rc == N.PTB_EHELD:
@@ -614,25 +603,21 @@ class PlannedBlocks(_OfMerger):
         plan = m._plan
         if m._merged is None:
             m._merged = torch.empty_like(m._image)
-        lib = N.load()
         dev = m._image.device
         th, tw = int(m.weight.shape[1]), int(m.weight.shape[2])
         keep = 1 if m._selfplan.planned else 0
         fresh = m._fresh
 
-        def launch(fresh_ptr):
-            return lib.ptb_accumulate_planned2(m._image.data_ptr(), plan.norm_full.data_ptr(), m._merged.data_ptr(), m.weight.data_ptr(),
-                                               batch.data_ptr(), dcode, n_views, varr, code, xs, ys, B, m.channels, th, tw, m.image_height,
-                                               m.image_width, fresh_ptr, FRESH_ROWS, plan.remaining.ctypes.data, plan.done.ctypes.data,
-                                               keep, N.stream_ptr(dev))
+        def launch(fresh_ptr, count):
+            return N.launch("ptb_accumulate_planned2", dev, m._image.data_ptr(), plan.norm_full.data_ptr(), m._merged.data_ptr(), m.weight.data_ptr(),
+                            batch.data_ptr(), dcode, n_views, varr, code, xs, ys, B, m.channels, th, tw, m.image_height, m.image_width, fresh_ptr,
+                            FRESH_ROWS, plan.remaining.ctypes.data, plan.done.ctypes.data, keep, raw=True, count=count)
 
-        with N.on_device(dev):
-            rc = launch(fresh.ctypes.data if fresh.any() else None)
-            if rc == N.EFRESH:  # a cell straddles written and never-written blocks: zero-fill once, then plain RMW
-                N.fresh_fallbacks += 1
-                m._materialize()
-                rc = launch(None)
-        N.bump()
+        rc = launch(fresh.ctypes.data if fresh.any() else None, True)
+        if rc == N.EFRESH:  # a cell straddles written and never-written blocks: zero-fill once, then plain RMW (one counted call for the pair)
+            N.fresh_fallbacks += 1
+            m._materialize()
+            rc = launch(None, False)
         return rc
 
     def take_fast(self, batch, crop_coords, key, views, code, rnd=0):
@@ -719,13 +704,9 @@ class PlannedBlocks(_OfMerger):
             m._materialize()
             m._check_state()
             mask = torch.from_numpy(pending.astype(np.uint8)).to(m._image.device)
-            lib = N.load()
             dev = m._image.device
-            with N.on_device(dev):
-                rc = lib.ptb_merge_div_masked(m._image.data_ptr(), m._norm.data_ptr(), out.data_ptr(), m.channels,
-                                              m.image_height, m.image_width, mask.data_ptr(), FRESH_ROWS, N.stream_ptr(dev))
-            N.bump()
-            N.check(rc, "TileMerger.merge")
+            N.launch("ptb_merge_div_masked", dev, m._image.data_ptr(), m._norm.data_ptr(), out.data_ptr(), m.channels, m.image_height, m.image_width,
+                     mask.data_ptr(), FRESH_ROWS, what="TileMerger.merge")
         return out
 
 
@@ -739,27 +720,21 @@ class Incremental(_OfMerger):
     def take(self, batch, coords, xy, xs, ys, views, n_views, varr, reduction, dcode, act=None):
         m = self.m
         B = xy.shape[1]
-        lib = N.load()
         dev = m._image.device
         th, tw = int(m.weight.shape[1]), int(m.weight.shape[2])
         norm_ptr = m._norm.data_ptr() if m._eager_norm else None
+        # with ``act``: ``A(batch)`` in registers (csrc/ptb_tile_activation.hip)
+        name, tail = ("ptb_deaug_accumulate_t", ()) if act is None else ("ptb_deaug_accumulate_act", (act[0], act[1]))
 
-        def launch(fresh_ptr):
-            if act is not None:      # ``A(batch)`` in registers (csrc/ptb_tile_activation.hip)
-                return lib.ptb_deaug_accumulate_act(m._image.data_ptr(), norm_ptr, m.weight.data_ptr(), batch.data_ptr(), dcode, n_views, varr,
-                                                    reduction, xs, ys, B, m.channels, th, tw, m.image_height, m.image_width, fresh_ptr,
-                                                    FRESH_ROWS, act[0], act[1], N.stream_ptr(dev))
-            return lib.ptb_deaug_accumulate_t(m._image.data_ptr(), norm_ptr, m.weight.data_ptr(), batch.data_ptr(), dcode, n_views, varr,
-                                              reduction, xs, ys, B, m.channels, th, tw, m.image_height, m.image_width, fresh_ptr,
-                                              FRESH_ROWS, N.stream_ptr(dev))
+        def launch(fresh_ptr, count):
+            return N.launch(name, dev, m._image.data_ptr(), norm_ptr, m.weight.data_ptr(), batch.data_ptr(), dcode, n_views, varr, reduction, xs, ys, B,
+                            m.channels, th, tw, m.image_height, m.image_width, fresh_ptr, FRESH_ROWS, *tail, raw=True, count=count)
 
-        with N.on_device(dev):
-            rc = launch(m._fresh.ctypes.data if m._fresh.any() else None)
-            if rc == N.EFRESH:  # geometry not block aligned (or a non-default chunk size): zero-fill once, then plain RMW
-                N.fresh_fallbacks += 1
-                m._materialize()
-                rc = launch(None)
-        N.bump()
+        rc = launch(m._fresh.ctypes.data if m._fresh.any() else None, True)
+        if rc == N.EFRESH:  # geometry not block aligned (or a non-default chunk size): zero-fill once, then plain RMW (one counted call for the pair)
+            N.fresh_fallbacks += 1
+            m._materialize()
+            rc = launch(None, False)
         if rc == -2 and act is not None:   # a shape of the scalar kernels (tiles off the 4-pixel grid): A in torch ops, then today's entry point
             from .tta_3d import apply_activation
 
@@ -780,13 +755,9 @@ class Incremental(_OfMerger):
         m._norm_ready()
         m._materialize()
         m._check_state()
-        lib = N.load()
         dev = m._image.device
-        with N.on_device(dev):
-            rc = lib.ptb_merge_div(m._image.data_ptr(), m._norm.data_ptr(), out.data_ptr(), m.channels,
-                                   m.image_height * m.image_width, N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "TileMerger.merge")
+        N.launch("ptb_merge_div", dev, m._image.data_ptr(), m._norm.data_ptr(), out.data_ptr(), m.channels, m.image_height * m.image_width,
+                 what="TileMerger.merge")
         return out
 
 

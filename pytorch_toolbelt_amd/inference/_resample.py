@@ -31,26 +31,23 @@ def _f32(x, what="multiscale TTA"):
     return (x if x.dtype == torch.float32 else x.float()).contiguous()
 
 
+def _resize_entry(mode, align_corners, backward):
+    """``(entry point, its arguments after the sizes)`` of one resize mode; all but bilinear take the direction as their last argument"""
+    if mode == "bilinear":
+        return "ptb_resize_bilinear_bwd" if backward else "ptb_resize_bilinear", (1 if align_corners else 0,)
+    if mode == "bicubic":
+        return "ptb_resize_bicubic", (1 if align_corners else 0, int(backward))
+    return {"nearest-exact": "ptb_resize_nearest_exact", "area": "ptb_resize_area"}.get(mode, "ptb_resize_nearest"), (int(backward),)
+
+
 class _Resize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, size, mode, align_corners):
         B, C, H, W = x.shape
         ho, wo = int(size[0]), int(size[1])
         out = torch.empty((B, C, ho, wo), device=x.device, dtype=torch.float32)
-        lib = N.load()
-        with N.on_device(x.device):
-            if mode == "bilinear":
-                rc = lib.ptb_resize_bilinear(x.data_ptr(), out.data_ptr(), B * C, H, W, ho, wo, 1 if align_corners else 0, N.stream_ptr(x.device))
-            elif mode == "bicubic":
-                rc = lib.ptb_resize_bicubic(x.data_ptr(), out.data_ptr(), B * C, H, W, ho, wo, 1 if align_corners else 0, 0, N.stream_ptr(x.device))
-            elif mode == "nearest-exact":
-                rc = lib.ptb_resize_nearest_exact(x.data_ptr(), out.data_ptr(), B * C, H, W, ho, wo, 0, N.stream_ptr(x.device))
-            elif mode == "area":
-                rc = lib.ptb_resize_area(x.data_ptr(), out.data_ptr(), B * C, H, W, ho, wo, 0, N.stream_ptr(x.device))
-            else:
-                rc = lib.ptb_resize_nearest(x.data_ptr(), out.data_ptr(), B * C, H, W, ho, wo, 0, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_resize")
+        name, tail = _resize_entry(mode, align_corners, False)
+        N.launch(name, x.device, x.data_ptr(), out.data_ptr(), B * C, H, W, ho, wo, *tail, what="ptb_resize")
         ctx.cfg = (B, C, H, W, ho, wo, mode, bool(align_corners))
         return out
 
@@ -59,20 +56,8 @@ class _Resize(torch.autograd.Function):
         B, C, H, W, ho, wo, mode, ac = ctx.cfg
         g = g.to(torch.float32).contiguous()
         gin = torch.zeros((B, C, H, W), device=g.device, dtype=torch.float32)
-        lib = N.load()
-        with N.on_device(g.device):
-            if mode == "bilinear":
-                rc = lib.ptb_resize_bilinear_bwd(g.data_ptr(), gin.data_ptr(), B * C, H, W, ho, wo, 1 if ac else 0, N.stream_ptr(g.device))
-            elif mode == "bicubic":
-                rc = lib.ptb_resize_bicubic(g.data_ptr(), gin.data_ptr(), B * C, H, W, ho, wo, 1 if ac else 0, 1, N.stream_ptr(g.device))
-            elif mode == "nearest-exact":
-                rc = lib.ptb_resize_nearest_exact(g.data_ptr(), gin.data_ptr(), B * C, H, W, ho, wo, 1, N.stream_ptr(g.device))
-            elif mode == "area":
-                rc = lib.ptb_resize_area(g.data_ptr(), gin.data_ptr(), B * C, H, W, ho, wo, 1, N.stream_ptr(g.device))
-            else:
-                rc = lib.ptb_resize_nearest(g.data_ptr(), gin.data_ptr(), B * C, H, W, ho, wo, 1, N.stream_ptr(g.device))
-        N.bump()
-        N.check(rc, "ptb_resize (backward)")
+        name, tail = _resize_entry(mode, ac, True)
+        N.launch(name, g.device, g.data_ptr(), gin.data_ptr(), B * C, H, W, ho, wo, *tail, what="ptb_resize (backward)")
         return gin, None, None, None
 
 
@@ -102,16 +87,14 @@ class _MsReduce(torch.autograd.Function):
         out = torch.empty((B, C, ho, wo), device=first.device, dtype=torch.float32)
         hs = N.int_array([int(m.shape[2]) for m in maps])
         ws = N.int_array([int(m.shape[3]) for m in maps])
-        lib = N.load()
-        with N.on_device(first.device):
-            # the 64 x 64-tile kernel of the fused flips + multiscale pass with a single (identity) view: 1.08x source traffic
-            # instead of the 1.21x of the 64 x 16-tile kernel; shapes it does not take (odd widths, ratios above ~1.3) fall through
-            rc = lib.ptb_ms_flip_deaug_reduce(_ptr_array(maps), hs, ws, len(maps), 1, N.int_array([N.IDENT]), N.RED_SUM, out.data_ptr(), B * C,
-                                              ho, wo, 1 if align_corners else 0, code, N.stream_ptr(first.device))
-            if rc == N.PTB_EUNSUPPORTED:
-                rc = lib.ptb_ms_deaug_reduce(_ptr_array(maps), hs, ws, len(maps), out.data_ptr(), B * C, ho, wo, 1 if align_corners else 0, code,
-                                             N.stream_ptr(first.device))
-        N.bump()
+        # the 64 x 64-tile kernel of the fused flips + multiscale pass with a single (identity) view: 1.08x source traffic
+        # instead of the 1.21x of the 64 x 16-tile kernel; shapes it does not take (odd widths, ratios above ~1.3) fall through
+        # (one counted call for the pair)
+        rc = N.launch("ptb_ms_flip_deaug_reduce", first.device, _ptr_array(maps), hs, ws, len(maps), 1, N.int_array([N.IDENT]), N.RED_SUM,
+                      out.data_ptr(), B * C, ho, wo, 1 if align_corners else 0, code, raw=True)
+        if rc == N.PTB_EUNSUPPORTED:
+            rc = N.launch("ptb_ms_deaug_reduce", first.device, _ptr_array(maps), hs, ws, len(maps), out.data_ptr(), B * C, ho, wo,
+                          1 if align_corners else 0, code, raw=True, count=False)
         N.check(rc, "ptb_ms_deaug_reduce")
         ctx.save_for_backward(out, *maps)
         ctx.cfg = (B * C, ho, wo, bool(align_corners), code)
@@ -125,12 +108,8 @@ class _MsReduce(torch.autograd.Function):
         grads = [torch.zeros_like(m) for m in maps]
         hs = N.int_array([int(m.shape[2]) for m in maps])
         ws = N.int_array([int(m.shape[3]) for m in maps])
-        lib = N.load()
-        with N.on_device(g.device):
-            rc = lib.ptb_ms_deaug_reduce_bwd(_ptr_array(maps), hs, ws, len(maps), out.data_ptr(), g.data_ptr(), _ptr_array(grads), planes, ho, wo,
-                                             1 if ac else 0, code, N.stream_ptr(g.device))
-        N.bump()
-        N.check(rc, "ptb_ms_deaug_reduce_bwd")
+        N.launch("ptb_ms_deaug_reduce_bwd", g.device, _ptr_array(maps), hs, ws, len(maps), out.data_ptr(), g.data_ptr(), _ptr_array(grads), planes,
+                 ho, wo, 1 if ac else 0, code)
         return (None, None, None) + tuple(grads)
 
 
@@ -170,11 +149,8 @@ def ms_flip_reduce(maps, views, size, align_corners: bool, inner_code: int, code
     out = torch.empty((B, C, ho, wo), device=first.device, dtype=torch.float32)
     hs = N.int_array([int(m.shape[2]) for m in ms])
     ws = N.int_array([int(m.shape[3]) for m in ms])
-    lib = N.load()
-    with N.on_device(first.device):
-        rc = lib.ptb_ms_flip_deaug_reduce(_ptr_array(ms), hs, ws, len(ms), V, N.int_array(list(views)), inner_code, out.data_ptr(), B * C, ho, wo,
-                                          1 if align_corners else 0, code, N.stream_ptr(first.device))
-    N.bump()
+    rc = N.launch("ptb_ms_flip_deaug_reduce", first.device, _ptr_array(ms), hs, ws, len(ms), V, N.int_array(list(views)), inner_code,
+                  out.data_ptr(), B * C, ho, wo, 1 if align_corners else 0, code, raw=True)
     if rc == N.PTB_EUNSUPPORTED:
         return None
     N.check(rc, "ptb_ms_flip_deaug_reduce")

@@ -67,12 +67,7 @@ def _raw_view_transform(x, views: Sequence[int], in_is_batch: bool, scale: float
     if any(v & 1 for v in views) and H != W:
         raise ValueError(f"Input tensor must have number of rows equal to number of cols. Got input tensor of shape {x.size()}")
     out = torch.empty((V * B, C, H, W), device=x.device, dtype=x.dtype)
-    lib = N.load()
-    with N.on_device(x.device):
-        rc = lib.ptb_view_transform(x.data_ptr(), out.data_ptr(), V, N.int_array(views), 1 if in_is_batch else 0, float(scale),
-                                    B, C, H, W, N.stream_ptr(x.device))
-    N.bump()
-    N.check(rc, "ptb_view_transform")
+    N.launch("ptb_view_transform", x.device, x.data_ptr(), out.data_ptr(), V, N.int_array(views), 1 if in_is_batch else 0, float(scale), B, C, H, W)
     return out
 
 
@@ -86,11 +81,8 @@ def _raw_deaug_reduce(x, views: Sequence[int], code: int):
     if any(v & 1 for v in views) and H != W:
         raise ValueError(f"Transposing views need square inputs, got {tuple(x.shape)}")
     out = torch.empty((B, C, H, W), device=x.device, dtype=torch.float32)
-    lib = N.load()
     dcode = N.DTYPE_CODES[x.dtype]
-    with N.on_device(x.device):
-        rc = lib.ptb_deaug_reduce_t(x.data_ptr(), dcode | N.layout_flag(x), out.data_ptr(), V, N.int_array(views), code, B, C, H, W, N.stream_ptr(x.device))
-    N.bump()
+    rc = N.launch("ptb_deaug_reduce_t", x.device, x.data_ptr(), dcode | N.layout_flag(x), out.data_ptr(), V, N.int_array(views), code, B, C, H, W, raw=True)
     if rc == -2 and dcode != N.F32:   # shape needs the scalar kernels
         return _raw_deaug_reduce(x.float(), views, code)      # (.float() keeps the memory format)
     N.check(rc, "ptb_deaug_reduce")
@@ -121,12 +113,7 @@ def _raw_deaug_reduce_bwd(x, out, g, views, code):
     V = len(views)
     n, C, H, W = x.shape
     grad = torch.empty_like(x)
-    lib = N.load()
-    with N.on_device(x.device):
-        rc = lib.ptb_deaug_reduce_bwd(x.data_ptr(), out.data_ptr(), g.data_ptr(), grad.data_ptr(), V, N.int_array(views), code,
-                                      n // V, C, H, W, N.stream_ptr(x.device))
-    N.bump()
-    N.check(rc, "ptb_deaug_reduce_bwd")
+    N.launch("ptb_deaug_reduce_bwd", x.device, x.data_ptr(), out.data_ptr(), g.data_ptr(), grad.data_ptr(), V, N.int_array(views), code, n // V, C, H, W)
     return grad
 
 
@@ -173,12 +160,8 @@ def _raw_permute(x, views: Sequence[int], in_is_batch: bool):
         payload *= r
     align = x.data_ptr() | out.data_ptr()
     elem = next(e for e in (16, 8, 4, 2, 1) if payload % e == 0 and align % e == 0)
-    lib = N.load()
-    with N.on_device(x.device):
-        rc = lib.ptb_view_permute(x.data_ptr(), out.data_ptr(), V, N.int_array(views), 1 if in_is_batch else 0, B * C, H, W, elem,
-                                  payload // elem, N.stream_ptr(x.device))
-    N.bump()
-    N.check(rc, "ptb_view_permute")
+    N.launch("ptb_view_permute", x.device, x.data_ptr(), out.data_ptr(), V, N.int_array(views), 1 if in_is_batch else 0, B * C, H, W, elem,
+             payload // elem)
     return out
 
 
@@ -296,10 +279,7 @@ class _StackReduceAny(torch.autograd.Function):
         T, rest = x.shape[0], x.shape[1:]
         flat = x.contiguous().view(T, -1)
         out = torch.empty(flat.shape[1], dtype=torch.float32, device=x.device)
-        with N.on_device(x.device):
-            rc = N.load().ptb_stack_reduce(flat.data_ptr(), T, flat.shape[1], code, float(eps), out.data_ptr(), N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_stack_reduce")
+        N.launch("ptb_stack_reduce", x.device, flat.data_ptr(), T, flat.shape[1], code, float(eps), out.data_ptr())
         ctx.cfg, ctx.rest = (code, float(eps), T), rest
         ctx.save_for_backward(flat, out)
         return out.view(rest)
@@ -310,11 +290,7 @@ class _StackReduceAny(torch.autograd.Function):
         flat, out = ctx.saved_tensors
         g = g.contiguous().view(-1).float()
         grad = torch.empty_like(flat)
-        with N.on_device(flat.device):
-            rc = N.load().ptb_stack_reduce_bwd(flat.data_ptr(), out.data_ptr(), g.data_ptr(), T, flat.shape[1], code, eps, grad.data_ptr(),
-                                               N.stream_ptr(flat.device))
-        N.bump()
-        N.check(rc, "ptb_stack_reduce_bwd")
+        N.launch("ptb_stack_reduce_bwd", flat.device, flat.data_ptr(), out.data_ptr(), g.data_ptr(), T, flat.shape[1], code, eps, grad.data_ptr())
         return grad.view((T,) + tuple(ctx.rest)), None, None
 
 

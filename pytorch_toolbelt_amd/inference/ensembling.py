@@ -58,11 +58,7 @@ def _ensemble_native(tensors: List[Tensor], code: int, act: int, temperature: fl
         return out.to(back) if back is not None else out
     B, C, HW = fact
     ptrs = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
-    lib = N.load()
-    with N.on_device(first.device):
-        rc = lib.ptb_ensemble_reduce(ptrs, len(xs), code, act, float(temperature), B, C, HW, out.data_ptr(), N.stream_ptr(first.device))
-    N.bump()
-    N.check(rc, "Ensembler")
+    N.launch("ptb_ensemble_reduce", first.device, ptrs, len(xs), code, act, float(temperature), B, C, HW, out.data_ptr(), what="Ensembler")
     return out.to(back) if back is not None else out
 
 

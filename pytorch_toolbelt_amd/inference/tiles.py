@@ -266,14 +266,9 @@ class ImageSlicer:
             sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float32).reshape(-1), (channels,)))
             bi = np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.float32).reshape(-1), (channels,)))
             fa = (sc.ctypes.data_as(N._fp), bi.ctypes.data_as(N._fp))
-        lib = N.load()
-        with N.on_device(image.device):
-            rc = lib.ptb_split_tiles(image.data_ptr(), code, self.image_height, self.image_width, channels,
-                                     xy[0].ctypes.data_as(N._i64p), xy[1].ctypes.data_as(N._i64p), n, th, tw,
-                                     len(views), N.int_array(views), fa[0] if fa else None, fa[1] if fa else None,
-                                     int(border_type), pad, out_code, out.data_ptr(), N.stream_ptr(image.device))
-        N.bump()
-        N.check(rc, "ImageSlicer.split_device")
+        N.launch("ptb_split_tiles", image.device, image.data_ptr(), code, self.image_height, self.image_width, channels,
+                 xy[0].ctypes.data_as(N._i64p), xy[1].ctypes.data_as(N._i64p), n, th, tw, len(views), N.int_array(views), fa[0] if fa else None,
+                 fa[1] if fa else None, int(border_type), pad, out_code, out.data_ptr(), what="ImageSlicer.split_device")
         return out
 
     def _mean(self, tile_size):
@@ -608,14 +603,9 @@ class TileMerger:
         if pending:
             xy = np.ascontiguousarray(np.concatenate(pending, axis=1))
             th, tw = int(self.weight.shape[1]), int(self.weight.shape[2])
-            lib = N.load()
             dev = self._norm.device
-            with N.on_device(dev):
-                rc = lib.ptb_norm_accumulate(self._norm.data_ptr(), self.weight.data_ptr(), xy[0].ctypes.data_as(N._i64p),
-                                             xy[1].ctypes.data_as(N._i64p), xy.shape[1], th, tw, self.image_height,
-                                             self.image_width, None, 0, N.stream_ptr(dev))
-            N.bump()
-            N.check(rc, "TileMerger.norm_mask")
+            N.launch("ptb_norm_accumulate", dev, self._norm.data_ptr(), self.weight.data_ptr(), xy[0].ctypes.data_as(N._i64p),
+                     xy[1].ctypes.data_as(N._i64p), xy.shape[1], th, tw, self.image_height, self.image_width, None, 0, what="TileMerger.norm_mask")
             self._applied = len(self._log)
         if self._norm_pure:
             self._norm_key = self._log_key()
@@ -881,14 +871,9 @@ class TileMerger:
         out = torch.empty(shape, device=self._image.device, dtype=out_dtype)
         if out.numel() == 0:
             return out
-        lib = N.load()
         dev = self._image.device
-        with N.on_device(dev):
-            rc = lib.ptb_merge_crop(src.data_ptr(), norm_ptr, self.channels, self.image_height,
-                                    self.image_width, top, left, oh, ow, 1 if layout == "hwc" else 0, kind, out.data_ptr(),
-                                    N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "TileMerger.merge_crop")
+        N.launch("ptb_merge_crop", dev, src.data_ptr(), norm_ptr, self.channels, self.image_height, self.image_width, top, left, oh, ow,
+                 1 if layout == "hwc" else 0, kind, out.data_ptr(), what="TileMerger.merge_crop")
         return out
 
 

@@ -158,20 +158,13 @@ class VolumeSlicer:
             fa = (sc.ctypes.data_as(N._fp), bi.ctypes.data_as(N._fp))
         volume = volume.contiguous()
         D, H, W = (int(s) for s in self.volume_shape)
-        lib = N.load()
-        with N.on_device(volume.device):
-            if mirror is None:
-                rc = lib.ptb_volume_split(volume.data_ptr(), code, D, H, W, channels, starts[0].ctypes.data_as(N._i64p),
-                                          starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), n, d, h, w,
-                                          fa[0] if fa else None, fa[1] if fa else None, pad, out_code, out.data_ptr(),
-                                          N.stream_ptr(volume.device))
-            else:
-                rc = lib.ptb_volume_split_mirror(volume.data_ptr(), code, D, H, W, channels, starts[0].ctypes.data_as(N._i64p),
-                                                 starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), n, d, h, w,
-                                                 fa[0] if fa else None, fa[1] if fa else None, pad, len(views), N.int_array(views),
-                                                 out_code, out.data_ptr(), N.stream_ptr(volume.device))
-        N.bump()
-        N.check(rc, "VolumeSlicer.split_device")
+        args = (volume.data_ptr(), code, D, H, W, channels, starts[0].ctypes.data_as(N._i64p), starts[1].ctypes.data_as(N._i64p),
+                starts[2].ctypes.data_as(N._i64p), n, d, h, w, fa[0] if fa else None, fa[1] if fa else None, pad)
+        if mirror is None:
+            N.launch("ptb_volume_split", volume.device, *args, out_code, out.data_ptr(), what="VolumeSlicer.split_device")
+        else:
+            N.launch("ptb_volume_split_mirror", volume.device, *args, len(views), N.int_array(views), out_code, out.data_ptr(),
+                     what="VolumeSlicer.split_device")
         return out
 
     def _mean(self, volume_size):
@@ -219,11 +212,8 @@ def resample_volume(volume: torch.Tensor, size, align_corners: bool = False, dty
     volume = volume.contiguous()
     out = torch.empty(size + tuple(volume.shape[3:]), device=volume.device, dtype=dtype)
     D, H, W = (int(s) for s in volume.shape[:3])
-    with N.on_device(volume.device):
-        rc = N.load().ptb_volume_resize_trilinear(volume.data_ptr(), N.VOLUME_DTYPE_CODES[volume.dtype], D, H, W, channels, *size,
-                                                  1 if align_corners else 0, N.DTYPE_CODES[dtype], out.data_ptr(), N.stream_ptr(volume.device))
-    N.bump()
-    N.check(rc, "resample_volume")
+    N.launch("ptb_volume_resize_trilinear", volume.device, volume.data_ptr(), N.VOLUME_DTYPE_CODES[volume.dtype], D, H, W, channels, *size,
+             1 if align_corners else 0, N.DTYPE_CODES[dtype], out.data_ptr(), what="resample_volume")
     return out
 
 
@@ -489,8 +479,7 @@ class VolumeMerger(_DeferredVolume):
             self._held = HeldBatches("VolumeMerger")
             self._groups_done = 0
             self._table = torch.empty(max(16, self._plan.table_bytes), device=device, dtype=torch.uint8)   # the library allocates no device memory
-            with N.on_device(self._table.device):
-                N.check(N.load().ptb_volume_plan_upload(self._plan.handle, self._table.data_ptr(), N.stream_ptr(self._table.device)), "VolumeMerger")
+            N.launch("ptb_volume_plan_upload", self._table.device, self._plan.handle, self._table.data_ptr(), what="VolumeMerger", count=False)
             self._result = torch.empty(spec.out_shape(channels), device=device, dtype=spec.out_dtype)
             return
         self.volume = torch.zeros((channels, *shape), device=device, dtype=dtype)
@@ -567,12 +556,10 @@ class VolumeMerger(_DeferredVolume):
         dev = self.weight.device
         args = (plan.handle, pos, B, batch.data_ptr(), tile_elems, B * tile_elems, dtype, len(views), N.int_array(views) if views else None, code,
                 self.weight.data_ptr(), self._result.data_ptr())
-        with N.on_device(dev):
-            if act == N.ACT_NONE:
-                rc = N.load().ptb_volume_plan_submit(*args, N.stream_ptr(dev))
-            else:
-                rc = N.load().ptb_volume_plan_submit_act(*args, act, temperature, N.stream_ptr(dev))
-        N.bump()
+        if act == N.ACT_NONE:
+            rc = N.launch("ptb_volume_plan_submit", dev, *args, raw=True)
+        else:
+            rc = N.launch("ptb_volume_plan_submit_act", dev, *args, act, temperature, raw=True)
         if rc < 0:
             N.check(rc, what)
         self._held.keep(batch, span, last_group=int(plan.last_group_of_tile[pos:pos + B].max()))
@@ -593,15 +580,10 @@ class VolumeMerger(_DeferredVolume):
             raise RuntimeError(f"tile batch of shape {tuple(batch.shape)} does not match [B, {self.channels}, {d}, {h}, {w}]")
         starts = _roi_starts(rois, (d, h, w))
         D, H, W = (int(s) for s in self.volume.shape[1:])
-        lib = N.load()
         dev = self.volume.device
-        with N.on_device(dev):
-            rc = lib.ptb_volume_accumulate(self.volume.data_ptr(), self.norm_mask.data_ptr(), self.weight.data_ptr(), batch.data_ptr(),
-                                           starts[0].ctypes.data_as(N._i64p), starts[1].ctypes.data_as(N._i64p),
-                                           starts[2].ctypes.data_as(N._i64p), len(rois), self.channels, d, h, w, D, H, W,
-                                           N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "VolumeMerger.integrate_batch")
+        N.launch("ptb_volume_accumulate", dev, self.volume.data_ptr(), self.norm_mask.data_ptr(), self.weight.data_ptr(), batch.data_ptr(),
+                 starts[0].ctypes.data_as(N._i64p), starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), len(rois), self.channels,
+                 d, h, w, D, H, W, what="VolumeMerger.integrate_batch")
 
     def accumulate_single(self, tile: torch.Tensor, roi, *, activation=None, temperature=1.0):
         """Accumulate one ``[C, d, h, w]`` prediction at ``roi`` (3 slices); ``activation`` / ``temperature``: see the class."""
@@ -652,18 +634,14 @@ class VolumeMerger(_DeferredVolume):
             batch = batch.contiguous()
         starts = _roi_starts(rois, (d, h, w))
         D, H, W = (int(s) for s in self.volume.shape[1:])
-        lib = N.load()
         dev = self.volume.device
         args = (self.volume.data_ptr(), self.norm_mask.data_ptr(), self.weight.data_ptr(), batch.data_ptr(), dtype, len(views), N.int_array(views),
                 code, starts[0].ctypes.data_as(N._i64p), starts[1].ctypes.data_as(N._i64p), starts[2].ctypes.data_as(N._i64p), len(rois),
                 self.channels, d, h, w, D, H, W)
-        with N.on_device(dev):
-            if act == N.ACT_NONE:
-                rc = lib.ptb_volume_mirror_accumulate(*args, N.stream_ptr(dev))
-            else:
-                rc = lib.ptb_volume_mirror_accumulate_act(*args, act, temperature, N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, what)
+        if act == N.ACT_NONE:
+            N.launch("ptb_volume_mirror_accumulate", dev, *args, what=what)
+        else:
+            N.launch("ptb_volume_mirror_accumulate_act", dev, *args, act, temperature, what=what)
 
     def integrate_batch_deaugment(self, batch: torch.Tensor, rois, mirror: str = "dhw", reduction="mean", *, activation=None, temperature=1.0):
         """Fused ``integrate_batch(mirror_volume_deaugment(batch, mirror, reduction), rois)``, bit for bit -- with ``activation`` /
@@ -703,13 +681,9 @@ class VolumeMerger(_DeferredVolume):
         if self._defer:
             return self._deferred_merge()
         out = torch.empty_like(self.volume)
-        lib = N.load()
         dev = self.volume.device
-        with N.on_device(dev):
-            rc = lib.ptb_merge_div(self.volume.data_ptr(), self.norm_mask.data_ptr(), out.data_ptr(), self.channels,
-                                   self.norm_mask.numel(), N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "VolumeMerger.merge")
+        N.launch("ptb_merge_div", dev, self.volume.data_ptr(), self.norm_mask.data_ptr(), out.data_ptr(), self.channels, self.norm_mask.numel(),
+                 what="VolumeMerger.merge")
         return out if self.dtype == torch.float32 else out.to(self.dtype)
 
     def merge_crop(self, crop, layout: str = "cdhw", dtype=torch.float32, argmax: bool = False) -> torch.Tensor:
@@ -737,13 +711,9 @@ class VolumeMerger(_DeferredVolume):
         out = torch.empty(out_shape, device=self.volume.device, dtype=out_dtype)
         if out.numel() == 0:
             return out
-        lib = N.load()
         dev = self.volume.device
-        with N.on_device(dev):
-            rc = lib.ptb_volume_merge_crop(self.volume.data_ptr(), self.norm_mask.data_ptr(), self.channels, *shape, z0, y0, x0, od, oh, ow,
-                                           1 if layout == "dhwc" else 0, kind, out.data_ptr(), N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "VolumeMerger.merge_crop")
+        N.launch("ptb_volume_merge_crop", dev, self.volume.data_ptr(), self.norm_mask.data_ptr(), self.channels, *shape, z0, y0, x0, od, oh, ow,
+                 1 if layout == "dhwc" else 0, kind, out.data_ptr(), what="VolumeMerger.merge_crop")
         return out
 
 

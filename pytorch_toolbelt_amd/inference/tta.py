@@ -160,10 +160,8 @@ def _image_deaugment_activated(image: Tensor, group: str, reduction: MaybeStrOrC
         out = torch.empty((B, C, H, W), device=y.device, dtype=torch.float32)
         if out.numel() == 0:
             return out
-        with N.on_device(y.device):
-            rc = N.load().ptb_deaug_reduce_act(y.data_ptr(), N.DTYPE_CODES[y.dtype] | N.layout_flag(y), out.data_ptr(), len(views), N.int_array(views),
-                                               code, B, C, H, W, act, float(temperature), N.stream_ptr(y.device))
-        N.bump()
+        rc = N.launch("ptb_deaug_reduce_act", y.device, y.data_ptr(), N.DTYPE_CODES[y.dtype] | N.layout_flag(y), out.data_ptr(), len(views),
+                      N.int_array(views), code, B, C, H, W, act, float(temperature), raw=True)
         if rc != N.PTB_EUNSUPPORTED:      # (unsupported: a shape of the scalar kernels -- A in torch ops, then today's call)
             N.check(rc, "ptb_deaug_reduce_act")
             return out

@@ -105,12 +105,8 @@ def _mirror(x: torch.Tensor, code: int, views, in_is_batch: bool, out_shape) -> 
     x = x.contiguous()
     n, C, D, H, W = x.shape
     out = torch.empty(out_shape, device=x.device, dtype=x.dtype)
-    lib = N.load()
-    with N.on_device(x.device):
-        rc = lib.ptb_volume_mirror(x.data_ptr(), code, out.data_ptr(), len(views), N.int_array(views), 1 if in_is_batch else 0,
-                                   n if in_is_batch else n // len(views), C, D, H, W, N.stream_ptr(x.device))
-    N.bump()
-    N.check(rc, "ptb_volume_mirror")
+    N.launch("ptb_volume_mirror", x.device, x.data_ptr(), code, out.data_ptr(), len(views), N.int_array(views), 1 if in_is_batch else 0,
+             n if in_is_batch else n // len(views), C, D, H, W)
     return out
 
 
@@ -135,11 +131,8 @@ def _deaugment_activated(y, views, code, act, temperature):
     else:
         y = y.contiguous()
     out = torch.empty((B, C, D, H, W), device=y.device, dtype=torch.float32)
-    with N.on_device(y.device):
-        rc = N.load().ptb_volume_mirror_reduce_act(y.data_ptr(), dtype, out.data_ptr(), V, N.int_array(views), code, B, C, D, H, W, act,
-                                                   temperature, N.stream_ptr(y.device))
-    N.bump()
-    N.check(rc, "ptb_volume_mirror_reduce_act")
+    N.launch("ptb_volume_mirror_reduce_act", y.device, y.data_ptr(), dtype, out.data_ptr(), V, N.int_array(views), code, B, C, D, H, W, act,
+             temperature)
     return out
 
 
@@ -187,12 +180,7 @@ def mirror_volume_deaugment(y: torch.Tensor, mirror: str = "dhw",
                 y = y.contiguous()
             out = torch.empty((B,) + tuple(y.shape[1:]), device=y.device, dtype=y.dtype)
             _, C, D, H, W = y.shape
-            lib = N.load()
-            with N.on_device(y.device):
-                rc = lib.ptb_volume_mirror_reduce(y.data_ptr(), dtype, out.data_ptr(), V, N.int_array(views), code, B, C, D, H, W,
-                                                  N.stream_ptr(y.device))
-            N.bump()
-            N.check(rc, "ptb_volume_mirror_reduce")
+            N.launch("ptb_volume_mirror_reduce", y.device, y.data_ptr(), dtype, out.data_ptr(), V, N.int_array(views), code, B, C, D, H, W)
             return out
         stack = _mirror(y, dtype, views, False, (V, B) + tuple(y.shape[1:]))
     if code is not None:

@@ -25,21 +25,15 @@ SUM_SLOTS = 64  # PTB_SUM_SLOTS: the kernels spread their fp64 atomics over this
 # PTB_SKIP_LABEL_CHECK=1 disables the check.
 _CHECK_LABELS = os.environ.get("PTB_SKIP_LABEL_CHECK", "0") != "1"
 SYNC_LABEL_CHECK = os.environ.get("PTB_SYNC_LABEL_CHECK", "0") == "1"
-_LABEL_MSG = "Class values must be smaller than num_classes."
+LABEL_MSG = "Class values must be smaller than num_classes."
 _pending = []  # (pinned host int32 tensor, event)
 ONE_LAUNCH_REGION_LOSS = os.environ.get("PTB_ONE_LAUNCH_REGION_LOSS", "1") != "0"   # (A/B switch: 0 = kernel + finalize-free epilogue launch)
 _pending_lock = threading.Lock()
 
 
-def _f32c(t, what):
+def as_f32(t, what):
     N.require_device(t, what)
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
+    return (t if t.dtype == torch.float32 else t.float()).contiguous()
 
 
 def _poll(block: bool):
@@ -58,7 +52,7 @@ def _poll(block: bool):
         with _pending_lock:
             _pending = keep + _pending
     if bad:
-        raise RuntimeError(_LABEL_MSG + " (reported asynchronously by an earlier loss call)")
+        raise RuntimeError(LABEL_MSG + " (reported asynchronously by an earlier loss call)")
 
 
 def flush_label_check():
@@ -67,19 +61,12 @@ def flush_label_check():
 
 
 def check_labels(flag):
+    """Copy a device label flag to pinned host memory on the current stream and have it examined (see ``watch_host_flag``)."""
     if not _CHECK_LABELS:
         return
-    if SYNC_LABEL_CHECK:
-        if int(flag.item()) != 0:
-            raise RuntimeError(_LABEL_MSG)
-        return
-    _poll(block=False)
     host = torch.empty(1, dtype=torch.int32, pin_memory=True)
     host.copy_(flag, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream(flag.device))
-    with _pending_lock:
-        _pending.append((host, ev))
+    watch_host_flag(host, flag.device)
 
 
 _flag_ring = None        # pinned int32 [256]: label flags the kernels of the one-launch region loss write straight into host memory
@@ -105,13 +92,14 @@ def host_flag_slot():
 
 
 def watch_host_flag(slot, device):
-    """Register a pinned flag slot the launch just issued on the current stream will write (see ``check_labels``)."""
+    """Register a pinned int32 the work just issued on the current stream of ``device`` will write: it is examined at the next
+    loss call, or right away (one host synchronisation) under ``SYNC_LABEL_CHECK``."""
     if not _CHECK_LABELS:
         return
     if SYNC_LABEL_CHECK:
         torch.cuda.current_stream(device).synchronize()
         if int(slot[0]) != 0:
-            raise RuntimeError(_LABEL_MSG)
+            raise RuntimeError(LABEL_MSG)
         return
     _poll(block=False)
     ev = torch.cuda.Event()
@@ -126,7 +114,7 @@ def region_workspace(device, C):
     need = int(N.load().ptb_region_workspace_bytes(C))
     if need < 0:
         return None
-    key = (device.index, N._raw_stream(device.index) if N._raw_stream is not None else torch.cuda.current_stream(device).cuda_stream)
+    key = (device.index, N.raw_stream(device.index))
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < need:
         if len(_workspaces) >= 64:            # (streams come and go: forget the oldest half; a workspace is recreated zeroed on demand)
@@ -147,11 +135,39 @@ def finalize(sums, flag=None):
     """[row] float64 = the slots added up by ``ptb_sums_finalize``; NaN when the kernel raised the label flag (a label outside
     [0, C) that is not ignore_index can therefore never yield a finite loss, whatever the asynchronous host check does)."""
     out = torch.empty(sums.shape[1], dtype=torch.float64, device=sums.device)
-    lib = N.load()
-    with N.on_device(sums.device):
-        rc = lib.ptb_sums_finalize(sums.data_ptr(), sums.shape[0], sums.shape[1], out.data_ptr(), _ptr(flag), N.stream_ptr(sums.device))
-    N.check(rc, "ptb_sums_finalize")
+    N.launch("ptb_sums_finalize", sums.device, sums.data_ptr(), sums.shape[0], sums.shape[1], out.data_ptr(), N.ptr(flag), count=False)
     return out
+
+
+def fold_map_grad(coef, g_map, has_map, skip_empty=False):
+    """Backward of a forward that returned sums and, on request, the unreduced map: ``coef`` is the upstream gradient on the sums
+    (one or two entries) and ``g_map`` the one on the map.  The map's gradient is ``(coef[0] + g_map) * dL``, so the scalar is folded
+    into the map and its multiplier becomes 1.  Returns ``(coef, grad_map)``, unchanged and None when there is no map gradient."""
+    if not has_map or g_map is None or (skip_empty and not g_map.numel()):
+        return coef, None
+    grad_map = (g_map.to(torch.float32) + coef[0]).contiguous()
+    if coef.numel() == 1:
+        return torch.ones(1, device=coef.device), grad_map
+    return torch.stack([torch.ones((), device=coef.device), coef[1]]), grad_map
+
+
+def fused_seg_bwd(x, labels, dense, class_weights, kf, gi, gp, flags, prob, gamma, alpha, threshold, ignore_label, ignore_value):
+    """d/dx of the focal sums (coefficients ``kf``) plus the region statistics (``gi``, ``gp``) in one kernel; where that kernel does
+    not apply (C > 16, unaligned, ...) two kernels and an add.  Either way one counted call, counted once everything was launched."""
+    B, C, HW = x.shape
+    grad = torch.empty_like(x)
+    rc = N.launch("ptb_seg_fused_bwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), N.ptr(class_weights), kf.data_ptr(), gi.data_ptr(),
+                  gp.data_ptr(), grad.data_ptr(), B, C, HW, flags, prob, gamma, alpha, threshold, ignore_label, ignore_value,
+                  raw=True, count="ok")
+    if rc != N.PTB_EUNSUPPORTED:
+        N.check(rc, "ptb_seg_fused_bwd")
+        return grad
+    grad2 = torch.empty_like(x)
+    N.launch("ptb_focal_bwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), N.ptr(class_weights), kf.data_ptr(), None, grad.data_ptr(),
+             B, C, HW, flags, gamma, alpha, threshold, ignore_label, ignore_value, count=False)
+    N.launch("ptb_seg_stats_bwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), gi.data_ptr(), gp.data_ptr(), grad2.data_ptr(),
+             B, C, HW, SEG_STATS | (flags & SEG_HAS_IGNORE), prob, ignore_label, ignore_value, count="ok")
+    return grad.add_(grad2)
 
 
 class SigmoidFocalSums(torch.autograd.Function):
@@ -164,13 +180,8 @@ class SigmoidFocalSums(torch.autograd.Function):
         B, C, HW = x.shape
         sums, flag = new_sums(2 + 3 * C, x.device)
         elem = torch.empty_like(x) if flags & SEG_ELEMWISE else None
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_seg_loss_fwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(class_weights), sums.data_ptr(), _ptr(elem),
-                                      flag.data_ptr(), B, C, HW, flags | SEG_FOCAL, PROB_SIGMOID, gamma, alpha, threshold,
-                                      ignore_label, ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_seg_loss_fwd")
+        N.launch("ptb_seg_loss_fwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), N.ptr(class_weights), sums.data_ptr(), N.ptr(elem),
+                 flag.data_ptr(), B, C, HW, flags | SEG_FOCAL, PROB_SIGMOID, gamma, alpha, threshold, ignore_label, ignore_value)
         if labels is not None:
             check_labels(flag)
         ctx.save_for_backward(x, labels, dense, class_weights)
@@ -188,19 +199,10 @@ class SigmoidFocalSums(torch.autograd.Function):
         flags, gamma, alpha, threshold, ignore_label, ignore_value = ctx.cfg
         B, C, HW = x.shape
         coef = g_sums.to(torch.float32).contiguous() if g_sums is not None else torch.zeros(2, device=x.device)
-        grad_elem = None
-        if ctx.has_elem and g_elem is not None:
-            # grad = (g_sums[0] + g_elem) * dL + g_sums[1] * dF: fold the scalar into the map, multiplier 1
-            grad_elem = (g_elem.to(torch.float32) + coef[0]).contiguous()
-            coef = torch.stack([torch.ones((), device=x.device), coef[1]])
+        coef, grad_elem = fold_map_grad(coef, g_elem, ctx.has_elem)     # grad = (g_sums[0] + g_elem) * dL + g_sums[1] * dF
         grad = torch.empty_like(x)
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_focal_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(class_weights), coef.data_ptr(), _ptr(grad_elem),
-                                   grad.data_ptr(), B, C, HW, flags, gamma, alpha, threshold, ignore_label, ignore_value,
-                                   N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_focal_bwd")
+        N.launch("ptb_focal_bwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), N.ptr(class_weights), coef.data_ptr(), N.ptr(grad_elem),
+                 grad.data_ptr(), B, C, HW, flags, gamma, alpha, threshold, ignore_label, ignore_value)
         return grad, None, None, None, None, None, None, None, None, None
 
 
@@ -235,14 +237,12 @@ class FocalScalar(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         coef = torch.empty(2 + 2 * C, dtype=torch.float32, device=x.device)
         slot = host_flag_slot() if _CHECK_LABELS else None
-        with N.on_device(x.device):
-            rc = N.load().ptb_region_loss_fwd(x.data_ptr(), labels.data_ptr(), None, None, ws.data_ptr(), B, C, HW, flags | SEG_FOCAL, PROB_SIGMOID,
-                                              gamma, 0.0, 0.0, 0, 0.0, scale, 0.0, 0.0, 0.0, 1e-7, 0, None, C, loss.data_ptr(), coef.data_ptr(),
-                                              _ptr(slot), N.stream_ptr(x.device))
+        rc = N.launch("ptb_region_loss_fwd", x.device, x.data_ptr(), labels.data_ptr(), None, None, ws.data_ptr(), B, C, HW, flags | SEG_FOCAL,
+                      PROB_SIGMOID, gamma, 0.0, 0.0, 0, 0.0, scale, 0.0, 0.0, 0.0, 1e-7, 0, None, C, loss.data_ptr(), coef.data_ptr(),
+                      N.ptr(slot), raw=True, count="ok")
         if rc == N.PTB_EUNSUPPORTED:
             return None
         N.check(rc, "ptb_region_loss_fwd (focal)")
-        N.bump()
         if slot is not None:
             watch_host_flag(slot, x.device)
         return loss, coef
@@ -263,11 +263,8 @@ class FocalScalar(torch.autograd.Function):
         B, C, HW = x.shape
         coef = torch.stack([g.to(torch.float32) * scale, torch.zeros((), device=x.device)]).contiguous()
         grad = torch.empty_like(x)
-        with N.on_device(x.device):
-            rc = N.load().ptb_focal_bwd(x.data_ptr(), labels.data_ptr(), None, None, coef.data_ptr(), None, grad.data_ptr(), B, C, HW, flags, gamma,
-                                        0.0, 0.0, 0, 0.0, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_focal_bwd")
+        N.launch("ptb_focal_bwd", x.device, x.data_ptr(), labels.data_ptr(), None, None, coef.data_ptr(), None, grad.data_ptr(), B, C, HW, flags,
+                 gamma, 0.0, 0.0, 0, 0.0)
         return grad, None, None, None, None
 
 
@@ -283,13 +280,8 @@ class SoftmaxActFocalSums(torch.autograd.Function):
         weights, cw_mode, cw_n, cw_div = cw
         sums, flag = new_sums(2, x.device)
         elem = torch.empty_like(x) if flags & SEG_ELEMWISE else None
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_focal_softmax_fwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(weights), cw_mode, cw_n, cw_div, sums.data_ptr(),
-                                           _ptr(elem), flag.data_ptr(), B, C, HW, flags | SEG_FOCAL, gamma, alpha, threshold, ignore_label,
-                                           ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_focal_softmax_fwd")
+        N.launch("ptb_focal_softmax_fwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), N.ptr(weights), cw_mode, cw_n, cw_div,
+                 sums.data_ptr(), N.ptr(elem), flag.data_ptr(), B, C, HW, flags | SEG_FOCAL, gamma, alpha, threshold, ignore_label, ignore_value)
         if labels is not None:
             check_labels(flag)
         ctx.save_for_backward(x, labels, dense, weights)
@@ -303,18 +295,10 @@ class SoftmaxActFocalSums(torch.autograd.Function):
         flags, gamma, alpha, threshold, ignore_label, ignore_value, cw_mode, cw_n, cw_div = ctx.cfg
         B, C, HW = x.shape
         coef = g_sums.to(torch.float32).contiguous() if g_sums is not None else torch.zeros(2, device=x.device)
-        grad_elem = None
-        if ctx.has_elem and g_elem is not None:
-            grad_elem = (g_elem.to(torch.float32) + coef[0]).contiguous()   # (g_sums[0] + g_elem) * dL: multiplier 1
-            coef = torch.stack([torch.ones((), device=x.device), coef[1]])
+        coef, grad_elem = fold_map_grad(coef, g_elem, ctx.has_elem)
         grad = torch.empty_like(x)
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_focal_softmax_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(weights), cw_mode, cw_n, cw_div, coef.data_ptr(),
-                                           _ptr(grad_elem), grad.data_ptr(), B, C, HW, flags, gamma, alpha, threshold, ignore_label,
-                                           ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_focal_softmax_bwd")
+        N.launch("ptb_focal_softmax_bwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), N.ptr(weights), cw_mode, cw_n, cw_div,
+                 coef.data_ptr(), N.ptr(grad_elem), grad.data_ptr(), B, C, HW, flags, gamma, alpha, threshold, ignore_label, ignore_value)
         return grad, None, None, None, None, None, None, None, None, None
 
 
@@ -326,12 +310,8 @@ class RegionStats(torch.autograd.Function):
         B, C, HW = x.shape
         sums, flag = new_sums(2 + 3 * C, x.device)
         flags = SEG_STATS | (SEG_HAS_IGNORE if has_ignore else 0)
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_seg_loss_fwd(x.data_ptr(), _ptr(labels), _ptr(dense), None, sums.data_ptr(), None, flag.data_ptr(), B, C, HW,
-                                      flags, prob, 0.0, 0.0, 0.0, ignore_label, ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_seg_loss_fwd")
+        N.launch("ptb_seg_loss_fwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), None, sums.data_ptr(), None, flag.data_ptr(), B, C, HW,
+                 flags, prob, 0.0, 0.0, 0.0, ignore_label, ignore_value)
         if labels is not None:
             check_labels(flag)
         ctx.save_for_backward(x, labels, dense)
@@ -345,12 +325,8 @@ class RegionStats(torch.autograd.Function):
         B, C, HW = x.shape
         g = g.to(torch.float32).contiguous()
         grad = torch.empty_like(x)
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_seg_stats_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), g[0].data_ptr(), g[1].data_ptr(), grad.data_ptr(),
-                                       B, C, HW, flags, prob, ignore_label, ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_seg_stats_bwd")
+        N.launch("ptb_seg_stats_bwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), g[0].data_ptr(), g[1].data_ptr(), grad.data_ptr(),
+                 B, C, HW, flags, prob, ignore_label, ignore_value)
         return grad, None, None, None, None, None, None
 
 
@@ -362,12 +338,8 @@ class SoftmaxFocalSums(torch.autograd.Function):
         B, C, HW = x.shape
         sums, flag = new_sums(2, x.device)
         pix = torch.empty((B, HW), dtype=torch.float32, device=x.device) if want_map else None
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_softmax_focal_fwd(x.data_ptr(), labels.data_ptr(), _ptr(class_weights), sums.data_ptr(), _ptr(pix),
-                                           flag.data_ptr(), B, C, HW, reduced, gamma, threshold, ignore_label, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_softmax_focal_fwd")
+        N.launch("ptb_softmax_focal_fwd", x.device, x.data_ptr(), labels.data_ptr(), N.ptr(class_weights), sums.data_ptr(), N.ptr(pix),
+                 flag.data_ptr(), B, C, HW, reduced, gamma, threshold, ignore_label)
         check_labels(flag)
         ctx.save_for_backward(x, labels, class_weights)
         ctx.cfg = (reduced, gamma, threshold, ignore_label)
@@ -380,17 +352,10 @@ class SoftmaxFocalSums(torch.autograd.Function):
         reduced, gamma, threshold, ignore_label = ctx.cfg
         B, C, HW = x.shape
         coef = g_sums.to(torch.float32).contiguous()
-        grad_pix = None
-        if ctx.has_map and g_pix is not None:
-            grad_pix = (g_pix.to(torch.float32) + coef[0]).contiguous()
-            coef = torch.stack([torch.ones((), device=x.device), coef[1]])
+        coef, grad_pix = fold_map_grad(coef, g_pix, ctx.has_map)
         grad = torch.empty_like(x)
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_softmax_focal_bwd(x.data_ptr(), labels.data_ptr(), _ptr(class_weights), coef.data_ptr(), _ptr(grad_pix),
-                                           grad.data_ptr(), B, C, HW, reduced, gamma, threshold, ignore_label, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_softmax_focal_bwd")
+        N.launch("ptb_softmax_focal_bwd", x.device, x.data_ptr(), labels.data_ptr(), N.ptr(class_weights), coef.data_ptr(), N.ptr(grad_pix),
+                 grad.data_ptr(), B, C, HW, reduced, gamma, threshold, ignore_label)
         return grad, None, None, None, None, None, None, None
 
 
@@ -409,13 +374,8 @@ class FusedSegSums(torch.autograd.Function):
     def forward(ctx, x, labels, dense, class_weights, flags, prob, gamma, alpha, threshold, ignore_label, ignore_value):
         B, C, HW = x.shape
         sums, flag = new_sums(2 + 3 * C, x.device)
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_seg_loss_fwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(class_weights), sums.data_ptr(), None,
-                                      flag.data_ptr(), B, C, HW, flags | SEG_FOCAL | SEG_STATS, prob, gamma, alpha, threshold,
-                                      ignore_label, ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_seg_loss_fwd")
+        N.launch("ptb_seg_loss_fwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), N.ptr(class_weights), sums.data_ptr(), None,
+                 flag.data_ptr(), B, C, HW, flags | SEG_FOCAL | SEG_STATS, prob, gamma, alpha, threshold, ignore_label, ignore_value)
         if labels is not None:
             check_labels(flag)
         ctx.save_for_backward(x, labels, dense, class_weights)
@@ -427,31 +387,10 @@ class FusedSegSums(torch.autograd.Function):
     def backward(ctx, g_focal, g_stats):
         x, labels, dense, class_weights = ctx.saved_tensors
         flags, prob, gamma, alpha, threshold, ignore_label, ignore_value = ctx.cfg
-        B, C, HW = x.shape
-        lib = N.load()
-        grad = torch.empty_like(x)
         coef = g_focal.to(torch.float32).contiguous()
         gs = g_stats.to(torch.float32).contiguous()
-        with N.on_device(x.device):
-            rc = lib.ptb_seg_fused_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(class_weights), coef.data_ptr(), gs[0].data_ptr(),
-                                       gs[1].data_ptr(), grad.data_ptr(), B, C, HW, flags, prob, gamma, alpha, threshold, ignore_label,
-                                       ignore_value, N.stream_ptr(x.device))
-        if rc == 0:
-            N.bump()
-            return grad, None, None, None, None, None, None, None, None, None, None
-        if rc != -2:
-            N.check(rc, "ptb_seg_fused_bwd")
-        grad2 = torch.empty_like(x)
-        with N.on_device(x.device):
-            rc = lib.ptb_focal_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(class_weights), coef.data_ptr(), None, grad.data_ptr(),
-                                   B, C, HW, flags, gamma, alpha, threshold, ignore_label, ignore_value, N.stream_ptr(x.device))
-            N.check(rc, "ptb_focal_bwd")
-            sflags = flags & SEG_HAS_IGNORE
-            rc = lib.ptb_seg_stats_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), gs[0].data_ptr(), gs[1].data_ptr(), grad2.data_ptr(),
-                                       B, C, HW, SEG_STATS | sflags, prob, ignore_label, ignore_value, N.stream_ptr(x.device))
-            N.check(rc, "ptb_seg_stats_bwd")
-        N.bump()
-        return grad.add_(grad2), None, None, None, None, None, None, None, None, None, None
+        grad = fused_seg_bwd(x, labels, dense, class_weights, coef, gs[0], gs[1], flags, prob, gamma, alpha, threshold, ignore_label, ignore_value)
+        return grad, None, None, None, None, None, None, None, None, None, None
 
 
 class RegionLoss(torch.autograd.Function):
@@ -466,36 +405,27 @@ class RegionLoss(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         coef = torch.empty(2 + 2 * C, dtype=torch.float32, device=x.device)
         what = SEG_STATS | (SEG_FOCAL if with_focal else 0)
-        lib = N.load()
         ctx.save_for_backward(x, labels, dense, class_weights, coef)
         ctx.cfg = (flags, prob, gamma, alpha, threshold, ignore_label, ignore_value, with_focal)
+        tail = (focal_scale if with_focal else 0.0, dice_weight, jaccard_weight, smooth, eps, 1 if log_loss else 0, N.ptr(class_mask), n_selected,
+                loss.data_ptr(), coef.data_ptr())
         ws = region_workspace(x.device, C) if ONE_LAUNCH_REGION_LOSS else None
         if ws is not None:
             # one launch: the streaming kernel's last workgroup adds up the slots, evaluates the tail and its derivative and leaves
             # the workspace zeroed (no memset / finalize / epilogue launches, no device-to-host copy of the label flag)
             slot = host_flag_slot() if (labels is not None and _CHECK_LABELS) else None
-            with N.on_device(x.device):
-                rc = lib.ptb_region_loss_fwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(class_weights), ws.data_ptr(), B, C, HW, flags | what,
-                                             prob, gamma, alpha, threshold, ignore_label, ignore_value, focal_scale if with_focal else 0.0,
-                                             dice_weight, jaccard_weight, smooth, eps, 1 if log_loss else 0, _ptr(class_mask), n_selected,
-                                             loss.data_ptr(), coef.data_ptr(), _ptr(slot), N.stream_ptr(x.device))
+            rc = N.launch("ptb_region_loss_fwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), N.ptr(class_weights), ws.data_ptr(), B, C, HW,
+                          flags | what, prob, gamma, alpha, threshold, ignore_label, ignore_value, *tail, N.ptr(slot), raw=True, count="ok")
             if rc != N.PTB_EUNSUPPORTED:
                 N.check(rc, "ptb_region_loss_fwd")
-                N.bump()
                 if slot is not None:
                     watch_host_flag(slot, x.device)
                 return loss
         sums, flag = new_sums(2 + 3 * C, x.device)
-        with N.on_device(x.device):
-            rc = lib.ptb_seg_loss_fwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(class_weights), sums.data_ptr(), None,
-                                      flag.data_ptr(), B, C, HW, flags | what, prob, gamma, alpha, threshold, ignore_label, ignore_value,
-                                      N.stream_ptr(x.device))
-            N.check(rc, "ptb_seg_loss_fwd")
-            rc = lib.ptb_region_epilogue(sums.data_ptr(), SUM_SLOTS, C, focal_scale if with_focal else 0.0, dice_weight, jaccard_weight,
-                                         smooth, eps, 1 if log_loss else 0, _ptr(class_mask), n_selected, loss.data_ptr(),
-                                         coef.data_ptr(), flag.data_ptr() if labels is not None else None, N.stream_ptr(x.device))
-            N.check(rc, "ptb_region_epilogue")
-        N.bump()
+        N.launch("ptb_seg_loss_fwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), N.ptr(class_weights), sums.data_ptr(), None,
+                 flag.data_ptr(), B, C, HW, flags | what, prob, gamma, alpha, threshold, ignore_label, ignore_value, count=False)
+        N.launch("ptb_region_epilogue", x.device, sums.data_ptr(), SUM_SLOTS, C, *tail, N.ptr(flag if labels is not None else None),
+                 count="ok")
         if labels is not None:
             check_labels(flag)
         return loss
@@ -507,30 +437,10 @@ class RegionLoss(torch.autograd.Function):
         B, C, HW = x.shape
         k = coef * g.to(torch.float32)          # upstream gradient folded into the coefficient arrays (device side)
         kf, gi, gp = k[:2], k[2:2 + C], k[2 + C:]
-        grad = torch.empty_like(x)
-        lib = N.load()
-        none = (None,) * 19
-        with N.on_device(x.device):
-            if with_focal:
-                rc = lib.ptb_seg_fused_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(class_weights), kf.data_ptr(), gi.data_ptr(),
-                                           gp.data_ptr(), grad.data_ptr(), B, C, HW, flags, prob, gamma, alpha, threshold, ignore_label,
-                                           ignore_value, N.stream_ptr(x.device))
-                if rc == -2:   # the fused kernel does not apply (C > 16, unaligned, ...): two kernels and an add
-                    grad2 = torch.empty_like(x)
-                    rc = lib.ptb_focal_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), _ptr(class_weights), kf.data_ptr(), None, grad.data_ptr(),
-                                           B, C, HW, flags, gamma, alpha, threshold, ignore_label, ignore_value, N.stream_ptr(x.device))
-                    N.check(rc, "ptb_focal_bwd")
-                    rc = lib.ptb_seg_stats_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), gi.data_ptr(), gp.data_ptr(), grad2.data_ptr(),
-                                               B, C, HW, SEG_STATS | (flags & SEG_HAS_IGNORE), prob, ignore_label, ignore_value,
-                                               N.stream_ptr(x.device))
-                    N.check(rc, "ptb_seg_stats_bwd")
-                    grad.add_(grad2)
-                else:
-                    N.check(rc, "ptb_seg_fused_bwd")
-            else:
-                rc = lib.ptb_seg_stats_bwd(x.data_ptr(), _ptr(labels), _ptr(dense), gi.data_ptr(), gp.data_ptr(), grad.data_ptr(),
-                                           B, C, HW, SEG_STATS | (flags & SEG_HAS_IGNORE), prob, ignore_label, ignore_value,
-                                           N.stream_ptr(x.device))
-                N.check(rc, "ptb_seg_stats_bwd")
-        N.bump()
-        return (grad,) + none
+        if with_focal:
+            grad = fused_seg_bwd(x, labels, dense, class_weights, kf, gi, gp, flags, prob, gamma, alpha, threshold, ignore_label, ignore_value)
+        else:
+            grad = torch.empty_like(x)
+            N.launch("ptb_seg_stats_bwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), gi.data_ptr(), gp.data_ptr(), grad.data_ptr(),
+                     B, C, HW, SEG_STATS | (flags & SEG_HAS_IGNORE), prob, ignore_label, ignore_value, count="ok")
+        return (grad,) + (None,) * 19

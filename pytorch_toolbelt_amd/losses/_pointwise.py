@@ -8,15 +8,10 @@ needs d(loss)/d(sum), handed to the kernels as device arrays -- nothing synchron
 import torch
 
 from .. import _native as N
-from ._kernels import _ptr, check_labels, finalize, new_sums
+from ._kernels import as_f32, check_labels, finalize, fold_map_grad, new_sums  # noqa: F401  (as_f32: the loss modules reach it as P.as_f32)
 
 SOFT_BCE, BALANCED_BCE, QFL, WING, LOGCOSH, SOFT_F1 = range(6)
 F_IGNORE, F_SMOOTH = 1, 2
-
-
-def as_f32(t, what):
-    N.require_device(t, what)
-    return (t if t.dtype == torch.float32 else t.float()).contiguous()
 
 
 class PointwiseSums(torch.autograd.Function):
@@ -26,12 +21,8 @@ class PointwiseSums(torch.autograd.Function):
     def forward(ctx, x, t, chan_w, chan_pw, kind, flags, p0, p1, p2, ignore_value, C, HW, want_elem):
         sums, _ = new_sums(4, x.device, with_flag=False)
         elem = torch.empty_like(x) if want_elem else None
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_pointwise_loss_fwd(kind, x.data_ptr(), t.data_ptr(), _ptr(chan_w), _ptr(chan_pw), sums.data_ptr(), _ptr(elem),
-                                            x.numel(), C, HW, flags, p0, p1, p2, ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_pointwise_loss_fwd")
+        N.launch("ptb_pointwise_loss_fwd", x.device, kind, x.data_ptr(), t.data_ptr(), N.ptr(chan_w), N.ptr(chan_pw), sums.data_ptr(), N.ptr(elem),
+                 x.numel(), C, HW, flags, p0, p1, p2, ignore_value)
         ctx.save_for_backward(x, t, chan_w, chan_pw)
         ctx.cfg = (kind, flags, p0, p1, p2, ignore_value, C, HW)
         ctx.has_elem = want_elem
@@ -46,20 +37,11 @@ class PointwiseSums(torch.autograd.Function):
             coef = torch.stack([-g[0], -g[1]])
         else:
             coef = torch.stack([g[0], g[1]])
-        grad_elem = None
-        if ctx.has_elem and g_elem is not None and g_elem.numel():
-            # grad = (g_sums[0] + g_elem) * dL: fold the scalar into the map and use multiplier 1
-            grad_elem = (g_elem.to(torch.float32) + coef[0]).contiguous()
-            coef = torch.stack([torch.ones((), device=x.device), coef[1]])
+        coef, grad_elem = fold_map_grad(coef, g_elem, ctx.has_elem, skip_empty=True)
         coef = coef.contiguous()
         grad = torch.empty_like(x)
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_pointwise_loss_apply(kind, 0, x.data_ptr(), t.data_ptr(), _ptr(chan_w), _ptr(chan_pw), coef.data_ptr(),
-                                              _ptr(grad_elem), grad.data_ptr(), x.numel(), C, HW, flags, p0, p1, p2, ignore_value,
-                                              N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_pointwise_loss_apply")
+        N.launch("ptb_pointwise_loss_apply", x.device, kind, 0, x.data_ptr(), t.data_ptr(), N.ptr(chan_w), N.ptr(chan_pw), coef.data_ptr(),
+                 N.ptr(grad_elem), grad.data_ptr(), x.numel(), C, HW, flags, p0, p1, p2, ignore_value)
         return (grad,) + (None,) * 12
 
 
@@ -70,12 +52,8 @@ class BalancedElementwise(torch.autograd.Function):
     def forward(ctx, x, t, w, flags, ignore_value):
         out = torch.empty_like(x)
         w = w.to(torch.float32).contiguous()
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_pointwise_loss_apply(BALANCED_BCE, 1, x.data_ptr(), t.data_ptr(), None, None, w.data_ptr(), None, out.data_ptr(),
-                                              x.numel(), 1, 1, flags, 0.0, 0.0, 0.0, ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_pointwise_loss_apply")
+        N.launch("ptb_pointwise_loss_apply", x.device, BALANCED_BCE, 1, x.data_ptr(), t.data_ptr(), None, None, w.data_ptr(), None, out.data_ptr(),
+                 x.numel(), 1, 1, flags, 0.0, 0.0, 0.0, ignore_value)
         ctx.save_for_backward(x, t, w)
         ctx.cfg = (flags, ignore_value)
         return out
@@ -86,12 +64,8 @@ class BalancedElementwise(torch.autograd.Function):
         flags, ignore_value = ctx.cfg
         grad = torch.empty_like(x)
         g = g.to(torch.float32).contiguous()
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_pointwise_loss_apply(BALANCED_BCE, 0, x.data_ptr(), t.data_ptr(), None, None, w.data_ptr(), g.data_ptr(),
-                                              grad.data_ptr(), x.numel(), 1, 1, flags, 0.0, 0.0, 0.0, ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_pointwise_loss_apply")
+        N.launch("ptb_pointwise_loss_apply", x.device, BALANCED_BCE, 0, x.data_ptr(), t.data_ptr(), None, None, w.data_ptr(), g.data_ptr(),
+                 grad.data_ptr(), x.numel(), 1, 1, flags, 0.0, 0.0, 0.0, ignore_value)
         return grad, None, None, None, None
 
 
@@ -104,12 +78,8 @@ class SoftCESums(torch.autograd.Function):
         B, C, HW = x.shape
         sums, flag = new_sums(4, x.device)
         pix = torch.empty((B, HW), dtype=torch.float32, device=x.device) if want_map else None
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_soft_ce_fwd(x.data_ptr(), labels.data_ptr(), sums.data_ptr(), _ptr(pix), flag.data_ptr(), B, C, HW, eps,
-                                     1 if has_ignore else 0, ignore_label, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_soft_ce_fwd")
+        N.launch("ptb_soft_ce_fwd", x.device, x.data_ptr(), labels.data_ptr(), sums.data_ptr(), N.ptr(pix), flag.data_ptr(), B, C, HW, eps,
+                 1 if has_ignore else 0, ignore_label)
         check_labels(flag)
         ctx.save_for_backward(x, labels)
         ctx.cfg = (eps, has_ignore, ignore_label)
@@ -123,18 +93,11 @@ class SoftCESums(torch.autograd.Function):
         eps, has_ignore, ignore_label = ctx.cfg
         B, C, HW = x.shape
         coef = g_total.to(torch.float32).reshape(1)
-        grad_pix = None
-        if ctx.has_map and g_pix is not None and g_pix.numel():
-            grad_pix = (g_pix.to(torch.float32) + coef[0]).contiguous()
-            coef = torch.ones(1, device=x.device)
+        coef, grad_pix = fold_map_grad(coef, g_pix, ctx.has_map, skip_empty=True)
         coef = coef.contiguous()
         grad = torch.empty_like(x)
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_soft_ce_bwd(x.data_ptr(), labels.data_ptr(), coef.data_ptr(), _ptr(grad_pix), grad.data_ptr(), B, C, HW, eps,
-                                     1 if has_ignore else 0, ignore_label, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_soft_ce_bwd")
+        N.launch("ptb_soft_ce_bwd", x.device, x.data_ptr(), labels.data_ptr(), coef.data_ptr(), N.ptr(grad_pix), grad.data_ptr(), B, C, HW, eps,
+                 1 if has_ignore else 0, ignore_label)
         return grad, None, None, None, None, None
 
 
@@ -145,12 +108,8 @@ class BiTemperedBinarySums(torch.autograd.Function):
     def forward(ctx, x, t, t1, t2, smoothing, iters, has_ignore, ignore_value, want_elem):
         sums, _ = new_sums(4, x.device, with_flag=False)
         elem = torch.empty_like(x) if want_elem else None
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_bitempered_binary_fwd(x.data_ptr(), t.data_ptr(), sums.data_ptr(), _ptr(elem), x.numel(), t1, t2, smoothing, iters,
-                                               1 if has_ignore else 0, ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_bitempered_binary_fwd")
+        N.launch("ptb_bitempered_binary_fwd", x.device, x.data_ptr(), t.data_ptr(), sums.data_ptr(), N.ptr(elem), x.numel(), t1, t2, smoothing,
+                 iters, 1 if has_ignore else 0, ignore_value)
         ctx.save_for_backward(x, t)
         ctx.cfg = (t1, t2, smoothing, iters, has_ignore, ignore_value)
         ctx.has_elem = want_elem
@@ -161,18 +120,11 @@ class BiTemperedBinarySums(torch.autograd.Function):
         x, t = ctx.saved_tensors
         t1, t2, smoothing, iters, has_ignore, ignore_value = ctx.cfg
         coef = g_sum.to(torch.float32).reshape(1)
-        grad_elem = None
-        if ctx.has_elem and g_elem is not None and g_elem.numel():
-            grad_elem = (g_elem.to(torch.float32) + coef[0]).contiguous()
-            coef = torch.ones(1, device=x.device)
+        coef, grad_elem = fold_map_grad(coef, g_elem, ctx.has_elem, skip_empty=True)
         coef = coef.contiguous()
         grad = torch.empty_like(x)
-        lib = N.load()
-        with N.on_device(x.device):
-            rc = lib.ptb_bitempered_binary_bwd(x.data_ptr(), t.data_ptr(), coef.data_ptr(), _ptr(grad_elem), grad.data_ptr(), x.numel(),
-                                               t1, t2, smoothing, iters, 1 if has_ignore else 0, ignore_value, N.stream_ptr(x.device))
-        N.bump()
-        N.check(rc, "ptb_bitempered_binary_bwd")
+        N.launch("ptb_bitempered_binary_bwd", x.device, x.data_ptr(), t.data_ptr(), coef.data_ptr(), N.ptr(grad_elem), grad.data_ptr(), x.numel(),
+                 t1, t2, smoothing, iters, 1 if has_ignore else 0, ignore_value)
         return (grad,) + (None,) * 8
 
 
@@ -183,12 +135,7 @@ class BiTemperedRows(torch.autograd.Function):
     def forward(ctx, act, onehot, t1, t2, smoothing, iters):
         R, Kc = act.shape
         loss = torch.empty(R, dtype=torch.float32, device=act.device)
-        lib = N.load()
-        with N.on_device(act.device):
-            rc = lib.ptb_bitempered_rows(act.data_ptr(), onehot.data_ptr(), None, loss.data_ptr(), R, Kc, t1, t2, smoothing, iters, 0,
-                                         N.stream_ptr(act.device))
-        N.bump()
-        N.check(rc, "ptb_bitempered_rows")
+        N.launch("ptb_bitempered_rows", act.device, act.data_ptr(), onehot.data_ptr(), None, loss.data_ptr(), R, Kc, t1, t2, smoothing, iters, 0)
         ctx.save_for_backward(act, onehot)
         ctx.cfg = (t1, t2, smoothing, iters)
         return loss
@@ -199,10 +146,6 @@ class BiTemperedRows(torch.autograd.Function):
         t1, t2, smoothing, iters = ctx.cfg
         g = g.to(torch.float32).contiguous()
         grad = torch.empty_like(act)
-        lib = N.load()
-        with N.on_device(act.device):
-            rc = lib.ptb_bitempered_rows(act.data_ptr(), onehot.data_ptr(), g.data_ptr(), grad.data_ptr(), act.shape[0], act.shape[1], t1, t2,
-                                         smoothing, iters, 1, N.stream_ptr(act.device))
-        N.bump()
-        N.check(rc, "ptb_bitempered_rows (backward)")
+        N.launch("ptb_bitempered_rows", act.device, act.data_ptr(), onehot.data_ptr(), g.data_ptr(), grad.data_ptr(), act.shape[0], act.shape[1], t1,
+                 t2, smoothing, iters, 1, what="ptb_bitempered_rows (backward)")
         return grad, None, None, None, None, None

@@ -20,7 +20,7 @@ def prepare_classes(mode, classes):
 def _dense_target(y_true, x, bs, C, y_pred):
     """Dense 0/1 (or soft) target as fp32 [B, C, HW]; the kernels take B, C, HW from the prediction, so a target with another
     element count (half-resolution mask, wrong channel count) must fail here instead of being read past its end."""
-    dense = K._f32c(y_true.to(device=x.device), "region loss")
+    dense = K.as_f32(y_true.to(device=x.device), "region loss")
     if dense.numel() != x.numel():
         raise RuntimeError(f"target shape {tuple(y_true.shape)} does not match prediction shape {tuple(y_pred.shape)}")
     return dense.reshape(bs, C, -1)
@@ -35,7 +35,7 @@ def region_statistics(y_pred, y_true, mode, from_logits, ignore_index):
 
         return sync_region_statistics.apply(H.region_statistics(y_pred, y_true, mode, from_logits, ignore_index))
     bs = y_true.size(0)
-    x = K._f32c(y_pred, "region loss")
+    x = K.as_f32(y_pred, "region loss")
     if mode == MULTICLASS_MODE:
         x = x.reshape(bs, x.size(1), -1)
         labels = y_true.to(device=x.device).reshape(bs, -1)
@@ -70,7 +70,7 @@ def _inputs(y_pred, y_true, mode, from_logits, ignore_index):
     """(x [B, C, HW], labels | None, dense | None, prob, has_ignore, ignore_label, ignore_value) for the kernels."""
     assert y_true.size(0) == y_pred.size(0)
     bs = y_true.size(0)
-    x = K._f32c(y_pred, "region loss")
+    x = K.as_f32(y_pred, "region loss")
     has_ign = ignore_index is not None
     if mode == MULTICLASS_MODE:
         x = x.reshape(bs, x.size(1), -1)

@@ -102,7 +102,6 @@ class DistanceMapLoss(torch.autograd.Function):
         Kn, _, host, dev_table = table
         has_ignore, ignore_label, ignore_value = ignore
         dims, D, H, W = geometry
-        lib = N.load()
         planes = (0 if dist_maps is not None else _distance.PLANE_TRUTH) | (_distance.PLANE_PRED if kind == HAUSDORFF else 0)
         truth, pred = dist_maps, None
         if planes:
@@ -113,17 +112,15 @@ class DistanceMapLoss(torch.autograd.Function):
             if kind == HAUSDORFF:
                 pred = maps[-1]                    # (in the form of the caller's maps: float32 distances, or the squared integers)
         maps_kind = _MAPS_I32_SQUARED if truth.dtype == torch.int32 else _MAPS_F32
-        _, _, slots = _distance.plan_maps(what, lib, dims, B, D, H, W, Kn, 1, 1 << 62)
+        _, _, slots = _distance.plan_maps(what, N.load(), dims, B, D, H, W, Kn, 1, 1 << 62)
         results = B if per_sample else 1
-        with N.on_device(x.device):
-            ws = M.scratch(16 * slots, x.device)
-            loss = torch.empty(results, dtype=torch.float32, device=x.device)
-            inv = torch.empty(results, dtype=torch.float32, device=x.device)
-            flag = torch.empty(1, dtype=torch.int32, device=x.device)
-            N.bump()
-            N.check(lib.ptb_dloss_fwd(kind, x.data_ptr(), K._ptr(labels), K._ptr(dense), host, K._ptr(dev_table), truth.data_ptr(), K._ptr(pred),
-                                      maps_kind, B, C, Kn, S, prob, int(has_ignore), ignore_label, ignore_value, alpha, int(per_sample),
-                                      ws.data_ptr(), ws.numel(), loss.data_ptr(), inv.data_ptr(), flag.data_ptr(), N.stream_ptr(x.device)), what)
+        ws = M.scratch(16 * slots, x.device)
+        loss = torch.empty(results, dtype=torch.float32, device=x.device)
+        inv = torch.empty(results, dtype=torch.float32, device=x.device)
+        flag = torch.empty(1, dtype=torch.int32, device=x.device)
+        N.launch("ptb_dloss_fwd", x.device, kind, x.data_ptr(), N.ptr(labels), N.ptr(dense), host, N.ptr(dev_table), truth.data_ptr(), N.ptr(pred),
+                 maps_kind, B, C, Kn, S, prob, int(has_ignore), ignore_label, ignore_value, alpha, int(per_sample),
+                 ws.data_ptr(), ws.numel(), loss.data_ptr(), inv.data_ptr(), flag.data_ptr(), what=what)
         if labels is not None:
             K.check_labels(flag)
         ctx.save_for_backward(x, labels, dense, truth, pred, inv, dev_table)
@@ -138,11 +135,9 @@ class DistanceMapLoss(torch.autograd.Function):
         B, C, S = x.shape
         coef = (g.reshape(-1).to(torch.float32) * inv).contiguous()        # upstream gradient / count, on the device
         grad = torch.empty_like(x)
-        with N.on_device(x.device):
-            N.bump()
-            N.check(N.load().ptb_dloss_bwd(kind, x.data_ptr(), K._ptr(labels), K._ptr(dense), host, K._ptr(dev_table), truth.data_ptr(), K._ptr(pred),
-                                           maps_kind, B, C, Kn, S, prob, int(has_ignore), ignore_label, ignore_value, alpha, int(per_sample),
-                                           coef.data_ptr(), grad.data_ptr(), N.stream_ptr(x.device)), _NAMES[kind])
+        N.launch("ptb_dloss_bwd", x.device, kind, x.data_ptr(), N.ptr(labels), N.ptr(dense), host, N.ptr(dev_table), truth.data_ptr(), N.ptr(pred),
+                 maps_kind, B, C, Kn, S, prob, int(has_ignore), ignore_label, ignore_value, alpha, int(per_sample),
+                 coef.data_ptr(), grad.data_ptr(), what=_NAMES[kind])
         return grad, None, None, None, None
 
 

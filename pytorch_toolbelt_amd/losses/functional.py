@@ -86,14 +86,14 @@ def _softmax_act_focal(output, labels, dense, softmax_dim, gamma, alpha, reducti
     if not -nd <= softmax_dim < nd:
         raise IndexError(f"Dimension out of range (expected to be in range of [{-nd}, {nd - 1}], but got {softmax_dim})")
     d = softmax_dim % nd
-    x = K._f32c(output, "focal loss")
+    x = K.as_f32(output, "focal loss")
     B, C, HW = math.prod(shape[:d]), shape[d], math.prod(shape[d + 1:])
     x = x.reshape(B, C, HW)
     flags, want_map = _focal_flags(alpha, reduced_threshold, ignore_index, normalized, reduction)
     if dense is not None:
         if tuple(dense.shape) != shape:
             raise RuntimeError(f"target shape {tuple(dense.shape)} does not match output shape {shape}")
-        dense = K._f32c(dense, "focal loss").reshape(B, C, HW)
+        dense = K.as_f32(dense, "focal loss").reshape(B, C, HW)
     else:
         if d != 1:   # index labels one-hot along dim 1 (focal.py:88-105); only that layout has the on-the-fly one-hot
             raise NotImplementedError("BinaryFocalLoss with label maps and activation='softmax' needs softmax_dim=1")
@@ -137,7 +137,7 @@ def _sigmoid_focal(output, labels, dense, gamma, alpha, reduction, normalized, r
     if not output.is_cuda:
         return H.sigmoid_focal(output, labels, dense, gamma, alpha, reduction, normalized, reduced_threshold, eps, ignore_index, class_weights)
     shape = output.shape
-    x = K.as_bchw(K._f32c(output, "focal loss"))
+    x = K.as_bchw(K.as_f32(output, "focal loss"))
     flags = 0
     if alpha is not None:
         flags |= K.SEG_HAS_ALPHA
@@ -155,7 +155,7 @@ def _sigmoid_focal(output, labels, dense, gamma, alpha, reduction, normalized, r
     if dense is not None:
         if dense.shape != shape:
             raise RuntimeError(f"target shape {tuple(dense.shape)} does not match output shape {tuple(shape)}")
-        dense = K.as_bchw(K._f32c(dense, "focal loss"))
+        dense = K.as_bchw(K.as_f32(dense, "focal loss"))
     else:
         labels = labels.to(device=x.device, dtype=torch.int64).reshape(x.shape[0], -1).contiguous()
         if labels.shape[1] != x.shape[2]:   # the kernel takes B, C, HW from the logits: a smaller target would be read past its end
@@ -207,7 +207,7 @@ def softmax_focal_loss_with_logits(
     label equals ``ignore_index`` give 0 but still count in the "mean" denominator."""
     if not output.is_cuda:
         return H.softmax_focal(output, target, class_weights, gamma, reduction, normalized, reduced_threshold, eps, ignore_index)
-    x = K.as_bchw(K._f32c(output, "softmax focal loss"))
+    x = K.as_bchw(K.as_f32(output, "softmax focal loss"))
     labels = target.to(device=x.device, dtype=torch.int64).reshape(x.shape[0], -1).contiguous()
     if labels.shape[1] != x.shape[2]:
         raise RuntimeError(f"target shape {tuple(target.shape)} does not match output shape {tuple(output.shape)}")
@@ -260,7 +260,7 @@ def _region_sums(output: torch.Tensor, target: torch.Tensor, dims):
             perm = keep + red
             o3 = output.permute(perm).reshape(1, math.prod(shape), -1)
             t3 = target.permute(perm).reshape(o3.shape)
-            stats = K.RegionStats.apply(K._f32c(o3, "soft score"), None, K._f32c(t3, "soft score"), K.PROB_IDENTITY, False, 0, 0.0)
+            stats = K.RegionStats.apply(K.as_f32(o3, "soft score"), None, K.as_f32(t3, "soft score"), K.PROB_IDENTITY, False, 0, 0.0)
             return stats[0].float().reshape(shape), (stats[1] + stats[2]).float().reshape(shape)
         if not keep:
             kept = None
@@ -271,8 +271,8 @@ def _region_sums(output: torch.Tensor, target: torch.Tensor, dims):
             for s in output.shape[:kept]:
                 lead *= int(s)
             o3 = output.reshape(lead, output.shape[kept], -1)
-    x = K._f32c(o3, "soft score")
-    t = K._f32c(target.reshape(o3.shape), "soft score")
+    x = K.as_f32(o3, "soft score")
+    t = K.as_f32(target.reshape(o3.shape), "soft score")
     stats = K.RegionStats.apply(x, None, t, K.PROB_IDENTITY, False, 0, 0.0)
     inter, card = stats[0], stats[0 + 1] + stats[2]
     if kept is None:

@@ -45,7 +45,7 @@ class FocalDiceJaccardLoss(nn.Module):
             return (wf * focal_loss + wd * R.finish(dice, true_mass, self.log_loss, self.eps, None)
                     + wj * R.finish(jacc, true_mass, self.log_loss, self.eps, None))
         bs = y_pred.size(0)
-        x = K._f32c(y_pred, "fused loss")
+        x = K.as_f32(y_pred, "fused loss")
         flags = (K.SEG_HAS_ALPHA if self.alpha is not None else 0) | (K.SEG_HAS_IGNORE if self.ignore_index is not None else 0) | K.SEG_NO_TERM
         ign = self.ignore_index
         if self.mode == R.MULTICLASS_MODE:
@@ -56,7 +56,7 @@ class FocalDiceJaccardLoss(nn.Module):
         else:
             C = 1 if self.mode == R.BINARY_MODE else x.size(1)
             x = x.reshape(bs, C, -1)
-            dense = K._f32c(y_true.to(device=x.device), "fused loss").reshape(bs, C, -1)
+            dense = K.as_f32(y_true.to(device=x.device), "fused loss").reshape(bs, C, -1)
             focal, stats = K.FusedSegSums.apply(x, None, dense, None, flags, K.PROB_SIGMOID, float(self.gamma), float(self.alpha or 0.0), 0.0,
                                                 0, float(ign) if ign is not None else 0.0)
         from ..parallel import sync_region_statistics

@@ -80,25 +80,21 @@ class HardMinedCrossEntropy(torch.autograd.Function):
         what, rule, k, t0, min_kept, ignore, per_sample = cfg
         B, C, S = x.shape
         has_ignore, ignore_label, ignore_value = ignore
-        lib = N.load()
-        nbytes = lib.ptb_hardce_workspace_bytes(int(dense is not None), B, C, S, int(per_sample))
+        nbytes = N.load().ptb_hardce_workspace_bytes(int(dense is not None), B, C, S, int(per_sample))
         if nbytes < 0:
             N.check(int(nbytes), what)
         sets = B if per_sample else 1
-        with N.on_device(x.device):
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            emap = torch.empty((B, S) if labels is not None else (B, C, S), dtype=torch.float32, device=x.device)
-            loss = torch.empty(sets, dtype=torch.float32, device=x.device)
-            thr = torch.empty(sets, dtype=torch.float32, device=x.device)
-            kept = torch.empty(sets, dtype=torch.int64, device=x.device)
-            inv = torch.empty(sets, dtype=torch.float32, device=x.device)
-            select = torch.empty((sets, 2), dtype=torch.int32, device=x.device)
-            flag = torch.empty(1, dtype=torch.int32, device=x.device)
-            N.bump()
-            N.check(lib.ptb_hardce_fwd(x.data_ptr(), K._ptr(labels), K._ptr(dense), B, C, S, int(has_ignore), ignore_label, ignore_value,
-                                       int(per_sample), rule, k, t0, min_kept, emap.data_ptr(), ws.data_ptr(), ws.numel(), loss.data_ptr(),
-                                       thr.data_ptr(), kept.data_ptr(), inv.data_ptr(), select.data_ptr(), flag.data_ptr(),
-                                       N.stream_ptr(x.device)), what)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        emap = torch.empty((B, S) if labels is not None else (B, C, S), dtype=torch.float32, device=x.device)
+        loss = torch.empty(sets, dtype=torch.float32, device=x.device)
+        thr = torch.empty(sets, dtype=torch.float32, device=x.device)
+        kept = torch.empty(sets, dtype=torch.int64, device=x.device)
+        inv = torch.empty(sets, dtype=torch.float32, device=x.device)
+        select = torch.empty((sets, 2), dtype=torch.int32, device=x.device)
+        flag = torch.empty(1, dtype=torch.int32, device=x.device)
+        N.launch("ptb_hardce_fwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), B, C, S, int(has_ignore), ignore_label, ignore_value,
+                 int(per_sample), rule, k, t0, min_kept, emap.data_ptr(), ws.data_ptr(), ws.numel(), loss.data_ptr(), thr.data_ptr(),
+                 kept.data_ptr(), inv.data_ptr(), select.data_ptr(), flag.data_ptr(), what=what)
         if labels is not None:
             K.check_labels(flag)
         ctx.save_for_backward(x, labels, dense, emap, inv, select)
@@ -115,10 +111,8 @@ class HardMinedCrossEntropy(torch.autograd.Function):
         B, C, S = x.shape
         coef = (g.reshape(-1).to(torch.float32) * inv).contiguous()        # upstream gradient / kept, on the device
         grad = torch.empty_like(x)
-        with N.on_device(x.device):
-            N.bump()
-            N.check(N.load().ptb_hardce_bwd(x.data_ptr(), K._ptr(labels), K._ptr(dense), emap.data_ptr(), B, C, S, int(per_sample), coef.data_ptr(),
-                                            select.data_ptr(), grad.data_ptr(), N.stream_ptr(x.device)), what)
+        N.launch("ptb_hardce_bwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), emap.data_ptr(), B, C, S, int(per_sample), coef.data_ptr(),
+                 select.data_ptr(), grad.data_ptr(), what=what)
         return grad, None, None, None
 
 
@@ -143,7 +137,7 @@ def _host_loss(x, labels, dense, rule, k, t0, min_kept, ignore, per_sample):
     if labels is not None:
         valid = labels != ignore_label if has_ignore else torch.ones_like(labels, dtype=torch.bool)
         if bool(((labels < 0) | (labels >= C))[valid].any()):
-            raise RuntimeError(K._LABEL_MSG)
+            raise RuntimeError(K.LABEL_MSG)
         m = xd.max(dim=1).values
         xl = xd.gather(1, torch.where(valid, labels, torch.zeros_like(labels)).unsqueeze(1)).squeeze(1)
         l = (m - xl) + torch.log(torch.exp(xd - m.unsqueeze(1)).sum(dim=1))

@@ -23,6 +23,14 @@ FUSED_TAIL = True          # False: the gscale * coef product and the zero "grad
 BINNED_GRADIENT = True     # False: the gradient is scattered to pixel order in the forward (ptb_lovasz_fwd / ptb_lovasz_bwd; A/B and tests)
 
 
+def _temp(P, S, dev):
+    """The sort's temporary storage for S segments of P pixels, and its size in bytes."""
+    tb = N.load().ptb_lovasz_temp_bytes(P, S)
+    if tb < 0:
+        raise RuntimeError("ptb_lovasz_temp_bytes failed")
+    return torch.empty(max(int(tb), 1), dtype=torch.uint8, device=dev), int(tb)
+
+
 class _LovaszSegments(torch.autograd.Function):
     """Per-segment Lovasz dot products [S] (float64) and per-segment foreground counts [S] (int32).  With ``present_only`` set
     (True: classes="present", False: all classes) the first result is the module's scalar instead (float32): the mean over
@@ -50,57 +58,42 @@ class _LovaszSegments(torch.autograd.Function):
         if n > 0 and not want_grad and KEY_ONLY_FORWARD:
             # evaluation / no_grad: a key-only sort (ptb_lovasz_fwd_keys) -- the foreground flag rides in the key, no (index, fg)
             # values exist: half the bytes per pass, two work arrays instead of four
-            lib = N.load()
             keys = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2)]
             chunk = torch.empty(S * ((P + _CHUNK - 1) // _CHUNK), dtype=torch.int32, device=dev)
-            with N.on_device(dev):
-                tb = lib.ptb_lovasz_temp_bytes(P, S)
-                if tb < 0:
-                    raise RuntimeError("ptb_lovasz_temp_bytes failed")
-                temp = torch.empty(max(int(tb), 1), dtype=torch.uint8, device=dev)
-                args = (pred.data_ptr(), K._ptr(labels), K._ptr(flabels), B, C, HW, mode, 1 if per_image else 0,
-                        1 if has_ignore else 0, ignore_label, ignore_value, keys[0].data_ptr(), keys[1].data_ptr(),
-                        chunk.data_ptr(), fg_total.data_ptr(), seg_loss.data_ptr(), temp.data_ptr(), int(tb))
-                rc = lib.ptb_lovasz_fwd_keys(*args, N.stream_ptr(dev))
-            N.bump()
-            N.check(rc, "ptb_lovasz_fwd_keys")
+            temp, tb = _temp(P, S, dev)
+            N.launch("ptb_lovasz_fwd_keys", dev, pred.data_ptr(), N.ptr(labels), N.ptr(flabels), B, C, HW, mode, 1 if per_image else 0,
+                     1 if has_ignore else 0, ignore_label, ignore_value, keys[0].data_ptr(), keys[1].data_ptr(),
+                     chunk.data_ptr(), fg_total.data_ptr(), seg_loss.data_ptr(), temp.data_ptr(), tb)
         elif n > 0:
-            lib = N.load()
             # (four allocations, not two [2, n] ones: the backward keeps only the binned pair keys[1] / vals[1] alive)
             keys = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2)]
             vals = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2)]
             chunk = torch.empty(S * ((P + _CHUNK - 1) // _CHUNK), dtype=torch.int32, device=dev)
-            with N.on_device(dev):
-                tb = lib.ptb_lovasz_temp_bytes(P, S)
-                if tb < 0:
-                    raise RuntimeError("ptb_lovasz_temp_bytes failed")
-                temp = torch.empty(max(int(tb), 1), dtype=torch.uint8, device=dev)
-                head = (pred.data_ptr(), K._ptr(labels), K._ptr(flabels), B, C, HW, mode, 1 if per_image else 0,
-                        1 if has_ignore else 0, ignore_label, ignore_value, keys[0].data_ptr(), keys[1].data_ptr(),
-                        vals[0].data_ptr(), vals[1].data_ptr(), chunk.data_ptr(), fg_total.data_ptr(), seg_loss.data_ptr())
-                tail = (temp.data_ptr(), int(tb), N.stream_ptr(dev))
-                rc = N.PTB_EUNSUPPORTED
-                if want_grad and BINNED_GRADIENT:
-                    # the gradient stays binned by pixel block (one more pass of the sort's scatter instead of n random writes);
-                    # keys[1] / vals[1] hold the pairs for the backward kernel
-                    rc = lib.ptb_lovasz_fwd_binned(*head, None, *tail)
-                    if rc >= 0:
-                        binned = (vals[1], keys[1], int(rc))
-                        rc = 0
-                if rc == N.PTB_EUNSUPPORTED:
-                    if want_grad:
-                        gpix = torch.empty(n, dtype=torch.float32, device=dev)
-                    rc = lib.ptb_lovasz_fwd(*head, gpix.data_ptr() if want_grad else None, *tail)
-            N.bump()
+            temp, tb = _temp(P, S, dev)
+            head = (pred.data_ptr(), N.ptr(labels), N.ptr(flabels), B, C, HW, mode, 1 if per_image else 0,
+                    1 if has_ignore else 0, ignore_label, ignore_value, keys[0].data_ptr(), keys[1].data_ptr(),
+                    vals[0].data_ptr(), vals[1].data_ptr(), chunk.data_ptr(), fg_total.data_ptr(), seg_loss.data_ptr())
+            rc = N.PTB_EUNSUPPORTED
+            try_binned = want_grad and BINNED_GRADIENT
+            if try_binned:
+                # the gradient stays binned by pixel block (one more pass of the sort's scatter instead of n random writes);
+                # keys[1] / vals[1] hold the pairs for the backward kernel
+                rc = N.launch("ptb_lovasz_fwd_binned", dev, *head, None, temp.data_ptr(), tb, raw=True)
+                if rc >= 0:
+                    binned = (vals[1], keys[1], int(rc))
+                    rc = 0
+            if rc == N.PTB_EUNSUPPORTED:      # (one counted call for the forward, whichever of the two served it)
+                if want_grad:
+                    gpix = torch.empty(n, dtype=torch.float32, device=dev)
+                rc = N.launch("ptb_lovasz_fwd", dev, *head, gpix.data_ptr() if want_grad else None, temp.data_ptr(), tb, raw=True,
+                              count=not try_binned)
             N.check(rc, "ptb_lovasz_fwd")
         coef_unit = None
         if present_only is not None:
             loss = torch.empty((), dtype=torch.float32, device=dev)
             coef_unit = torch.empty(S, dtype=torch.float32, device=dev)
-            with N.on_device(dev):
-                rc = N.load().ptb_lovasz_reduce(seg_loss.data_ptr(), fg_total.data_ptr(), groups, C, 1 if present_only else 0, loss.data_ptr(),
-                                                coef_unit.data_ptr(), N.stream_ptr(dev))
-            N.check(rc, "ptb_lovasz_reduce")
+            N.launch("ptb_lovasz_reduce", dev, seg_loss.data_ptr(), fg_total.data_ptr(), groups, C, 1 if present_only else 0, loss.data_ptr(),
+                     coef_unit.data_ptr(), count=False)
             seg_loss = loss
         if binned is not None:
             ctx.save_for_backward(pred, labels, flabels, gpix, coef_unit, binned[0], binned[1])
@@ -122,30 +115,21 @@ class _LovaszSegments(torch.autograd.Function):
             return (None,) * 10
         grad = torch.empty_like(pred)          # (the kernel writes every element)
         if pred.numel():
-            lib = N.load()
             g32 = g_loss.to(torch.float32)
+            head = (pred.data_ptr(), N.ptr(labels), N.ptr(flabels))
+            tail = (B, C, HW, mode, 1 if per_image else 0, 1 if has_ignore else 0, ignore_label, ignore_value)
             if FUSED_TAIL and ctx.block_log2 is not None and coef_unit is not None and g32.numel() == 1 and g32.device == pred.device:
                 # the incoming gradient of the scalar loss stays a device scalar: the kernel forms gscale * coef_unit[s] itself
                 g32 = g32.contiguous()
-                with N.on_device(pred.device):
-                    rc = lib.ptb_lovasz_bwd_binned2(pred.data_ptr(), K._ptr(labels), K._ptr(flabels), coef_unit.data_ptr(), g32.data_ptr(),
-                                                    bvals.data_ptr(), bgrad.data_ptr(), grad.data_ptr(), B, C, HW, mode, 1 if per_image else 0,
-                                                    1 if has_ignore else 0, ignore_label, ignore_value, ctx.block_log2, N.stream_ptr(pred.device))
-                N.bump()
-                N.check(rc, "ptb_lovasz_bwd_binned2")
+                N.launch("ptb_lovasz_bwd_binned2", pred.device, *head, coef_unit.data_ptr(), g32.data_ptr(), bvals.data_ptr(), bgrad.data_ptr(),
+                         grad.data_ptr(), *tail, ctx.block_log2)
                 return grad, None, None, None, None, None, None, None, None, None
             coef = (g32 * coef_unit if coef_unit is not None else g32).contiguous()
-            with N.on_device(pred.device):
-                if ctx.block_log2 is not None:
-                    rc = lib.ptb_lovasz_bwd_binned(pred.data_ptr(), K._ptr(labels), K._ptr(flabels), coef.data_ptr(), bvals.data_ptr(), bgrad.data_ptr(),
-                                                   grad.data_ptr(), B, C, HW, mode, 1 if per_image else 0, 1 if has_ignore else 0, ignore_label,
-                                                   ignore_value, ctx.block_log2, N.stream_ptr(pred.device))
-                else:
-                    rc = lib.ptb_lovasz_bwd(pred.data_ptr(), K._ptr(labels), K._ptr(flabels), coef.data_ptr(), gpix.data_ptr(), grad.data_ptr(),
-                                        B, C, HW, mode, 1 if per_image else 0, 1 if has_ignore else 0, ignore_label, ignore_value,
-                                        N.stream_ptr(pred.device))
-            N.bump()
-            N.check(rc, "ptb_lovasz_bwd")
+            if ctx.block_log2 is not None:
+                N.launch("ptb_lovasz_bwd_binned", pred.device, *head, coef.data_ptr(), bvals.data_ptr(), bgrad.data_ptr(), grad.data_ptr(), *tail,
+                         ctx.block_log2, what="ptb_lovasz_bwd")
+            else:
+                N.launch("ptb_lovasz_bwd", pred.device, *head, coef.data_ptr(), gpix.data_ptr(), grad.data_ptr(), *tail)
         return grad, None, None, None, None, None, None, None, None, None
 
 
@@ -154,7 +138,7 @@ def _lovasz_hinge(logits, labels, per_image=True, ignore_index=None):
     per_image averages the per-image losses; an image with only void pixels contributes 0."""
     if not logits.is_cuda:
         return H.lovasz_hinge(logits, labels.to(logits.device), per_image, ignore_index)
-    x = K._f32c(logits, "BinaryLovaszLoss")
+    x = K.as_f32(logits, "BinaryLovaszLoss")
     B = x.shape[0]
     x = x.reshape(B, -1)
     y = labels.to(device=x.device, dtype=torch.float32).reshape(B, -1).contiguous()
@@ -176,7 +160,7 @@ def _lovasz_softmax(probas, labels, classes="present", per_image=False, ignore_i
         return H.lovasz_softmax(probas, labels.to(probas.device), classes, per_image, ignore_index)
     if probas.dim() == 3:
         probas = probas.unsqueeze(1)
-    x = K._f32c(probas, "LovaszLoss")
+    x = K.as_f32(probas, "LovaszLoss")
     B, C = x.shape[0], x.shape[1]
     if C == 1 and len(classes) > 1:
         raise ValueError("Sigmoid output possible only with 1 class")   # reference lovasz.py:129-131 (always hit for C == 1)

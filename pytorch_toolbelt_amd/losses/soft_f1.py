@@ -29,8 +29,8 @@ def soft_micro_f1(preds: Tensor, targets: Tensor, eps=1e-6) -> Tensor:
     ``F1_c = 2 TP_c / (2 TP_c + FN_c + FP_c + eps)``, ``TP = sum p t``, ``FP = sum p (1 - t)``, ``FN = sum (1 - p) t``."""
     if preds.is_cuda and preds.dim() == 2 and targets.shape == preds.shape and preds.numel():
         n, c = preds.shape
-        x = K._f32c(preds, "soft_micro_f1")
-        t = K._f32c(targets.to(preds.device), "soft_micro_f1")
+        x = K.as_f32(preds, "soft_micro_f1")
+        t = K.as_f32(targets.to(preds.device), "soft_micro_f1")
         if c == 1:
             sums, _ = P.PointwiseSums.apply(x.reshape(-1), t.reshape(-1), None, None, P.SOFT_F1, P.F_SMOOTH, 0.0, 0.0, 0.0, 0.0, 1, 1, False)
             return _f1_from_counts(sums[0:1], sums[1:2], sums[2:3], eps).to(preds.dtype)
@@ -63,8 +63,8 @@ class BinarySoftF1Loss(nn.Module):
 
     def forward(self, preds: Tensor, targets: Tensor) -> Tensor:
         if preds.is_cuda and preds.numel():
-            x = K._f32c(preds, "BinarySoftF1Loss").reshape(-1)
-            t = K._f32c(targets.to(preds.device), "BinarySoftF1Loss").reshape(-1)
+            x = K.as_f32(preds, "BinarySoftF1Loss").reshape(-1)
+            t = K.as_f32(targets.to(preds.device), "BinarySoftF1Loss").reshape(-1)
             if t.numel() != x.numel():
                 raise RuntimeError(f"target shape {tuple(targets.shape)} does not match prediction shape {tuple(preds.shape)}")
             ign = self.ignore_index is not None
@@ -95,7 +95,7 @@ class SoftF1Loss(nn.Module):
             # softmax + one-hot + the three per-class sums in one pass over the class-major view [1, C, N]; the clamp to
             # [eps, 1 - eps] (1e-6 by default) moves a probability by at most eps -- far inside the 1e-5 parity tolerance; a caller's
             # larger eps takes the op chain below, which clamps for real
-            x = K._f32c(preds, "SoftF1Loss").t().contiguous().unsqueeze(0)
+            x = K.as_f32(preds, "SoftF1Loss").t().contiguous().unsqueeze(0)
             labels = targets.to(device=preds.device, dtype=torch.int64).reshape(1, -1).contiguous()
             if labels.shape[1] != x.shape[2]:
                 raise RuntimeError(f"target shape {tuple(targets.shape)} does not match prediction shape {tuple(preds.shape)}")

@@ -203,15 +203,10 @@ class _HipOps:
         """out[c] = (image[c] + extra[c] on the first ``extra_rows`` rows) / norm; image [C,h,W] may be a row-slice view."""
         from . import _native as N
 
-        lib = N.load()
         C, h, W = image.shape
         dev = image.device
-        with N.on_device(dev):
-            rc = lib.ptb_merge_div_ex(image.data_ptr(), norm.data_ptr(), out.data_ptr(), C, h * W, image.stride(0), out.stride(0),
-                                      extra.data_ptr() if extra is not None else None,
-                                      extra.stride(0) if extra is not None else 0, extra_rows * W, N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "ptb_merge_div_ex")
+        N.launch("ptb_merge_div_ex", dev, image.data_ptr(), norm.data_ptr(), out.data_ptr(), C, h * W, image.stride(0), out.stride(0),
+                 N.ptr(extra), extra.stride(0) if extra is not None else 0, extra_rows * W)
         return out
 
 
@@ -223,11 +218,7 @@ class _HipOps:
         r0, r1, c0, c1 = rect
         dst = image[:, r0 - top:r1 - top, c0:c1]
         dev = image.device
-        with N.on_device(dev):
-            rc = N.load().ptb_rect_add(dst.data_ptr(), buf.data_ptr(), image.shape[0], r1 - r0, c1 - c0, image.stride(0), image.stride(1),
-                                       N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "ptb_rect_add")
+        N.launch("ptb_rect_add", dev, dst.data_ptr(), buf.data_ptr(), image.shape[0], r1 - r0, c1 - c0, image.stride(0), image.stride(1))
 
 
 def deferred_geometry(plan, rank: int, crops: np.ndarray, image_height: int):
@@ -351,10 +342,7 @@ class _DeferredBand:
             return None
         dev = merger.device
         table = torch.empty(max(int(nbytes), 64), dtype=torch.uint8, device=dev)
-        with N.on_device(dev):
-            rc = lib.ptb_band_plan_upload(handle, table.data_ptr(), N.stream_ptr(dev))
-        N.bump()
-        N.check(rc, "ShardedTileMerger (deferred band plan)")
+        N.launch("ptb_band_plan_upload", dev, handle, table.data_ptr(), what="ShardedTileMerger (deferred band plan)")
         ng = ctypes.c_int()
         lib.ptb_band_plan_info(handle, ctypes.byref(ng), None, None, None, None)
         rows_arr = np.zeros(3 * ng.value, dtype=np.int64)
@@ -441,14 +429,10 @@ class _DeferredBand:
         span = self.held.admit(batch, any(self.pos <= last < self.pos + B for _y0, _y1, last in self.groups))
         if self.out is None:
             self.out = torch.empty(self.out_shape, device=dev, dtype=torch.float32)
-        with N.on_device(dev):
-            # one C call: take the batch, launch the groups it completes, pack every outgoing rectangle whose rows are now written
-            rc = N.load().ptb_band_plan_submit_rank(self.handle, self.pos, B, batch.data_ptr(), per_tile, B * per_tile, N.DTYPE_CODES[batch.dtype],
-                                                    n_views, varr, reduction, self.out.data_ptr(), self.norm.data_ptr(), self.weight.data_ptr(),
-                                                    self.n_sends, self.rects.ctypes.data_as(N._i64p), self.send_ptrs, self.packed,
-                                                    self.event_p, ctypes.byref(self.all_packed),
-                                                    N.stream_ptr(dev))
-        N.bump()
+        # one C call: take the batch, launch the groups it completes, pack every outgoing rectangle whose rows are now written
+        rc = N.launch("ptb_band_plan_submit_rank", dev, self.handle, self.pos, B, batch.data_ptr(), per_tile, B * per_tile, N.DTYPE_CODES[batch.dtype],
+                      n_views, varr, reduction, self.out.data_ptr(), self.norm.data_ptr(), self.weight.data_ptr(), self.n_sends,
+                      self.rects.ctypes.data_as(N._i64p), self.send_ptrs, self.packed, self.event_p, ctypes.byref(self.all_packed), raw=True)
         if rc < 0:
             N.check(rc, "ShardedTileMerger.integrate_batch (deferred band)")
         self.held.keep(batch, span)
@@ -478,12 +462,9 @@ class _DeferredBand:
         if self.out is None:
             self.out = torch.empty(self.out_shape, device=dev, dtype=torch.float32)
         per_tile = self.channels * self.th * self.tw
-        with N.on_device(dev):
-            rc = N.load().ptb_band_plan_submit_rank(self.handle, pos, B, batch.data_ptr(), per_tile, B * per_tile, N.DTYPE_CODES[batch.dtype],
-                                                    n_views, varr, code, self.out.data_ptr(), self.norm.data_ptr(), self.weight.data_ptr(),
-                                                    self.n_sends, self.rects_p, self.send_ptrs, self.packed, self.event_p, self.all_packed_ref,
-                                                    N.stream_ptr(dev))
-        N.bump()
+        rc = N.launch("ptb_band_plan_submit_rank", dev, self.handle, pos, B, batch.data_ptr(), per_tile, B * per_tile, N.DTYPE_CODES[batch.dtype],
+                      n_views, varr, code, self.out.data_ptr(), self.norm.data_ptr(), self.weight.data_ptr(), self.n_sends, self.rects_p,
+                      self.send_ptrs, self.packed, self.event_p, self.all_packed_ref, raw=True)
         if rc < 0:
             N.check(rc, "ShardedTileMerger.integrate_batch (deferred band)")
         self.held.keep(batch, span)
@@ -1167,11 +1148,8 @@ class ShardedTileMerger:
             raise RuntimeError("ShardedTileMerger.merge(): not all of this rank's tiles were integrated")
         if d.n_recvs or d.n_ranges:
             # add the neighbours' partial sums, divide the rows that held partial sums: one C call (ptb_rect_add + ptb_merge_div_ex launches)
-            with N.on_device(self.device):
-                rc = N.load().ptb_band_plan_finish_rank(d.handle, d.out.data_ptr(), d.norm.data_ptr(), d.n_recvs, d.recv_rects_p,
-                                                        d.recv_ptrs if d.n_recvs else None, d.n_ranges, d.ranges_p, N.stream_ptr(self.device))
-            N.bump()
-            N.check(rc, "ShardedTileMerger.merge (deferred band)")
+            N.launch("ptb_band_plan_finish_rank", self.device, d.handle, d.out.data_ptr(), d.norm.data_ptr(), d.n_recvs, d.recv_rects_p,
+                     d.recv_ptrs if d.n_recvs else None, d.n_ranges, d.ranges_p, what="ShardedTileMerger.merge (deferred band)")
         d.held.clear()
         return d.out[:, o0 - d.top:o1 - d.top]
 
@@ -1304,14 +1282,9 @@ def ms_image_deaugment_strip(strips, source_heights, src_rows, out_rows, out_siz
     if out.numel() == 0:
         return out
     ptrs = (ctypes.c_void_p * len(ms))(*[m.data_ptr() for m in ms])
-    lib = N.load()
-    with N.on_device(first.device):
-        rc = lib.ptb_ms_deaug_reduce_strip(ptrs, N.int_array([int(h) for h in source_heights]), N.int_array([int(m.shape[3]) for m in ms]),
-                                           N.int_array([int(s0) for s0, _ in src_rows]), N.int_array([int(s1 - s0) for s0, s1 in src_rows]),
-                                           len(ms), out.data_ptr(), B * C, ho, wo, r0, r1 - r0, 1 if align_corners else 0, code,
-                                           N.stream_ptr(first.device))
-    N.bump()
-    N.check(rc, "ptb_ms_deaug_reduce_strip")
+    N.launch("ptb_ms_deaug_reduce_strip", first.device, ptrs, N.int_array([int(h) for h in source_heights]),
+             N.int_array([int(m.shape[3]) for m in ms]), N.int_array([int(s0) for s0, _ in src_rows]),
+             N.int_array([int(s1 - s0) for s0, s1 in src_rows]), len(ms), out.data_ptr(), B * C, ho, wo, r0, r1 - r0, 1 if align_corners else 0, code)
     return out
 
 
@@ -1349,11 +1322,8 @@ def ms_flips_image_deaugment_strip(strips, source_heights, src_rows, out_rows, o
     if out.numel() == 0:
         return out
     ptrs = (ctypes.c_void_p * len(ms))(*[m.data_ptr() for m in ms])
-    with N.on_device(first.device):
-        rc = N.load().ptb_ms_flip_deaug_reduce_strip(ptrs, N.int_array([int(h) for h in source_heights]), N.int_array([int(m.shape[3]) for m in ms]),
-                                                     N.int_array([int(s0) for s0, _ in src_rows]), N.int_array([int(s1 - s0) for s0, s1 in src_rows]),
-                                                     len(ms), V, N.int_array(list(views)), inner, out.data_ptr(), B * C, ho, wo, r0, r1 - r0,
-                                                     1 if align_corners else 0, outer, N.stream_ptr(first.device))
-    N.bump()
-    N.check(rc, "ptb_ms_flip_deaug_reduce_strip")
+    N.launch("ptb_ms_flip_deaug_reduce_strip", first.device, ptrs, N.int_array([int(h) for h in source_heights]),
+             N.int_array([int(m.shape[3]) for m in ms]), N.int_array([int(s0) for s0, _ in src_rows]),
+             N.int_array([int(s1 - s0) for s0, s1 in src_rows]), len(ms), V, N.int_array(list(views)), inner, out.data_ptr(), B * C, ho, wo, r0, r1 - r0,
+             1 if align_corners else 0, outer)
     return out

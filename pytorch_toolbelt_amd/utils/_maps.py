@@ -147,14 +147,10 @@ def scratch(nbytes, device):
 
 
 def workspace(plan, what, device, *plan_args):
-    """``(tensor, bytes)``: the workspace a ``ptb_*_plan`` entry with one int64 result asks for; call it inside ``N.on_device``"""
+    """``(tensor, bytes)``: the workspace a ``ptb_*_plan`` entry with one int64 result asks for"""
     nbytes = ctypes.c_int64()
     N.check(plan(*plan_args, ctypes.byref(nbytes)), what)
     return scratch(nbytes.value, device), nbytes.value
-
-
-def opt_ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def check_max_sweeps(what, max_sweeps, default):

@@ -131,16 +131,13 @@ def connected_components(labels, connectivity=8, background=0, dims=2):
     if not labels.is_cuda:
         cc, count = _label_host(labels.contiguous(), B, D, H, W, full, background)
         return torch.from_numpy(cc).reshape(labels.shape), torch.from_numpy(count).reshape(stack)
-    lib = N.load()
     x = labels.contiguous()
-    nbytes = _workspace(lib, what, dims, B, D, H, W, remove=False)
-    with N.on_device(dev):
-        cc = torch.empty(x.shape, dtype=torch.int32, device=dev)
-        count = torch.empty(stack, dtype=torch.int64, device=dev)
-        ws = M.scratch(nbytes, dev)
-        N.bump()
-        N.check(lib.ptb_cc_label(x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, connectivity, int(background is not None), background or 0,
-                                 cc.data_ptr(), count.data_ptr(), ws.data_ptr(), nbytes, N.stream_ptr(dev)), what)
+    nbytes = _workspace(N.load(), what, dims, B, D, H, W, remove=False)
+    cc = torch.empty(x.shape, dtype=torch.int32, device=dev)
+    count = torch.empty(stack, dtype=torch.int64, device=dev)
+    ws = M.scratch(nbytes, dev)
+    N.launch("ptb_cc_label", dev, x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, connectivity, int(background is not None), background or 0,
+             cc.data_ptr(), count.data_ptr(), ws.data_ptr(), nbytes, what=what)
     return cc, count
 
 
@@ -190,15 +187,11 @@ def component_stats(cc, count=None, values=None, max_components=None):
     if not cc.is_cuda:
         _stats_host(cc, values, n, out)
         return out
-    lib = N.load()
     x = cc.contiguous()
     v = values.contiguous() if values is not None else None
     D = x.shape[0] if dims == 3 else 1
-    with N.on_device(dev):
-        N.bump()
-        N.check(lib.ptb_cc_stats(x.data_ptr(), dims, D, x.shape[-2], x.shape[-1], n, v.data_ptr() if v is not None else None,
-                                 M.ELEM_BYTES[v.dtype] if v is not None else 0, out["area"].data_ptr(), out["bbox"].data_ptr(),
-                                 out["value"].data_ptr() if v is not None else None, N.stream_ptr(dev)), what)
+    N.launch("ptb_cc_stats", dev, x.data_ptr(), dims, D, x.shape[-2], x.shape[-1], n, N.ptr(v), M.ELEM_BYTES[v.dtype] if v is not None else 0,
+             out["area"].data_ptr(), out["bbox"].data_ptr(), N.ptr(out.get("value")), what=what)
     return out
 
 
@@ -252,12 +245,9 @@ def remove_small_components(labels, min_area, connectivity=8, background=0, dims
             res[b][small] = fill
         res = res.reshape(labels.shape)
     else:
-        lib = N.load()
-        nbytes = _workspace(lib, what, dims, B, D, H, W, remove=True)
-        with N.on_device(dev):
-            res = out if out is not None and out.is_contiguous() else torch.empty_like(x)
-            ws = M.scratch(nbytes, dev)
-            N.bump()
-            N.check(lib.ptb_cc_remove_small(x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, connectivity, int(bg is not None), bg or 0, min_area,
-                                            fill, res.data_ptr(), ws.data_ptr(), nbytes, N.stream_ptr(dev)), what)
+        nbytes = _workspace(N.load(), what, dims, B, D, H, W, remove=True)
+        res = out if out is not None and out.is_contiguous() else torch.empty_like(x)
+        ws = M.scratch(nbytes, dev)
+        N.launch("ptb_cc_remove_small", dev, x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, connectivity, int(bg is not None), bg or 0, min_area,
+                 fill, res.data_ptr(), ws.data_ptr(), nbytes, what=what)
     return M.finish_out(out, res)

@@ -97,15 +97,12 @@ def distance_transform(labels, background=0, foreground=None, dims=2, spacing=No
         res = torch.from_numpy(_host(labels.contiguous(), B, D, H, W, sites_equal, value if M.fits(value, labels.dtype) else None, sp, squared, signed))
         res = res.reshape(labels.shape)
     else:
-        lib = N.load()
         x = labels.contiguous()
-        with N.on_device(dev):
-            res = out if M.direct_out(out) else torch.empty(x.shape, dtype=dtype, device=dev)
-            ws, nbytes = M.workspace(lib.ptb_edt_plan, what, dev, dims, B, D, H, W, int(signed))
-            N.bump()
-            N.check(lib.ptb_edt(x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, M.SITES_EQUAL if sites_equal else M.SITES_NOT_EQUAL, value,
-                                (ctypes.c_double * 3)(*sp) if sp is not None else None, (_SQUARED if squared else 0) | (_SIGNED if signed else 0),
-                                res.data_ptr(), _OUT_I32 if dtype == torch.int32 else _OUT_F32, ws.data_ptr(), nbytes, N.stream_ptr(dev)), what)
+        res = out if M.direct_out(out) else torch.empty(x.shape, dtype=dtype, device=dev)
+        ws, nbytes = M.workspace(N.load().ptb_edt_plan, what, dev, dims, B, D, H, W, int(signed))
+        N.launch("ptb_edt", dev, x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, M.SITES_EQUAL if sites_equal else M.SITES_NOT_EQUAL, value,
+                 (ctypes.c_double * 3)(*sp) if sp is not None else None, (_SQUARED if squared else 0) | (_SIGNED if signed else 0),
+                 res.data_ptr(), _OUT_I32 if dtype == torch.int32 else _OUT_F32, ws.data_ptr(), nbytes, what=what)
     return M.finish_out(out, res)
 
 
@@ -160,33 +157,27 @@ def signed_maps_device(what, x, labels, dense, C, table, planes, prob, has_ignor
     """The signed maps ``[R, B, K, S]`` of the object maps one ``ptb_dloss_masks`` launch writes -- the truth plane, the thresholded
     prediction, or both (``planes``) -- by one ``ptb_edt`` call per chunk of entries.  ``x`` fp32 ``[B, C, S]`` (None for the truth plane
     alone); exactly one of ``labels`` int64 ``[B, S]`` / ``dense`` fp32 ``[B, C, S]``; ``C`` channels.  int32 with ``squared`` and unit spacing.  ``(maps, chunks)``."""
-    lib = N.load()
     K, _, host, dev_table = table
     src = labels if labels is not None else dense
     B, S = src.shape[0], src.shape[-1]
     R = (planes & 1) + (planes >> 1)
-    chunk, nbytes, _ = plan_maps(what, lib, dims, B, D, H, W, K, R, cap)
+    chunk, nbytes, _ = plan_maps(what, N.load(), dims, B, D, H, W, K, R, cap)
     E = R * B * K
     device = src.device
     as_int = squared and sp is None
-    with N.on_device(device):
-        masks = torch.empty(E * S, dtype=torch.uint8, device=device)
-        maps = torch.empty((R, B, K, S), dtype=torch.int32 if as_int else torch.float32, device=device)
-        ws = M.scratch(nbytes, device)
-        stream = N.stream_ptr(device)
-        N.bump()
-        N.check(lib.ptb_dloss_masks(x.data_ptr() if x is not None else None, labels.data_ptr() if labels is not None else None,
-                                    dense.data_ptr() if dense is not None else None, host, dev_table.data_ptr() if dev_table is not None else None,
-                                    planes, B, C, K, S, prob, int(has_ignore), ignore_label, ignore_value, masks.data_ptr(), stream), what)
-        spacing = (ctypes.c_double * 3)(*sp) if sp is not None else None
-        flags = _SIGNED | (_SQUARED if squared else 0)
-        chunks = 0
-        for e0 in range(0, E, chunk):
-            n = min(chunk, E - e0)
-            N.bump()
-            N.check(lib.ptb_edt(masks.data_ptr() + e0 * S, 1, dims, n, D, H, W, M.SITES_EQUAL, 0, spacing, flags, maps.data_ptr() + 4 * e0 * S,
-                                _OUT_I32 if as_int else _OUT_F32, ws.data_ptr(), nbytes, stream), what)
-            chunks += 1
+    masks = torch.empty(E * S, dtype=torch.uint8, device=device)
+    maps = torch.empty((R, B, K, S), dtype=torch.int32 if as_int else torch.float32, device=device)
+    ws = M.scratch(nbytes, device)
+    N.launch("ptb_dloss_masks", device, N.ptr(x), N.ptr(labels), N.ptr(dense), host, N.ptr(dev_table), planes, B, C, K, S, prob, int(has_ignore),
+             ignore_label, ignore_value, masks.data_ptr(), what=what)
+    spacing = (ctypes.c_double * 3)(*sp) if sp is not None else None
+    flags = _SIGNED | (_SQUARED if squared else 0)
+    chunks = 0
+    for e0 in range(0, E, chunk):
+        n = min(chunk, E - e0)
+        N.launch("ptb_edt", device, masks.data_ptr() + e0 * S, 1, dims, n, D, H, W, M.SITES_EQUAL, 0, spacing, flags, maps.data_ptr() + 4 * e0 * S,
+                 _OUT_I32 if as_int else _OUT_F32, ws.data_ptr(), nbytes, what=what)
+        chunks += 1
     return maps, chunks
 
 

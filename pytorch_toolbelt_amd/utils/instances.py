@@ -180,29 +180,25 @@ def _match_host(pred, truth, n_p, n_t, m, taus, K, pred_class, truth_class):
 # ---------------------------------------------------------------------------------------------------------------- device
 def _device(what, pred, truth, n_p, n_t, m, taus, K, pred_class, truth_class):
     """One native call: ``{name: tensor}`` for every output of the plan, views of one zeroed block"""
-    lib = N.load()
     dev = pred.device
     T, KK = len(taus), max(K, 1)
     positions = pred.numel()
     slots, ws_bytes, out_bytes = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
     offsets = (ctypes.c_int64 * len(_OUTPUTS))()
-    rc = lib.ptb_inst_plan(positions, n_p, n_t, m, T, K, ctypes.byref(slots), ctypes.byref(ws_bytes), offsets, ctypes.byref(out_bytes))
+    rc = N.load().ptb_inst_plan(positions, n_p, n_t, m, T, K, ctypes.byref(slots), ctypes.byref(ws_bytes), offsets, ctypes.byref(out_bytes))
     N.check(rc, what)
     p, t = pred.contiguous(), truth.contiguous()
-    with N.on_device(dev):
-        out = M.scratch(out_bytes.value, dev)
-        ws = M.scratch(ws_bytes.value, dev)
-        N.bump()
-        if T == 0:
-            rc = lib.ptb_inst_overlaps(p.data_ptr(), t.data_ptr(), positions, n_p, n_t, m, out.data_ptr(), out_bytes.value, ws.data_ptr(), ws_bytes.value,
-                                       N.stream_ptr(dev))
-        else:
-            pc = pred_class.contiguous() if K else None
-            tc = truth_class.contiguous() if K else None
-            rc = lib.ptb_inst_match(p.data_ptr(), t.data_ptr(), positions, n_p, n_t, m, (ctypes.c_double * T)(*taus), T,
-                                    pc.data_ptr() if K else None, M.ELEM_BYTES[pc.dtype] if K else 0, tc.data_ptr() if K else None,
-                                    M.ELEM_BYTES[tc.dtype] if K else 0, K, out.data_ptr(), out_bytes.value, ws.data_ptr(), ws_bytes.value, N.stream_ptr(dev))
-        N.check(rc, what)
+    out = M.scratch(out_bytes.value, dev)
+    ws = M.scratch(ws_bytes.value, dev)
+    if T == 0:
+        N.launch("ptb_inst_overlaps", dev, p.data_ptr(), t.data_ptr(), positions, n_p, n_t, m, out.data_ptr(), out_bytes.value, ws.data_ptr(),
+                 ws_bytes.value, what=what)
+    else:
+        pc = pred_class.contiguous() if K else None
+        tc = truth_class.contiguous() if K else None
+        N.launch("ptb_inst_match", dev, p.data_ptr(), t.data_ptr(), positions, n_p, n_t, m, (ctypes.c_double * T)(*taus), T,
+                 N.ptr(pc), M.ELEM_BYTES[pc.dtype] if K else 0, N.ptr(tc), M.ELEM_BYTES[tc.dtype] if K else 0, K, out.data_ptr(), out_bytes.value,
+                 ws.data_ptr(), ws_bytes.value, what=what)
     rows = m if T == 0 else 0
     shapes = {"num_pairs": (), "pred_area": (n_p,), "truth_area": (n_t,), "pairs": (rows, 2), "intersection": (rows,), "pred_match": (n_p,) if T else (0,),
               "truth_match": (n_t,) if T else (0,), "pred_iou": (n_p,) if T else (0,), "truth_iou": (n_t,) if T else (0,)}

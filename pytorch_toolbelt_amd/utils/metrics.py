@@ -124,14 +124,10 @@ def confusion_matrix(pred, target, num_classes, ignore_index=None, per_sample=Fa
 
 
 def _labels_native(pred, target, B, n, K, ignore_index, out):
-    lib = N.load()
     dev = pred.device
-    with N.on_device(dev):
-        invalid = torch.zeros(1, dtype=torch.int64, device=dev)
-        N.bump()
-        N.check(lib.ptb_confusion_labels(pred.data_ptr(), M.ELEM_BYTES[pred.dtype], target.data_ptr(), M.ELEM_BYTES[target.dtype], B, n, K,
-                                         int(ignore_index is not None), ignore_index or 0, out.data_ptr(), invalid.data_ptr(), N.stream_ptr(dev)),
-                "confusion_matrix")
+    invalid = torch.zeros(1, dtype=torch.int64, device=dev)
+    N.launch("ptb_confusion_labels", dev, pred.data_ptr(), M.ELEM_BYTES[pred.dtype], target.data_ptr(), M.ELEM_BYTES[target.dtype], B, n, K,
+             int(ignore_index is not None), ignore_index or 0, out.data_ptr(), invalid.data_ptr(), what="confusion_matrix")
     return invalid
 
 
@@ -176,15 +172,11 @@ def confusion_matrix_from_logits(logits, target, ignore_index=None, threshold=0.
     if Nb == 0 or S == 0:
         return out
     if logits.is_cuda:
-        lib = N.load()
         dev = logits.device
         dense, tgt = logits.contiguous(), target.contiguous()
-        with N.on_device(dev):
-            invalid = torch.zeros(1, dtype=torch.int64, device=dev)
-            N.bump()
-            N.check(lib.ptb_confusion_logits(dense.data_ptr(), N.DTYPE_CODES[dense.dtype], Nb, C, S, threshold, tgt.data_ptr(), M.ELEM_BYTES[tgt.dtype],
-                                             int(bool(per_sample)), int(ignore_index is not None), ignore_index or 0, out.data_ptr(), invalid.data_ptr(),
-                                             N.stream_ptr(dev)), what)
+        invalid = torch.zeros(1, dtype=torch.int64, device=dev)
+        N.launch("ptb_confusion_logits", dev, dense.data_ptr(), N.DTYPE_CODES[dense.dtype], Nb, C, S, threshold, tgt.data_ptr(), M.ELEM_BYTES[tgt.dtype],
+                 int(bool(per_sample)), int(ignore_index is not None), ignore_index or 0, out.data_ptr(), invalid.data_ptr(), what=what)
         if strict:
             _raise_invalid(what, int(invalid.item()), K)
     else:

@@ -48,13 +48,10 @@ def _squared_form(sq, sp):
 
 # ---------------------------------------------------------------------------------------------------------------- native call
 def _native(what, x, dims, B, D, H, W, sites_equal, value, sp, flags, index=None, squared=None, gather=None, mask=None, max_sq=0.0):
-    lib = N.load()
-    ws, nbytes = M.workspace(lib.ptb_nearest_plan, what, x.device, dims, B, D, H, W, flags)
-    ptr = M.opt_ptr
-    N.bump()
-    N.check(lib.ptb_nearest(x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, M.SITES_EQUAL if sites_equal else M.SITES_NOT_EQUAL, value,
-                            (ctypes.c_double * 3)(*sp) if sp is not None else None, flags, ptr(index), ptr(squared), ptr(gather), ptr(mask), max_sq,
-                            ws.data_ptr(), nbytes, N.stream_ptr(x.device)), what)
+    ws, nbytes = M.workspace(N.load().ptb_nearest_plan, what, x.device, dims, B, D, H, W, flags)
+    N.launch("ptb_nearest", x.device, x.data_ptr(), M.ELEM_BYTES[x.dtype], dims, B, D, H, W, M.SITES_EQUAL if sites_equal else M.SITES_NOT_EQUAL, value,
+             (ctypes.c_double * 3)(*sp) if sp is not None else None, flags, N.ptr(index), N.ptr(squared), N.ptr(gather), N.ptr(mask), max_sq,
+             ws.data_ptr(), nbytes, what=what)
 
 
 # ---------------------------------------------------------------------------------------------------------------- public
@@ -103,10 +100,9 @@ def nearest_site(labels, background=0, foreground=None, dims=2, spacing=None, re
         sq = torch.from_numpy(_squared_form(d, sp)).reshape(labels.shape)
     else:
         x = labels.contiguous()
-        with N.on_device(dev):
-            index = out if M.direct_out(out) else torch.empty(x.shape, dtype=torch.int32, device=dev)
-            sq = torch.empty(x.shape, dtype=sq_dtype, device=dev) if return_distance else None
-            _native(what, x, dims, B, D, H, W, sites_equal, value, sp, _INDEX | (_SQUARED if return_distance else 0), index=index, squared=sq)
+        index = out if M.direct_out(out) else torch.empty(x.shape, dtype=torch.int32, device=dev)
+        sq = torch.empty(x.shape, dtype=sq_dtype, device=dev) if return_distance else None
+        _native(what, x, dims, B, D, H, W, sites_equal, value, sp, _INDEX | (_SQUARED if return_distance else 0), index=index, squared=sq)
     index = M.finish_out(out, index)
     return (index, sq) if return_distance else index
 
@@ -173,7 +169,6 @@ def expand_labels(markers, distance=None, mask=None, background=0, dims=2, spaci
     else:
         x = markers.contiguous()
         m = mask.contiguous() if mask is not None else None
-        with N.on_device(dev):
-            res = out if M.direct_out(out, x) else torch.empty(x.shape, dtype=x.dtype, device=dev)
-            _native(what, x, dims, B, D, H, W, False, background, sp, _GATHER | (_MAX_SQ if distance is not None else 0), gather=res, mask=m, max_sq=max_sq)
+        res = out if M.direct_out(out, x) else torch.empty(x.shape, dtype=x.dtype, device=dev)
+        _native(what, x, dims, B, D, H, W, False, background, sp, _GATHER | (_MAX_SQ if distance is not None else 0), gather=res, mask=m, max_sq=max_sq)
     return M.finish_out(out, res)

@@ -173,19 +173,16 @@ def _run(what, op, erosion, seed, mask, name, h, connectivity, domain, dims, out
         m = mask.contiguous()
         s = seed.contiguous() if seed is not None else None
         k = domain.contiguous() if domain is not None else None
-        with N.on_device(dev):
-            res = out if M.direct_out(out, m, s, k) else torch.empty(m.shape, dtype=out_dtype, device=dev)
-            lib = N.load()
-            ws, nbytes = M.workspace(lib.ptb_reconstruct_plan, what, dev, dims, B, D, H, W, op)
-            ptr = M.opt_ptr                                             # (a bool tensor's bytes are the uint8 the kernels read)
-            took = (ctypes.c_int * 2)(-1, -1)
-            N.bump()
-            rc = lib.ptb_reconstruct(ptr(s), ptr(m), _CODES[m.dtype], ptr(k), dims, B, D, H, W, connectivity, op, int(erosion), h if op == _H_EXTREMA else 0.0,
-                                     _TOP[m.dtype] if op == _FILL else math.inf, max_sweeps, ptr(res), took, ws.data_ptr(), nbytes, N.stream_ptr(dev))
-            if rc == N.PTB_ENOTCONVERGED:
-                M.raise_not_converged(what, _PHASES[op], took, max_sweeps)
-            N.check(rc, what)
-            sweeps = (int(took[0]), max(int(took[1]), 0))
+        res = out if M.direct_out(out, m, s, k) else torch.empty(m.shape, dtype=out_dtype, device=dev)
+        ws, nbytes = M.workspace(N.load().ptb_reconstruct_plan, what, dev, dims, B, D, H, W, op)
+        took = (ctypes.c_int * 2)(-1, -1)
+        rc = N.launch("ptb_reconstruct", dev, N.ptr(s), m.data_ptr(), _CODES[m.dtype], N.ptr(k), dims, B, D, H, W, connectivity, op, int(erosion),
+                      h if op == _H_EXTREMA else 0.0, _TOP[m.dtype] if op == _FILL else math.inf, max_sweeps,
+                      res.data_ptr(), took, ws.data_ptr(), nbytes, raw=True)    # (a bool tensor's bytes are the uint8 the kernels read)
+        if rc == N.PTB_ENOTCONVERGED:
+            M.raise_not_converged(what, _PHASES[op], took, max_sweeps)
+        N.check(rc, what)
+        sweeps = (int(took[0]), max(int(took[1]), 0))
     res = M.finish_out(out, res)
     return (res, sweeps) if return_sweeps else res
 

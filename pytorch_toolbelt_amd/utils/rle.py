@@ -147,24 +147,20 @@ def _encode_native(stack, label_list):
     B, H, W = stack.shape
     K = 0 if label_list is None else len(label_list)
     E = B * max(K, 1)
-    lib = N.load()
-    nbytes = lib.ptb_rle_workspace_bytes(B, K, H, W)
+    nbytes = N.load().ptb_rle_workspace_bytes(B, K, H, W)
     if nbytes < 0:
         N.check(int(nbytes), "rle_encode_device")
     dev = stack.device
     eb = M.ELEM_BYTES[stack.dtype]
     lab = N.i64_array(label_list) if K else None
-    with N.on_device(dev):
-        ws = M.scratch(nbytes, dev)
-        stream = N.stream_ptr(dev)
-        N.bump()
-        N.check(lib.ptb_rle_count(stack.data_ptr(), eb, B, H, W, lab, K, ws.data_ptr(), nbytes, stream), "rle_encode_device (count)")
-        enc = ws[:8 * (E + 1)].view(torch.int64).cpu().tolist()          # the one D2H read: where every encoding starts, and the total
-        total = enc[E]
-        out = torch.empty(total, dtype=torch.int64, device=dev)
-        if total:
-            N.bump()
-            N.check(lib.ptb_rle_write(stack.data_ptr(), eb, B, H, W, lab, K, ws.data_ptr(), nbytes, out.data_ptr(), total, stream), "rle_encode_device (write)")
+    ws = M.scratch(nbytes, dev)
+    N.launch("ptb_rle_count", dev, stack.data_ptr(), eb, B, H, W, lab, K, ws.data_ptr(), nbytes, what="rle_encode_device (count)")
+    enc = ws[:8 * (E + 1)].view(torch.int64).cpu().tolist()          # the one D2H read: where every encoding starts, and the total
+    total = enc[E]
+    out = torch.empty(total, dtype=torch.int64, device=dev)
+    if total:
+        N.launch("ptb_rle_write", dev, stack.data_ptr(), eb, B, H, W, lab, K, ws.data_ptr(), nbytes, out.data_ptr(), total,
+                 what="rle_encode_device (write)")
     Kt = max(K, 1)
     views = out.split([enc[e + 1] - enc[e] for e in range(E)])         # (one call: thousands of slice expressions cost milliseconds)
     return [list(views[b * Kt:(b + 1) * Kt]) for b in range(B)]
@@ -207,13 +203,9 @@ def rle_decode_device(runs, shape, dtype=torch.uint8, device=None):
     mask = torch.empty((H, W), dtype=torch.uint8, device=device)
     if n == 0:
         return mask.to(dtype)
-    lib = N.load()
-    nbytes = lib.ptb_rle_decode_workspace_bytes(H, W)
+    nbytes = N.load().ptb_rle_decode_workspace_bytes(H, W)
     if nbytes < 0:
         N.check(int(nbytes), "rle_decode_device")
-    with N.on_device(device):
-        ws = M.scratch(nbytes, device)
-        N.bump()
-        N.check(lib.ptb_rle_decode(dev_runs.data_ptr(), dev_runs.numel() // 2, H, W, mask.data_ptr(), ws.data_ptr(), nbytes, N.stream_ptr(device)),
-                "rle_decode_device")
+    ws = M.scratch(nbytes, device)
+    N.launch("ptb_rle_decode", device, dev_runs.data_ptr(), dev_runs.numel() // 2, H, W, mask.data_ptr(), ws.data_ptr(), nbytes, what="rle_decode_device")
     return mask.view(torch.bool) if dtype == torch.bool else mask

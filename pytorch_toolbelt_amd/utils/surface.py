@@ -238,19 +238,15 @@ def surface_metrics(pred, truth, labels=None, *, background=0, dims=2, spacing=N
     elif not pred.is_cuda:
         res = _host(pred.contiguous(), truth.contiguous(), B, D, H, W, dims, full, values, rule, sp, pct, tols)
     else:
-        lib = N.load()
-        _, nbytes, _ = _plan(what, lib, dims, B, D, H, W, K, cap)
+        _, nbytes, _ = _plan(what, N.load(), dims, B, D, H, W, K, cap)
         p, t = pred.contiguous(), truth.contiguous()
-        with N.on_device(dev):
-            res = {"surface_count": torch.empty((B, K, 2), dtype=torch.int64, device=dev), "surface_dice": torch.empty((B, K, T), dtype=torch.float32, device=dev)}
-            res.update({key: torch.empty((B, K, 2), dtype=torch.float32, device=dev) for key in _KEYS2})
-            res.update({key: torch.empty((B, K), dtype=torch.float32, device=dev) for key in _KEYS1})
-            ws = M.scratch(nbytes, dev)
-            N.bump()
-            N.check(lib.ptb_surface_metrics(p.data_ptr(), M.ELEM_BYTES[p.dtype], t.data_ptr(), M.ELEM_BYTES[t.dtype], dims, B, D, H, W, N.i64_array(values), K, rule,
-                                            connectivity, (ctypes.c_double * 3)(*sp) if sp is not None else None, pct, (ctypes.c_double * T)(*tols), T,
-                                            res["surface_count"].data_ptr(), res["directed_hausdorff"].data_ptr(), res["hausdorff"].data_ptr(),
-                                            res["directed_percentile"].data_ptr(), res["hausdorff_percentile"].data_ptr(),
-                                            res["mean_surface_distance"].data_ptr(), res["assd"].data_ptr(), res["surface_dice"].data_ptr(),
-                                            ws.data_ptr(), nbytes, N.stream_ptr(dev)), what)
+        res = {"surface_count": torch.empty((B, K, 2), dtype=torch.int64, device=dev), "surface_dice": torch.empty((B, K, T), dtype=torch.float32, device=dev)}
+        res.update({key: torch.empty((B, K, 2), dtype=torch.float32, device=dev) for key in _KEYS2})
+        res.update({key: torch.empty((B, K), dtype=torch.float32, device=dev) for key in _KEYS1})
+        ws = M.scratch(nbytes, dev)
+        N.launch("ptb_surface_metrics", dev, p.data_ptr(), M.ELEM_BYTES[p.dtype], t.data_ptr(), M.ELEM_BYTES[t.dtype], dims, B, D, H, W,
+                 N.i64_array(values), K, rule, connectivity, (ctypes.c_double * 3)(*sp) if sp is not None else None, pct, (ctypes.c_double * T)(*tols), T,
+                 res["surface_count"].data_ptr(), res["directed_hausdorff"].data_ptr(), res["hausdorff"].data_ptr(),
+                 res["directed_percentile"].data_ptr(), res["hausdorff_percentile"].data_ptr(),
+                 res["mean_surface_distance"].data_ptr(), res["assd"].data_ptr(), res["surface_dice"].data_ptr(), ws.data_ptr(), nbytes, what=what)
     return {key: v.reshape(stack + tuple(v.shape[1:])) for key, v in res.items()}

@@ -165,21 +165,18 @@ def watershed(height, markers, mask=None, connectivity=8, background=0, dims=2, 
         x, h = markers.contiguous(), height.contiguous()
         m = mask.contiguous() if mask is not None else None
         flags = (_COST if return_cost else 0) | (_SEED if return_seed else 0)
-        with N.on_device(dev):
-            res = out if M.direct_out(out, x) else torch.empty(x.shape, dtype=x.dtype, device=dev)
-            cost = torch.empty(x.shape, dtype=torch.float32, device=dev) if return_cost else None
-            seed = torch.empty(x.shape, dtype=torch.int32, device=dev) if return_seed else None
-            lib = N.load()
-            ws, nbytes = M.workspace(lib.ptb_watershed_plan, what, dev, dims, B, D, H, W, flags)
-            ptr = M.opt_ptr
-            took = (ctypes.c_int * 2)(-1, -1)
-            N.bump()
-            rc = lib.ptb_watershed(h.data_ptr(), M.VALUE_CODES[h.dtype], x.data_ptr(), M.ELEM_BYTES[x.dtype], ptr(m), dims, B, D, H, W, connectivity, background, fill,
-                                   flags, max_sweeps, res.data_ptr(), ptr(cost), ptr(seed), took, ws.data_ptr(), nbytes, N.stream_ptr(dev))
-            if rc == N.PTB_ENOTCONVERGED:
-                M.raise_not_converged(what, _PHASES, took, max_sweeps)
-            N.check(rc, what)
-            sweeps = (int(took[0]), int(took[1]))
+        res = out if M.direct_out(out, x) else torch.empty(x.shape, dtype=x.dtype, device=dev)
+        cost = torch.empty(x.shape, dtype=torch.float32, device=dev) if return_cost else None
+        seed = torch.empty(x.shape, dtype=torch.int32, device=dev) if return_seed else None
+        ws, nbytes = M.workspace(N.load().ptb_watershed_plan, what, dev, dims, B, D, H, W, flags)
+        took = (ctypes.c_int * 2)(-1, -1)
+        rc = N.launch("ptb_watershed", dev, h.data_ptr(), M.VALUE_CODES[h.dtype], x.data_ptr(), M.ELEM_BYTES[x.dtype], N.ptr(m), dims, B, D, H, W,
+                      connectivity, background, fill, flags, max_sweeps, res.data_ptr(), N.ptr(cost), N.ptr(seed), took, ws.data_ptr(), nbytes,
+                      raw=True)
+        if rc == N.PTB_ENOTCONVERGED:
+            M.raise_not_converged(what, _PHASES, took, max_sweeps)
+        N.check(rc, what)
+        sweeps = (int(took[0]), int(took[1]))
     res = M.finish_out(out, res)
     extra = ((cost,) if return_cost else ()) + ((seed,) if return_seed else ()) + ((sweeps,) if return_sweeps else ())
     return (res,) + extra if extra else res
