@@ -1036,6 +1036,60 @@ int ptb_reconstruct(const void* seed, const void* mask, int dtype, const void* d
                     int connectivity, int op, int erosion, float h, float top, int max_sweeps, void* out, int32_t* sweeps_out, void* workspace,
                     int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Skeletons by parallel thinning, centreline Dice (no counterpart in the reference) -------------------------------
+ * THE NEIGHBOURS of a position P1 = (y, x): P2 (y-1, x), P3 (y-1, x+1), P4 (y, x+1), P5 (y+1, x+1), P6 (y+1, x), P7 (y+1, x-1),
+ * P8 (y, x-1), P9 (y-1, x-1); positions outside the entry are background.  One ITERATION is sub-iteration 0, then sub-iteration 1, each
+ * synchronous: every decision reads the state from before that sub-iteration.  An object position is deleted in sub-iteration k iff
+ *   PTB_THIN_ZHANG (Zhang & Suen 1984)  B = the number of set neighbours, A = the number of i with P_i = 0 and P_i+1 = 1 in the cycle
+ *       P2, P3, ..., P9, P2:  2 <= B <= 6 and A == 1 and  k = 0: P2 P4 P6 == 0 and P4 P6 P8 == 0;  k = 1: P2 P4 P8 == 0 and P2 P6 P8 == 0.
+ *   PTB_THIN_GUO_HALL (Guo & Hall 1989, as in OpenCV's ximgproc.thinning)
+ *       C = (!P2 & (P3|P4)) + (!P4 & (P5|P6)) + (!P6 & (P7|P8)) + (!P8 & (P9|P2)),  N1 = (P9|P2) + (P3|P4) + (P5|P6) + (P7|P8),
+ *       N2 = (P2|P3) + (P4|P5) + (P6|P7) + (P8|P9),  N = min(N1, N2),  m = (P6|P7|!P9) & P8 for k = 0, (P2|P3|!P5) & P4 for k = 1:
+ *       C == 1 and 2 <= N <= 3 and m == 0.
+ * THE SKELETON is the state after the first iteration that deletes nothing; with max_iterations = n >= 0 the state after at most n
+ * iterations (0: the object itself).  THE ITERATION COUNT is the number of iterations that deleted something.
+ *   ptb_thin_rule   HOST ONLY, no stream, no GPU: the rule on words, as the kernels evaluate it.  Bit i of centre and of nbr[0 .. 8) (the
+ *                   words of P2 .. P9) is one position; returns the positions of centre that sub-iteration sub (0 | 1) deletes; 0 for an
+ *                   unknown method or sub.
+ *   ptb_thin_steps  HOST ONLY: the sub-iterations one launch of the thinning kernel runs (even, <= 32).
+ *   ptb_skeleton    labels [B, H, W] contiguous of elem_bytes (1 = bool / uint8, 2 / 4 / 8 signed), read where it lies.  The object:
+ *                   PTB_THIN_NOT_EQUAL: labels != value, PTB_THIN_EQUAL: labels == value; a value the element type cannot hold occurs
+ *                   nowhere.  B * H * W <= 2^31 - 2 (PTB_EUNSUPPORTED above).  out [B, H, W] bytes, 0 | 1, 16-byte aligned; it must not
+ *                   overlap labels.  max_iterations < 0: run to stability under a guard of H + W iterations, beyond which the call returns
+ *                   PTB_ENOTCONVERGED with out unwritten (a max_iterations >= H + W counts as < 0).  took: HOST, two ints or NULL: the
+ *                   iteration count of the call (of the entry that took longest) and the launches of the thinning kernel that ran.
+ *   ptb_centerline_dice   pred, truth [B, H, W] label maps as above, each with its own elem_bytes.  Object k: with PTB_THIN_EQUAL the
+ *                   positions that hold class_values[k] (HOST, 1 <= K <= 32 values), with PTB_THIN_NOT_EQUAL (K == 1) those that do not hold
+ *                   class_values[0].  With S the skeleton and V the mask of object k in each map, all DEVICE, obj = b * K + k:
+ *                     counts [obj][4] int64 = |S_P & V_T|, |S_P|, |S_T & V_P|, |S_T|  (exact; zeroed by the call)
+ *                     tprec = counts[0] / counts[1], tsens = counts[2] / counts[3], cldice = 2 tprec tsens / (tprec + tsens): float32 [obj],
+ *                     evaluated in float64 in that order and rounded once.  An empty skeleton gives nan in its own ratio; cldice is nan
+ *                     when both are empty, 0 when exactly one is or when tprec + tsens == 0.
+ *                   2 * K * B * H * W <= 2^31 - 2 (PTB_EUNSUPPORTED above); thinning runs to stability under the guard.
+ * STATE: bit planes, 32 positions a word, WW = ceil(W / 32) words a row, bits at columns >= W zero; two planes for ping-pong (a launch
+ * reads one and writes the other) and, for ptb_centerline_dice, a third with the untouched masks, over 2 * K * B entries thinned in the
+ * same launches.  Launches on `stream`: a pack kernel (per side), LAUNCHES of the thinning kernel -- a workgroup holds a 64 x 64 tile
+ * with a halo of ptb_thin_steps() rows and one word in LDS and runs that many sub-iterations there; a tile runs iff it or one of its 8
+ * neighbours changed in the launch before --, then an unpack kernel, or a count kernel (popcounts folded per wave, then 64-bit integer
+ * atomic adds: exact and order-free) and a one-workgroup finish kernel.  No workgroup waits for another one, every loop is bounded.
+ * Launches go eight at a time; after each batch ONE 4-BYTE WORD IS READ BACK on `stream` and the stream is synchronised, and one more
+ * word (the iteration count) at the end -- so the calls CANNOT BE CAPTURED into a graph.  The result is a function of the inputs alone.
+ * workspace: DEVICE, 16-byte aligned, the plan entry's bytes: 4 * H * WW per plane and entry (2 planes; clDice: 3, over 2 * K * B
+ * entries), per tile 12, and 16 more; each array rounded up to 16 bytes. */
+#define PTB_THIN_ZHANG 0
+#define PTB_THIN_GUO_HALL 1
+#define PTB_THIN_EQUAL 0
+#define PTB_THIN_NOT_EQUAL 1
+uint32_t ptb_thin_rule(int method, int sub, const uint32_t* nbr, uint32_t centre);
+int ptb_thin_steps(void);
+int ptb_skeleton_plan(int64_t B, int64_t H, int64_t W, int64_t* workspace_bytes);
+int ptb_skeleton(const void* labels, int elem_bytes, int64_t B, int64_t H, int64_t W, int object_rule, int64_t value, int method,
+                 int64_t max_iterations, void* out, int32_t* took, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+int ptb_centerline_dice_plan(int64_t B, int64_t H, int64_t W, int K, int64_t* workspace_bytes);
+int ptb_centerline_dice(const void* pred, int pred_elem_bytes, const void* truth, int truth_elem_bytes, int64_t B, int64_t H, int64_t W,
+                        const int64_t* class_values, int K, int object_rule, int method, int64_t* counts, float* cldice, float* tprec,
+                        float* tsens, int32_t* took, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+
 /* ---- Surface metrics of two label maps (no counterpart in the reference) ---------------------------------------------
  * pred, truth = [B, D, H, W] contiguous label maps (dims = 2: D == 1), each with its own elem_bytes (1 = bool / uint8, 2 / 4 / 8
  * signed), read where they lie.  Object k of an entry is, with PTB_SURFACE_CLASSES, the positions that hold class_values[k] (HOST, K

@@ -199,6 +199,12 @@ SIGNATURES = {
     "ptb_reconstruct_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _i64p]),
     "ptb_reconstruct": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_f, _c_f, _c_int, _vp, _ip, _vp, _c_i64,
                                  _vp]),
+    "ptb_thin_rule": (ctypes.c_uint32, [_c_int, _c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]),
+    "ptb_thin_steps": (_c_int, []),
+    "ptb_skeleton_plan": (_c_int, [_c_i64, _c_i64, _c_i64, _i64p]),
+    "ptb_skeleton": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_int, _c_i64, _vp, _ip, _vp, _c_i64, _vp]),
+    "ptb_centerline_dice_plan": (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _i64p]),
+    "ptb_centerline_dice": (_c_int, [_vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _ip, _vp, _c_i64, _vp]),
     "ptb_surface_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _ip, _i64p, _i64p, _ip]),
     "ptb_surface_metrics": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, ctypes.POINTER(_c_d), _c_d,
                                      ctypes.POINTER(_c_d), _c_int] + [_vp] * 8 + [_vp, _c_i64, _vp]),

@@ -1,5 +1,5 @@
 """What the label-map tools of this package share on the host: the twin of ``csrc/ptb_common.h``.  ``components``, ``distance``, ``nearest``,
-``watershed``, ``reconstruct``, ``surface`` and ``instances`` (and ``rle``, ``metrics``, ``losses/distance_losses.py``) take their dtype tables, their
+``watershed``, ``reconstruct``, ``skeleton``, ``surface`` and ``instances`` (and ``rle``, ``metrics``, ``losses/distance_losses.py``) take their dtype tables, their
 argument checks, the handling of ``out=``, the workspace of a native call and the host form of the distance passes from here and from no
 sibling.  Private: nothing here is exported from ``utils`` or part of the interface.
 
