@@ -231,7 +231,10 @@ int ptb_sums_finalize(const double* slot_sums, int nslots, int n, double* out, c
  *   b * tile_stride elements, view v of a tile view_stride elements further (chunk-major [V*B, C, th, tw] model output:
  *   tile_stride = C*th*tw, view_stride = B*C*th*tw) -- and launches every group whose last tile is now in: the group's rows of
  *   merged [C, H, W] = sum_t w * reduce_v(view_v^-1(tile_t)) / norm_full (integration order per pixel, fp32, no contraction:
- *   bit-identical to the incremental entry points).  The batches must stay alive and unmodified until their last group was
+ *   bit-identical to the incremental entry points).  The launches of ptb_band_plan_submit / _submit_next / _submit_act do not READ
+ *   norm_full: they sum the window values of a pixel's covering tiles in integration order beside the blend, which is how
+ *   ptb_norm_accumulate builds that map (same bits; a pixel no tile covers is 0 / 0).  The argument stays part of the call and of the
+ *   image's configuration (non-NULL, 16-byte aligned, the same for every batch of an image); ptb_band_plan_submit_rank still reads it.  The batches must stay alive and unmodified until their last group was
  *   launched.  Returns the number of launches (>= 0); PTB_EUNSUPPORTED when `pos` is not the next planned tile or the
  *   configuration (dtype, views, reduction, merged / norm_full / weight pointers) differs from the image's first batch -- nothing
  *   is launched then and the caller integrates incrementally.
@@ -265,6 +268,8 @@ void ptb_band_plan_destroy(ptb_band_plan* plan);
  * rows) whose rows are complete into send_bufs[k] (`packed` [n_sends] in/out, zero at the start of an image) and, when the last one
  * has just been packed, records ready_event (a hipEvent_t; NULL only when n_sends == 0: a communication stream that did not wait
  * for it would send rectangles the pack kernels have not written yet -> PTB_EINVAL) on the stream.  Returns the band launches issued (>= 0).
+ * Its launches divide the rows inside [final_lo, final_hi) by norm_full as handed in (a rank may issue its tiles in another order than the
+ * image's, in which its map was summed); an image is taken through ptb_band_plan_submit or through this call, not both.
  * ptb_band_plan_finish_rank: the end of a rank's image -- adds the n_recvs received rectangles of partial sums ({r0, r1, c0, c1} in
  * the plan's rows, packed [C][rows][cols] buffers) to `merged` and divides the n_ranges row ranges {r0, r1} that held partial sums by
  * `norm` [H][W] in place (launches only). */

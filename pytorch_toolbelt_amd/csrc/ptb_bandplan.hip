@@ -52,8 +52,16 @@ __global__ __launch_bounds__(16 * CH) void band_plan_kernel(const ViewArgs a, co
     const int q = tid & 15, r = tid >> 4;
     const bool act = (r < ch) && (4 * q < cw);
     const long long pix = (long long)(it->ay + r) * a.dst_row_stride + it->ax + 4 * q;
-    float4 nfull = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (act && !partial) nfull = *reinterpret_cast<const float4*>(a.norm_full + pix);
+    // The normaliser is summed HERE, from the window values the blend multiplies by anyway: ptb_norm_accumulate builds its map by the same
+    // sequence (the covering tiles in integration order, __fadd_rn from zero), so the bits are the map's, and the map -- 105 MB per
+    // 5000 x 5000 image, re-read by every channel's workgroup on another XCD -- is not read.  A final item is covered by the plan's own
+    // tiles only, so its sum is complete; a partial item stores undivided sums and band_finish_kernel divides them by the global map.
+    // a.norm_map (ptb_band_plan_submit_rank): a rank of a sharded merge may issue its tiles in another order than the image's (the ones
+    // its neighbours wait for first), and its map was summed in the image's order -- a sum in the plan's order would end on other bits.
+    // Such launches load the map as before, into the registers the sum would use (wave-uniform choice, no register more).
+    const bool norm_map = a.norm_map != 0;
+    float4 nsum = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (norm_map && act && !partial) nsum = *reinterpret_cast<const float4*>(a.norm_full + pix);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     const int nt = it->ntiles;
     // ALL (round 6): one or two row-preserving views -- the plain loop without TTA (`integrate_batch(pred, crops)`, tiles.py:321-339), the
@@ -91,6 +99,15 @@ __global__ __launch_bounds__(16 * CH) void band_plan_kernel(const ViewArgs a, co
             }
         };
         request(c);
+#pragma unroll
+        for (int e = 0; e < MAX_COVER; ++e) {
+            if (e < nt && !norm_map) {
+                nsum.x = __fadd_rn(nsum.x, wv[e].x);
+                nsum.y = __fadd_rn(nsum.y, wv[e].y);
+                nsum.z = __fadd_rn(nsum.z, wv[e].z);
+                nsum.w = __fadd_rn(nsum.w, wv[e].w);
+            }
+        }
         for (; c < c_end; ++c) {
             acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -110,7 +127,7 @@ __global__ __launch_bounds__(16 * CH) void band_plan_kernel(const ViewArgs a, co
             if (act) {
                 float* o = a.merged + (long long)c * a.dst_chan_stride + pix;
                 if (partial) *reinterpret_cast<float4*>(o) = acc;
-                else out_store4(o, make_float4(__fdiv_rn(acc.x, nfull.x), __fdiv_rn(acc.y, nfull.y), __fdiv_rn(acc.z, nfull.z), __fdiv_rn(acc.w, nfull.w)));
+                else out_store4(o, make_float4(__fdiv_rn(acc.x, nsum.x), __fdiv_rn(acc.y, nsum.y), __fdiv_rn(acc.z, nsum.z), __fdiv_rn(acc.w, nsum.w)));
             }
         }
         return;
@@ -159,13 +176,19 @@ __global__ __launch_bounds__(16 * CH) void band_plan_kernel(const ViewArgs a, co
             acc.y = __fadd_rn(acc.y, __fmul_rn(val.y, w4.y));
             acc.z = __fadd_rn(acc.z, __fmul_rn(val.z, w4.z));
             acc.w = __fadd_rn(acc.w, __fmul_rn(val.w, w4.w));
+            if (!norm_map) {
+                nsum.x = __fadd_rn(nsum.x, w4.x);               // tiles.py:339: the normaliser's own sum, same order
+                nsum.y = __fadd_rn(nsum.y, w4.y);
+                nsum.z = __fadd_rn(nsum.z, w4.z);
+                nsum.w = __fadd_rn(nsum.w, w4.w);
+            }
         }
     }
     if (act) {
         float* o = a.merged + (long long)c * a.dst_chan_stride + pix;
         if (partial) *reinterpret_cast<float4*>(o) = acc;          // (partial sums are read back soon: plain store)
-        else out_store4(o, make_float4(__fdiv_rn(acc.x, nfull.x), __fdiv_rn(acc.y, nfull.y), __fdiv_rn(acc.z, nfull.z),
-                                       __fdiv_rn(acc.w, nfull.w)));   // tiles.py:346
+        else out_store4(o, make_float4(__fdiv_rn(acc.x, nsum.x), __fdiv_rn(acc.y, nsum.y), __fdiv_rn(acc.z, nsum.z),
+                                       __fdiv_rn(acc.w, nsum.w)));   // tiles.py:346
     }
 }
 
@@ -213,6 +236,7 @@ struct ptb_band_plan {
     int cfg_set = 0, cfg_dtype = 0, cfg_V = 0, cfg_codes = 0, cfg_red = 0;
     int cfg_views[ptb::MAX_VIEWS] = {0};
     bool cfg_act_entry = false;           // the image came in through ptb_band_plan_submit_act
+    bool cfg_norm_map = false;            // ... through ptb_band_plan_submit_rank: final items are divided by the caller's normaliser map
     int cfg_activation = 0;
     float cfg_temperature = 1.0f;
     const void *cfg_merged = nullptr, *cfg_norm = nullptr, *cfg_weight = nullptr;
@@ -482,7 +506,7 @@ extern "C" void ptb_band_plan_destroy(ptb_band_plan* p) { delete p; }
 // ptb_band_plan_submit (act_entry = false) and ptb_band_plan_submit_act (true: the kernels of ptb_tile_activation.hip)
 static int plan_submit(ptb_band_plan* p, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride, int in_dtype, int V,
                        const int* views, int reduction, float* merged, const float* norm_full, const float* weight, bool act_entry, int activation,
-                       float temperature, ptb_stream_t stream) {
+                       float temperature, bool norm_map, ptb_stream_t stream) {
     if (!p || !batch || !merged || !norm_full || !weight || B < 1) return PTB_EINVAL;
     if (!p->dev_items) return PTB_EINVAL;
     const int dtype_arg = in_dtype;      // (with PTB_ROUND_SRC and PTB_SRC_CHANNELS_LAST: part of the image's configuration)
@@ -505,7 +529,7 @@ static int plan_submit(ptb_band_plan* p, int pos, int B, const void* batch, int6
     if (p->cfg_set) {
         if (p->cfg_dtype != dtype_arg || p->cfg_V != V || p->cfg_codes != codes || p->cfg_red != reduction || p->cfg_merged != merged ||
             p->cfg_norm != norm_full || p->cfg_weight != weight || p->cfg_act_entry != act_entry || p->cfg_activation != activation ||
-            p->cfg_temperature != temperature) return PTB_EUNSUPPORTED;
+            p->cfg_temperature != temperature || p->cfg_norm_map != norm_map) return PTB_EUNSUPPORTED;
     }
     const long long per_tile = (long long)p->C * p->th * p->tw;
     const unsigned mask = in_dtype == PTB_F32 ? 15u : 7u;
@@ -516,7 +540,7 @@ static int plan_submit(ptb_band_plan* p, int pos, int B, const void* batch, int6
     p->cfg_set = 1; p->cfg_dtype = dtype_arg; p->cfg_V = V; p->cfg_codes = codes; p->cfg_red = reduction;
     for (int k = 0; k < V; ++k) p->cfg_views[k] = views[k];
     p->cfg_merged = merged; p->cfg_norm = norm_full; p->cfg_weight = weight;
-    p->cfg_act_entry = act_entry; p->cfg_activation = activation; p->cfg_temperature = temperature;
+    p->cfg_act_entry = act_entry; p->cfg_activation = activation; p->cfg_temperature = temperature; p->cfg_norm_map = norm_map;
     {
         int lg = 0;
         for (int b = 0; b < B; ++b) lg = std::max(lg, p->last_group[pos + b]);
@@ -533,6 +557,7 @@ static int plan_submit(ptb_band_plan* p, int pos, int B, const void* batch, int6
     a.in_dtype = in_dtype;
     a.round_src = (dtype_arg & PTB_ROUND_SRC) ? 1 : 0;
     a.lds_db = g_band_lds_db;
+    a.norm_map = norm_map ? 1 : 0;
     a.H = p->th; a.W = p->tw; a.C = p->C;
     a.dst_chan_stride = (long long)p->H * p->W;
     a.dst_row_stride = p->W;
@@ -585,7 +610,7 @@ extern "C" int ptb_band_plan_submit(ptb_band_plan* p, int pos, int B, const void
                                     int in_dtype, int V, const int* views, int reduction, float* merged, const float* norm_full,
                                     const float* weight, ptb_stream_t stream) {
     return plan_submit(p, pos, B, batch, tile_stride, view_stride, in_dtype, V, views, reduction, merged, norm_full, weight, false, PTB_ACT_NONE, 1.0f,
-                       stream);
+                       false, stream);
 }
 
 // ptb_band_plan_submit on A(batch) = sigmoid / softmax of the logits (PTB_ACT_*), evaluated in registers.  The source counts as fp32
@@ -595,7 +620,7 @@ extern "C" int ptb_band_plan_submit_act(ptb_band_plan* p, int pos, int B, const 
                                         const float* weight, int activation, float temperature, ptb_stream_t stream) {
     if (activation < PTB_ACT_NONE || activation > PTB_ACT_SOFTMAX || !std::isfinite(temperature)) return PTB_EINVAL;
     return plan_submit(p, pos, B, batch, tile_stride, view_stride, in_dtype & ~PTB_ROUND_SRC, V, views, reduction, merged, norm_full, weight, true,
-                       activation, temperature, stream);
+                       activation, temperature, false, stream);
 }
 
 // The next planned batch of an image as the shortest possible host call (round 6: one integrate_batch of the reference's loop, inference/
@@ -667,7 +692,9 @@ extern "C" int ptb_band_plan_submit_rank(ptb_band_plan* p, int pos, int B, const
                                          const float* weight, int n_sends, const int64_t* rects, float* const* send_bufs, int* packed,
                                          void* ready_event, int* all_packed, ptb_stream_t stream) {
     if (n_sends < 0 || (n_sends && (!rects || !send_bufs || !packed || !ready_event))) return PTB_EINVAL;
-    const int rc = ptb_band_plan_submit(p, pos, B, batch, tile_stride, view_stride, in_dtype, V, views, reduction, merged, norm_full, weight, stream);
+    // (norm_map: the final rows of a rank are divided by the map it hands in -- see band_plan_kernel)
+    const int rc = plan_submit(p, pos, B, batch, tile_stride, view_stride, in_dtype, V, views, reduction, merged, norm_full, weight, false, PTB_ACT_NONE,
+                               1.0f, true, stream);
     if (rc < 0) return rc;
     int done = 0, fresh = 0;
     for (int k = 0; k < n_sends; ++k) {

@@ -255,7 +255,11 @@ __global__ __launch_bounds__(CL_THREADS) void cl_plan_kernel(const ViewArgs a, c
                     wv[e] = a.weight[(long long)(ly + r) * a.W + lx + x];
                 }
             }
-            const float nfull = partial ? 1.f : a.norm_full[pix];
+            // the normaliser: the window values in integration order, as ptb_norm_accumulate sums them -- or the caller's map (a.norm_map: band_plan_kernel)
+            float nsum = (a.norm_map && !partial) ? a.norm_full[pix] : 0.f;
+#pragma unroll
+            for (int e = 0; e < MAX_COVER; ++e)
+                if (e < nt && !a.norm_map) nsum = __fadd_rn(nsum, wv[e]);
             for (int c0 = 0; c0 < a.C; c0 += CL_NC) {
                 const int nc = min(CL_NC, a.C - c0);
                 float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -268,7 +272,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_plan_kernel(const ViewArgs a, c
                     }
                 }
                 // (partial sums -- multi-GPU boundary rows -- are stored un-normalised, like band_plan_kernel)
-                cl_store_planes(a.merged + (long long)c0 * a.dst_chan_stride + pix, a.dst_chan_stride, nc, partial ? acc : cl_div(acc, nfull));
+                cl_store_planes(a.merged + (long long)c0 * a.dst_chan_stride + pix, a.dst_chan_stride, nc, partial ? acc : cl_div(acc, nsum));
             }
         }
     }

@@ -280,12 +280,15 @@ __global__ __launch_bounds__(TA_THREADS) void tact_plan_kernel(const ViewArgs a,
     const long long hw = (long long)a.H * a.W;
     if (nt == 0) {   // uncovered pixels: 0 / 0 like the plain merge (a path of its own: inside the pass loop it cost the eight-view instances spills)
         const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        float nz = 0.f;                       // the sum of no window value, kept from the compiler: the division below is the hardware's,
+        asm volatile("" : "+v"(nz));          // so the NaN carries the bits the plain merge's 0 / 0 has
+        const float4 nsum = make_float4(nz, nz, nz, nz);
         for (int rr = r; rr < rows && 4 * q < cw; rr += TA_CH) {
             const long long pix = (long long)(it_ay + rr) * a.dst_row_stride + it_ax + 4 * q;
             for (int c = 0; c < a.C; ++c) {
                 float* o = a.merged + (long long)c * a.dst_chan_stride + pix;
                 if (partial) *reinterpret_cast<float4*>(o) = zero;
-                else out_store4(o, ta_div(zero, *reinterpret_cast<const float4*>(a.norm_full + pix)));
+                else out_store4(o, ta_div(zero, nsum));
             }
         }
         return;
@@ -295,8 +298,7 @@ __global__ __launch_bounds__(TA_THREADS) void tact_plan_kernel(const ViewArgs a,
         const int ch = min(TA_CH, rows - r0);
         const bool lane = (r < ch) && (4 * q < cw);
         const long long pix = (long long)(it_ay + r0 + r) * a.dst_row_stride + it_ax + 4 * q;
-        float4 nfull = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (lane && !partial) nfull = *reinterpret_cast<const float4*>(a.norm_full + pix);
+        float4 nsum = make_float4(0.f, 0.f, 0.f, 0.f);   // the normaliser: the window values in integration order (band_plan_kernel), complete with the last tile
 #pragma unroll 1
         for (int e = 0; e < nt; ++e) {
             TA_COVER(e, slot, lx, ly0);
@@ -305,6 +307,7 @@ __global__ __launch_bounds__(TA_THREADS) void tact_plan_kernel(const ViewArgs a,
             const long long vs = t.vs[slot];
             float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
             if (lane) w4 = *reinterpret_cast<const float4*>(a.weight + (long long)(ly + r) * a.W + lx + 4 * q);
+            nsum = make_float4(__fadd_rn(nsum.x, w4.x), __fadd_rn(nsum.y, w4.y), __fadd_rn(nsum.z, w4.z), __fadd_rn(nsum.w, w4.w));
             float4 m[NV], rs[NV];
             if (act == PTB_ACT_SOFTMAX) ta_softmax_state<NV, CODES, LD>(m, rs, src, 0, vs, a.nviews, a.codes, a.H, a.W, a.C, lx, ly, cw, ch, tid, temp);
             const bool last = e + 1 == nt;
@@ -315,7 +318,7 @@ __global__ __launch_bounds__(TA_THREADS) void tact_plan_kernel(const ViewArgs a,
                 if (lane) {
                     float* o = a.merged + (long long)c * a.dst_chan_stride + pix;
                     const float4 acc = ta_blend(e ? *reinterpret_cast<const float4*>(o) : make_float4(0.f, 0.f, 0.f, 0.f), val, w4);
-                    if (last && !partial) out_store4(o, ta_div(acc, nfull));
+                    if (last && !partial) out_store4(o, ta_div(acc, nsum));
                     else *reinterpret_cast<float4*>(o) = acc;      // (partial sums are read back soon: plain store)
                 }
             }
@@ -454,7 +457,7 @@ __global__ __launch_bounds__(TA_CL_THREADS) void tact_cl_plan_kernel(const ViewA
     for (int r = ty; r < ch; r += 16) {
         for (int x = tx; x < cw; x += 16) {
             const long long pix = (long long)(ay + r) * a.dst_row_stride + ax + x;
-            const float nfull = partial ? 1.f : a.norm_full[pix];
+            float nsum = 0.f;   // the normaliser: summed from the window values beside the first channel group's blend (band_plan_kernel)
             for (int c0 = 0; c0 < a.C; c0 += TA_CREG) {
                 const int nc = min(TA_CREG, a.C - c0);
                 float s[TA_CREG][1];
@@ -465,6 +468,7 @@ __global__ __launch_bounds__(TA_CL_THREADS) void tact_cl_plan_kernel(const ViewA
                     TA_COVER(e, slot, lx, ly);
                     const int lj = lx + x, li = ly + r;
                     const float w = a.weight[(long long)li * a.W + lj];
+                    if (c0 == 0) nsum = __fadd_rn(nsum, w);
                     float v[TA_CREG][1];
                     tcl_reduce_px<LD, VEC>(v, static_cast<const float*>(t.src[slot]), 0, t.vs[slot], a.nviews, a.codes, a.H, a.W, a.C, li, lj, c0, nc, a.op,
                                            a.divisor, act, temp);
@@ -473,7 +477,7 @@ __global__ __launch_bounds__(TA_CL_THREADS) void tact_cl_plan_kernel(const ViewA
                 float* o = a.merged + (long long)c0 * a.dst_chan_stride + pix;
 #pragma unroll
                 for (int c = 0; c < TA_CREG; ++c)
-                    if (c < nc) o[(long long)c * a.dst_chan_stride] = partial ? s[c][0] : __fdiv_rn(s[c][0], nfull);
+                    if (c < nc) o[(long long)c * a.dst_chan_stride] = partial ? s[c][0] : __fdiv_rn(s[c][0], nsum);
             }
         }
     }

@@ -67,6 +67,7 @@ struct ViewArgs {
     int round_src;       // PTB_ROUND_SRC: the reduced value is rounded to the (half / bf16) source type before it is blended
     int chan_loop;       // band plan kernel, identity view: one workgroup per work item walks all channels (ptb_set_tunable key 27)
     int lds_db;          // band plan kernel, prefetching instances: alternate between two sets of LDS tiles (ptb_set_tunable key 25)
+    int norm_map;        // band plan kernels: 1 = divide final items by norm_full (ptb_band_plan_submit_rank), 0 = by the window values summed in the kernel
 };
 
 enum { MODE_REDUCE = 0, MODE_PERVIEW = 1, MODE_ACCUM = 2 };
