@@ -115,7 +115,9 @@ const char* ptb_last_hip_error(void);
  *      the transposing views: one barrier per covering tile instead of two (0|1, default 1),
  * 27 = band launches of the identity view (the plain loop without TTA) run one workgroup per work item over ALL channels: the window and
  *      the normaliser are loaded once per pixel instead of once per channel, every covering tile of a channel is requested at once (0|1,
- *      default 1).
+ *      default 1),
+ * 28 = fp16 / bf16 d4 launches of a band plan take the PAIRS of each launch group (ptb_band_plan_pairs) as 64 x 128 blocks, whose transposing
+ *      views are read in 256-byte rows like the row-preserving ones (0|1, default 1; 0: one 64 x 64 item per workgroup as for every other source).
  * Every setting computes the same values (key 19: bit for bit for segments of up to 2^24 elements -- above that the separate dot kernel's
  * (float)(i + 1) positions round and the two settings may differ in the last bits, the default being the reference's telescoping
  * difference); the keys exist for same-box A/B runs and for tests that compare two code paths bit for bit. */
@@ -245,6 +247,10 @@ int64_t ptb_band_plan_create(const int64_t* xs, const int64_t* ys, int n, int C,
 int ptb_band_plan_upload(ptb_band_plan* plan, void* dev_table, ptb_stream_t stream);
 int ptb_band_plan_info(const ptb_band_plan* plan, int* n_groups, int* n_bands, int64_t* n_items, int64_t* last_group_of_tile,
                        int64_t* group_rows);
+/* ptb_band_plan_pairs (host only): how launch group `group` of the table is laid out -- first *pair_cnt pairs of vertically adjacent full
+ * 64 x 64 items under the same covering tiles (top item, then the one 64 rows below it), then *single_cnt items without a partner;
+ * 2 * pair_cnt + single_cnt items in all.  Plans with 32-row items, non-square tiles or items off the 8-pixel grid of their tiles have no pairs. */
+int ptb_band_plan_pairs(const ptb_band_plan* plan, int group, int* pair_cnt, int* single_cnt);
 int ptb_band_plan_reset(ptb_band_plan* plan);
 int ptb_band_plan_state(const ptb_band_plan* plan, int* pos, int* launched);
 int ptb_band_plan_submit(ptb_band_plan* plan, int pos, int B, const void* batch, int64_t tile_stride, int64_t view_stride, int in_dtype,

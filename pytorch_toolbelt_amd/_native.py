@@ -82,6 +82,7 @@ SIGNATURES = {
     "ptb_band_plan_create": (_c_i64, [_i64p, _i64p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _i64p, _c_int, _vpp]),
     "ptb_band_plan_upload": (_c_int, [_vp, _vp, _vp]),
     "ptb_band_plan_info": (_c_int, [_vp, _ip, _ip, _i64p, _i64p, _i64p]),
+    "ptb_band_plan_pairs": (_c_int, [_vp, _c_int, _ip, _ip]),
     "ptb_band_plan_reset": (_c_int, [_vp]),
     "ptb_band_plan_state": (_c_int, [_vp, _ip, _ip]),
     "ptb_band_plan_submit": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_i64, _c_int, _c_int, _ip, _c_int, _vp, _vp, _vp, _vp]),

@@ -17,6 +17,8 @@
 // pays them once per 400 us.  Items are ordered heavy-first (4-tile items before 2- and 1-tile ones) so the tail is short work.
 #include <algorithm>
 #include <cmath>
+#include <map>
+#include <utility>
 #include <vector>
 
 #include "ptb_dispatch.h"
@@ -212,7 +214,8 @@ struct Group {
     std::vector<int> tiles;     // plan indices, ascending (slot = position)
     int last_tile;              // the group is complete once this plan index is in (-1: no tile at all)
     long long item_off;         // first item in the table
-    int item_cnt;
+    int item_cnt;               // = 2 * pair_cnt + single_cnt:
+    int pair_cnt, single_cnt;   // the group's items are its pairs (top item, then its bottom one), then the items without a partner
 };
 
 }  // namespace ptb
@@ -292,6 +295,55 @@ static int band_items(const ptb_band_plan& p, const std::vector<int>& cover, con
         }
     }
     return PTB_OK;
+}
+
+// Orders the items of one launch group: first the PAIRS -- two full 64 x 64 items of which the second lies 64 rows below the first
+// under the same covering tiles (same slots and lx, ly + 64), top item directly followed by its bottom one and marked pair_top -- then
+// the items without a partner; heavy first (4-tile items before 2- and 1-tile ones) within either part, so the tail is short work.
+// band_pair_kernel (ptb_bandpair.hip) reads the transposing views of a pair's 16-bit tiles 16 bytes per lane: the plan pairs only when
+// its tiles are square with rows of whole 16-byte groups, every tile row starts on the 8-pixel grid and so does every pair's block in
+// its tiles (ly % 8 == 0; a caller's cut may put a band off the grid).  A plan with tile rows off the grid gets NO pairs rather than
+// the few of the bands that happen to be aligned: its groups stay one launch each.  Every other kernel reads the table one item per
+// workgroup and does not care.  Returns the number of pairs.
+static int pair_items(const ptb_band_plan& p, std::vector<BandItem>& its) {
+    const int n = (int)its.size();
+    std::vector<int> bottom_of(n, -1);
+    std::vector<char> taken(n, 0);
+    if (p.ch == 64 && p.th == p.tw && p.tw % 8 == 0 && std::all_of(p.ys.begin(), p.ys.end(), [](int y) { return y % 8 == 0; })) {
+        std::map<std::pair<int, int>, int> at;      // (ax, ay) -> item
+        for (int i = 0; i < n; ++i) at[{its[i].ax, its[i].ay}] = i;
+        for (int i = 0; i < n; ++i) {               // (a band's items come top-down, so a column of an odd number of items leaves its LAST one single)
+            const BandItem& top = its[i];
+            if (taken[i] || top.ntiles < 1 || (top.cwch >> 16) != 64) continue;
+            const auto f = at.find({top.ax, top.ay + 64});
+            if (f == at.end() || taken[f->second]) continue;
+            const BandItem& bot = its[f->second];
+            bool ok = bot.cwch == top.cwch && bot.ntiles == top.ntiles && bot.partial == top.partial;
+            for (int e = 0; ok && e < top.ntiles; ++e)
+                ok = bot.cover[e] == top.cover[e] + (64ULL << 32) && ((top.cover[e] >> 32) & 7) == 0;
+            if (!ok) continue;
+            bottom_of[i] = f->second;
+            taken[i] = taken[f->second] = 1;
+        }
+    }
+    std::vector<int> tops, singles;
+    for (int i = 0; i < n; ++i) {
+        if (bottom_of[i] >= 0) tops.push_back(i);
+        else if (!taken[i]) singles.push_back(i);
+    }
+    const auto heavier = [&](int l, int r) { return its[l].ntiles > its[r].ntiles; };
+    std::stable_sort(tops.begin(), tops.end(), heavier);
+    std::stable_sort(singles.begin(), singles.end(), heavier);
+    std::vector<BandItem> out;
+    out.reserve(its.size());
+    for (int i : tops) {
+        out.push_back(its[i]);
+        out.back().pair_top = 1;
+        out.push_back(its[bottom_of[i]]);
+    }
+    for (int i : singles) out.push_back(its[i]);
+    its.swap(out);
+    return (int)tops.size();
 }
 
 extern "C" int64_t ptb_band_plan_create(const int64_t* xs64, const int64_t* ys64, int n, int C, int th, int tw, int H, int W,
@@ -380,8 +432,9 @@ extern "C" int64_t ptb_band_plan_create3(const int64_t* xs64, const int64_t* ys6
             if (rc != PTB_OK) return rc;
             p->band_group[b] = gi;
         }
-        std::stable_sort(its.begin(), its.end(), [](const BandItem& l, const BandItem& r) { return l.ntiles > r.ntiles; });
+        g.pair_cnt = pair_items(*p, its);
         g.item_cnt = (int)its.size();
+        g.single_cnt = g.item_cnt - 2 * g.pair_cnt;
         p->items.insert(p->items.end(), its.begin(), its.end());
         for (int t : tiles) p->last_group[t] = std::max(p->last_group[t], gi);
         p->groups.push_back(std::move(g));
@@ -486,6 +539,13 @@ extern "C" int ptb_band_plan_info(const ptb_band_plan* p, int* n_groups, int* n_
     return PTB_OK;
 }
 
+extern "C" int ptb_band_plan_pairs(const ptb_band_plan* p, int group, int* pair_cnt, int* single_cnt) {
+    if (!p || group < 0 || group >= (int)p->groups.size()) return PTB_EINVAL;
+    if (pair_cnt) *pair_cnt = p->groups[group].pair_cnt;
+    if (single_cnt) *single_cnt = p->groups[group].single_cnt;
+    return PTB_OK;
+}
+
 extern "C" int ptb_band_plan_reset(ptb_band_plan* p) {
     if (!p) return PTB_EINVAL;
     p->pos = 0; p->launched = 0; p->cfg_set = 0;
@@ -586,9 +646,15 @@ static int plan_submit(ptb_band_plan* p, int pos, int B, const void* batch, int6
             }
             // identity view on the prefetching instances: one workgroup per item walks the channels (see band_plan_kernel, ALL)
             a.chan_loop = (V == 1 && codes == CODES_ID && g_band_chan_loop && (in_dtype != PTB_F32 ? g_band_half_pf >= 1 : g_band_half_pf >= 2)) ? 1 : 0;
-            const long long blocks = (long long)g.item_cnt * (a.chan_loop ? 1 : p->C);
-            if (blocks > 0x7fffffffLL) return PTB_EUNSUPPORTED;
-            launch_plan(a, p->dev_items + g.item_off, gt, (int)blocks, p->ch, (hipStream_t)stream);
+            // fp16 / bf16 d4 model outputs: the group's pairs go to band_pair_kernel (ptb_bandpair.hip), what is left to band_plan_kernel
+            bool pairs = g_band_pairs && g.pair_cnt > 0 && in_dtype != PTB_F32 && V == 8 && codes == CODES_D4 && g_band_half_pf >= 1 && !norm_map;
+            for (size_t s = 0; pairs && s < g.tiles.size(); ++s) pairs = aligned16(gt.src[s]) && gt.vs[s] % 8 == 0;      // (16-byte loads)
+            const int first = pairs ? 2 * g.pair_cnt : 0;
+            const int per_item = a.chan_loop ? 1 : p->C;
+            if ((long long)g.item_cnt * per_item > 0x7fffffffLL) return PTB_EUNSUPPORTED;
+            const int blocks = (g.item_cnt - first) * per_item;
+            if (pairs) bp_launch_pairs(a, p->dev_items + g.item_off, gt, g.pair_cnt, (hipStream_t)stream);
+            if (blocks > 0) launch_plan(a, p->dev_items + g.item_off + first, gt, blocks, p->ch, (hipStream_t)stream);
             const int rc = check_launch();
             if (rc != PTB_OK) return rc;
             ++p->launched;

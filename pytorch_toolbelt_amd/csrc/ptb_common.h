@@ -87,5 +87,6 @@ extern int g_band_half_pf;       // 21: clamped to 0..2, the band plan kernel pr
 extern int g_lovasz_rankdot;     // 23: 0 | 1, last level of the key-only Lovasz forward without a scatter
 extern int g_band_lds_db;        // 25: 0 | 1, double-buffered LDS tiles in the prefetching band plan instances
 extern int g_band_chan_loop;     // 27: 0 | 1, identity-view band launches, one workgroup per item over all channels
+extern int g_band_pairs;         // 28: 0 | 1, fp16 / bf16 d4 band launches take the paired items of a group as 64 x 128 blocks (band_pair_kernel)
 
 }  // namespace ptb

@@ -220,6 +220,7 @@ const Tunable kTunables[] = {
     {23, &g_lovasz_rankdot, BOOL, {}},
     {25, &g_band_lds_db, BOOL, {}},
     {27, &g_band_chan_loop, BOOL, {}},
+    {28, &g_band_pairs, BOOL, {}},
 };
 }  // namespace
 

@@ -367,6 +367,23 @@ void with_view_set(int nviews, int codes, F&& f) {
 }
 
 
+// The reduction over the views of one pixel quad, in view order (band_pair_kernel of ptb_bandpair.hip ends on the same sum, hence the same bits)
+template <int NV, int OPK>
+__device__ __forceinline__ float4 reduce_views(const float4 (&v)[NV], int nv, int op, float divisor) {
+    float4 s = make_float4(red_pre<OPK>(v[0].x, op), red_pre<OPK>(v[0].y, op), red_pre<OPK>(v[0].z, op), red_pre<OPK>(v[0].w, op));
+#pragma unroll
+    for (int k = 1; k < NV; ++k) {
+        if (k < nv) {
+            s.x = __fadd_rn(s.x, red_pre<OPK>(v[k].x, op));
+            s.y = __fadd_rn(s.y, red_pre<OPK>(v[k].y, op));
+            s.z = __fadd_rn(s.z, red_pre<OPK>(v[k].z, op));
+            s.w = __fadd_rn(s.w, red_pre<OPK>(v[k].w, op));
+        }
+    }
+    return make_float4(red_post<OPK>(s.x, op, divisor), red_post<OPK>(s.y, op, divisor), red_post<OPK>(s.z, op, divisor),
+                       red_post<OPK>(s.w, op, divisor));
+}
+
 // The second half of gather_reduce: this thread's NV loaded float4 (row-preserving views already in output orientation, transposing
 // views as read along the source rows) -> transposing views through the LDS tile -> reduction over the views.
 template <int CH, int NV, int CODES, int OPK>
@@ -412,19 +429,7 @@ __device__ __forceinline__ float4 gather_tail(float4 (&v)[NV], int nv_rt, int co
         }
         if (more_entries) __syncthreads();  // LDS tiles are reused by the next covering tile
     }
-
-    float4 s = make_float4(red_pre<OPK>(v[0].x, op), red_pre<OPK>(v[0].y, op), red_pre<OPK>(v[0].z, op), red_pre<OPK>(v[0].w, op));
-#pragma unroll
-    for (int k = 1; k < NV; ++k) {
-        if (k < nv) {
-            s.x = __fadd_rn(s.x, red_pre<OPK>(v[k].x, op));
-            s.y = __fadd_rn(s.y, red_pre<OPK>(v[k].y, op));
-            s.z = __fadd_rn(s.z, red_pre<OPK>(v[k].z, op));
-            s.w = __fadd_rn(s.w, red_pre<OPK>(v[k].w, op));
-        }
-    }
-    return make_float4(red_post<OPK>(s.x, op, divisor), red_post<OPK>(s.y, op, divisor), red_post<OPK>(s.z, op, divisor),
-                       red_post<OPK>(s.w, op, divisor));
+    return reduce_views<NV, OPK>(v, nv, op, divisor);
 }
 
 
@@ -552,7 +557,8 @@ struct BandItem {                 // 64 B = one cache line per workgroup, read w
     int cwch;                     // extent: columns | rows << 16  (<= 64 x 64)
     int ntiles;                   // covering tiles (0: uncovered pixels -> 0 / 0 = NaN like the reference's merge)
     int partial;                  // 1: write the un-normalised weighted sum (multi-GPU boundary rows) instead of sum / norm
-    int pad[3];
+    int pair_top;                 // 1: the NEXT item of the table is the same 64 columns 64 rows further down, under the same covering tiles --
+    int pad[2];                   // band_pair_kernel takes the two as one 64 x 128 block; every other kernel reads one item per workgroup as ever
     unsigned long long cover[MAX_COVER];   // ascending integration order: tile slot | lx << 16 | ly << 32 (item origin in the tile)
 };
 static_assert(sizeof(BandItem) == 64, "BandItem layout");
@@ -561,6 +567,12 @@ struct GroupTiles {
     const void* src[PLAN_TILES];  // view 0, channel 0 of the tile
     long long vs[PLAN_TILES];     // elements between consecutive views of this tile (its batch size * C * th * tw)
 };
+
+// ------------------------------------------------------------------------------------------------ paired work items (fp16 / bf16 d4 sources)
+// `pairs` consecutive (top, bottom) item couples at `items`, one workgroup per couple and channel; a.nviews / a.codes are the d4 set,
+// a.in_dtype is PTB_F16 or PTB_BF16, a.norm_map is 0, every tile source is 16-byte aligned with a.W % 8 == 0 and view strides % 8 == 0.
+// Defined in ptb_bandpair.hip.
+void bp_launch_pairs(const ViewArgs& a, const BandItem* items, const GroupTiles& t, int pairs, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ channels-last sources
 // PTB_SRC_CHANNELS_LAST: `a.src` / the tile pointers address [.., th, tw, C] memory (a model output in torch.channels_last); everything
