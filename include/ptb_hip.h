@@ -1101,6 +1101,39 @@ int ptb_centerline_dice(const void* pred, int pred_elem_bytes, const void* truth
                         const int64_t* class_values, int K, int object_rule, int method, int64_t* counts, float* cldice, float* tprec,
                         float* tsens, int32_t* took, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Soft skeleton and the soft-clDice training loss (no counterpart in the reference; Shit et al., CVPR 2021) -------
+ * For one plane x of H x W values in [0, 1] and k = iterations: E(x)(p) = the minimum of x over p and its 4 edge neighbours inside the
+ * plane, D(x)(p) = the maximum over the 3 x 3 window inside the plane; positions outside the plane never take part.
+ *   v_0 = x, v_j+1 = E(v_j), o_j = D(v_j+1), delta_j = relu(v_j - o_j) for j = 0 .. k;
+ *   S_0 = delta_0, S_j = S_j-1 + relu(delta_j - S_j-1 delta_j);  softskel_k(x) = S_k  (the published soft_skel: k + 1 erosions and dilations).
+ * With p the activation (prob = PTB_PROB_*) of the fp32 logits x [B, C, S], S = H * W, g the target of selected class c (labels int64
+ * [B, S]: labels == c; or dense fp32 [B, C, S] as it is; exactly one of them), SP = softskel_k(p_c), ST = softskel_k(g_c), the sums over
+ * batch and positions:  tprec = (sum SP g + smooth) / (sum SP + smooth),  tsens = (sum ST p + smooth) / (sum ST + smooth),
+ * loss_c = 1 - 2 tprec tsens / (tprec + tsens) (1 where tprec + tsens == 0), loss = the mean of loss_c over the K selected classes.
+ * classes: HOST int[K], distinct channels in [0, C), 1 <= K <= 32 (PTB_EUNSUPPORTED above).  1 <= iterations <= ptb_softskel_cap() = 8
+ * (PTB_EUNSUPPORTED above: the cap comes from the LDS plan of the backward kernel).  H * W <= 2^31 - 2.
+ * GRADIENT: relu'(0) = 0 (strict comparisons); E and D pass the adjoint to the one position they select, among equal values the first
+ * in row-major window order (E: up, left, centre, right, down).  No gradient flows into the target.
+ *   ptb_soft_skeleton    x, out fp32 [N, H, W]: out = softskel_iterations(x).  One launch.
+ *   ptb_soft_cldice_slots  host only: the workgroups of the forward kernel, K * B * ceil(H / 32) * ceil(W / 32), or a negative code.
+ *   ptb_soft_cldice_fwd  writes st [B, K, S] = ST (the backward reads it), loss [1] and coef [K][3] = dloss / d(sum SP g), d(sum SP),
+ *                        d(sum ST p).  Every workgroup -- one per (class, entry, 32 x 32 tile) -- writes its four fp64 sums to its own
+ *                        slot of the workspace (DEVICE, 16-byte aligned, 32 bytes a slot); a one-workgroup kernel adds them in index order.
+ *   ptb_soft_cldice_bwd  grad [B, C, S] = upstream[0] * dloss / dx, upstream DEVICE float[1]; dp [B, K, S] is scratch the call writes
+ *                        (dloss / dp of the selected classes).  A tile kernel (the adjoint in gather form: no atomics) and a streaming
+ *                        pass for the activation.  Unselected channels of a sigmoid / identity get zeros.
+ * Stream-ordered, nothing is read back, no workgroup waits for another one; grids depend on the shape and iterations alone and every sum
+ * has a fixed order: the same bits on every run. */
+int ptb_softskel_cap(void);
+int ptb_soft_skeleton(const float* x, int64_t N, int64_t H, int64_t W, int iterations, float* out, ptb_stream_t stream);
+int64_t ptb_soft_cldice_slots(int64_t B, int K, int64_t H, int64_t W);
+int ptb_soft_cldice_fwd(const float* x, const int64_t* labels, const float* dense, int64_t B, int C, int64_t H, int64_t W, const int* classes,
+                        int K, int prob, int iterations, float smooth, float* st, void* workspace, int64_t workspace_bytes, float* loss,
+                        float* coef, ptb_stream_t stream);
+int ptb_soft_cldice_bwd(const float* x, const int64_t* labels, const float* dense, int64_t B, int C, int64_t H, int64_t W, const int* classes,
+                        int K, int prob, int iterations, const float* st, const float* coef, const float* upstream, float* dp, float* grad,
+                        ptb_stream_t stream);
+
 /* ---- Surface metrics of two label maps (no counterpart in the reference) ---------------------------------------------
  * pred, truth = [B, D, H, W] contiguous label maps (dims = 2: D == 1), each with its own elem_bytes (1 = bool / uint8, 2 / 4 / 8
  * signed), read where they lie.  Object k of an entry is, with PTB_SURFACE_CLASSES, the positions that hold class_values[k] (HOST, K

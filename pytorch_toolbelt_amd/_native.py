@@ -206,6 +206,11 @@ SIGNATURES = {
     "ptb_skeleton": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_int, _c_i64, _vp, _ip, _vp, _c_i64, _vp]),
     "ptb_centerline_dice_plan": (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _i64p]),
     "ptb_centerline_dice": (_c_int, [_vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _ip, _vp, _c_i64, _vp]),
+    "ptb_softskel_cap": (_c_int, []),
+    "ptb_soft_skeleton": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _c_int, _vp, _vp]),
+    "ptb_soft_cldice_slots": (_c_i64, [_c_i64, _c_int, _c_i64, _c_i64]),
+    "ptb_soft_cldice_fwd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_i64, _ip, _c_int, _c_int, _c_int, _c_f, _vp, _vp, _c_i64, _vp, _vp, _vp]),
+    "ptb_soft_cldice_bwd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_i64, _ip, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ptb_surface_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _ip, _i64p, _i64p, _ip]),
     "ptb_surface_metrics": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, ctypes.POINTER(_c_d), _c_d,
                                      ctypes.POINTER(_c_d), _c_int] + [_vp] * 8 + [_vp, _c_i64, _vp]),

@@ -254,3 +254,27 @@ def quality_focal(predictions, targets, beta, reduction):
     if reduction == "normalized":
         return loss.sum() / modulator.sum()
     return _reduce(loss, reduction) if reduction in ("mean", "sum") else loss
+
+
+def soft_skeleton(x, iterations):
+    """``softskel_k`` of the planes ``x [N, C, H, W]`` (losses/cldice.py holds the definition): the chain of the published ``soft_skel`` on
+    ``max_pool2d``, whose padding of ``-inf`` is "positions outside the plane never take part"; autograd gives its backward."""
+    def erode(v):
+        return -torch.maximum(F.max_pool2d(-v, (3, 1), 1, (1, 0)), F.max_pool2d(-v, (1, 3), 1, (0, 1)))
+
+    v, skel = x, None
+    for _ in range(iterations + 1):
+        nxt = erode(v)
+        delta = F.relu(v - F.max_pool2d(nxt, 3, 1, 1))
+        skel = delta if skel is None else skel + F.relu(delta - skel * delta)
+        v = nxt
+    return skel
+
+
+def soft_cldice(p, g, iterations, smooth):
+    """the soft-clDice loss of probabilities ``p`` and targets ``g``, both ``[B, K, H, W]``: per class, then the mean"""
+    g = g.detach()
+    sp, st = soft_skeleton(p, iterations), soft_skeleton(g, iterations)
+    tprec = ((sp * g).sum((0, 2, 3)) + smooth) / (sp.sum((0, 2, 3)) + smooth)
+    tsens = ((st * p).sum((0, 2, 3)) + smooth) / (st.sum((0, 2, 3)) + smooth)
+    return (1.0 - 2.0 * tprec * tsens / (tprec + tsens)).mean()

@@ -31,8 +31,8 @@ THE SKELETON is the state after the first iteration that deletes nothing; with `
 entirely (and so can lose a component); ``guo_hall`` keeps one position of it.
 
 Left out: 3-D thinning (Lee 1994 / Palagyi; there is no ``dims`` argument yet), the medial axis with distances (compose it as
-``skeletonize(m) * distance_transform(m)``), pruning of spurs and node / branch classification, ``ignore_index``, and the soft-clDice
-training loss with its gradients.
+``skeletonize(m) * distance_transform(m)``), pruning of spurs and node / branch classification, and ``ignore_index``.  The
+soft-clDice training loss is ``losses.SoftClDiceLoss``.
 """
 import ctypes
 
