@@ -1134,6 +1134,37 @@ int ptb_soft_cldice_bwd(const float* x, const int64_t* labels, const float* dens
                         int K, int prob, int iterations, const float* st, const float* coef, const float* upstream, float* dp, float* grad,
                         ptb_stream_t stream);
 
+/* ---- Soft skeleton and soft clDice of VOLUMES (dims = 3) ---------------------------------------------------------------
+ * The chain, the loss, relu'(0) = 0 and "no gradient into the target" are those above; only the stencils change.  For one volume x of
+ * D x H x W values: E(x)(p) = the minimum over p and its 6 face neighbours inside the volume, D(x)(p) = the maximum over the 3 x 3 x 3
+ * window inside the volume; positions outside the volume never take part (the published 5-D soft_erode / soft_dilate: three max_pool3d
+ * of (3,1,1), (1,3,1), (1,1,3), and one of (3,3,3)).  S = D * H * W; logits [B, C, S], labels [B, S], dense [B, C, S] as above.
+ * TIE RULE OF THE GRADIENT: a window hands its adjoint to the first of equal values in row-major window order, z slowest -- E: z-1, y-1,
+ * x-1, centre, x+1, y+1, z+1; D: the 27 offsets with dz, then dy, then dx ascending.  On volumes of distinct values the gradient does not
+ * depend on this rule.  1 <= iterations <= ptb_softskel_cap(), 1 <= K <= 32 (PTB_EUNSUPPORTED above either); B * S <= 2^31 - 2.
+ * One launch per stage, a workgroup per 8 x 8 x 32 tile with a halo of 2 in LDS; levels travel through HBM as fp32.
+ *   ptb_soft_skeleton_3d  x, out fp32 [N, D, H, W]: out = softskel_iterations(x).  workspace: DEVICE, at least 8 * N * S bytes (two rolling
+ *                        levels).  iterations + 1 launches.
+ *   ptb_soft_cldice_3d_workspace  host only: the bytes of the loss's workspace -- 32 per slot (K * B * tiles), then fp32 planes of
+ *                        B * K * S: the prediction's S, two rolling levels of the target, and two rolling levels of the prediction or,
+ *                        with keep_grad, the two level stores of iterations + 1 planes each (v_j+1 and delta_j).  A negative code:
+ *                        an unsupported shape.
+ *   ptb_soft_cldice_3d_fwd  writes st [B, K, S] = ST, loss [1] and coef [K][3] like ptb_soft_cldice_fwd; workspace DEVICE, 16-byte
+ *                        aligned, of the size above for the same keep_grad.  keep_grad = 0 keeps nothing for a backward.
+ *   ptb_soft_cldice_3d_bwd  takes the workspace a keep_grad forward of the same arguments filled and USES IT UP (delta_j is overwritten by
+ *                        direct_j, the rolling planes carry gv, the S plane dloss / dp): one backward per forward.  grad [B, C, S] =
+ *                        upstream[0] * dloss / dx.  A pointwise kernel, iterations + 2 gather launches (no atomics), the activation pass.
+ * Stream-ordered, nothing is read back, no workgroup waits for another one; every sum has a fixed order: the same bits on every run. */
+int ptb_soft_skeleton_3d(const float* x, int64_t N, int64_t D, int64_t H, int64_t W, int iterations, float* out, void* workspace,
+                         int64_t workspace_bytes, ptb_stream_t stream);
+int64_t ptb_soft_cldice_3d_workspace(int64_t B, int K, int64_t D, int64_t H, int64_t W, int iterations, int keep_grad);
+int ptb_soft_cldice_3d_fwd(const float* x, const int64_t* labels, const float* dense, int64_t B, int C, int64_t D, int64_t H, int64_t W,
+                           const int* classes, int K, int prob, int iterations, float smooth, int keep_grad, float* st, void* workspace,
+                           int64_t workspace_bytes, float* loss, float* coef, ptb_stream_t stream);
+int ptb_soft_cldice_3d_bwd(const float* x, const int64_t* labels, const float* dense, int64_t B, int C, int64_t D, int64_t H, int64_t W,
+                           const int* classes, int K, int prob, int iterations, const float* st, const float* coef, const float* upstream,
+                           void* workspace, int64_t workspace_bytes, float* grad, ptb_stream_t stream);
+
 /* ---- Surface metrics of two label maps (no counterpart in the reference) ---------------------------------------------
  * pred, truth = [B, D, H, W] contiguous label maps (dims = 2: D == 1), each with its own elem_bytes (1 = bool / uint8, 2 / 4 / 8
  * signed), read where they lie.  Object k of an entry is, with PTB_SURFACE_CLASSES, the positions that hold class_values[k] (HOST, K

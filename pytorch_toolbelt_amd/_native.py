@@ -211,6 +211,10 @@ SIGNATURES = {
     "ptb_soft_cldice_slots": (_c_i64, [_c_i64, _c_int, _c_i64, _c_i64]),
     "ptb_soft_cldice_fwd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_i64, _ip, _c_int, _c_int, _c_int, _c_f, _vp, _vp, _c_i64, _vp, _vp, _vp]),
     "ptb_soft_cldice_bwd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_i64, _ip, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ptb_soft_skeleton_3d": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _vp]),
+    "ptb_soft_cldice_3d_workspace": (_c_i64, [_c_i64, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _c_int]),
+    "ptb_soft_cldice_3d_fwd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_i64, _c_i64, _ip, _c_int, _c_int, _c_int, _c_f, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp]),
+    "ptb_soft_cldice_3d_bwd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_i64, _c_i64, _ip, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp]),
     "ptb_surface_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _ip, _i64p, _i64p, _ip]),
     "ptb_surface_metrics": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, ctypes.POINTER(_c_d), _c_d,
                                      ctypes.POINTER(_c_d), _c_int] + [_vp] * 8 + [_vp, _c_i64, _vp]),

@@ -36,12 +36,11 @@
 
 #include "ptb_common.h"
 #include "ptb_dispatch.h"
+#include "ptb_softskel_host.h"
 
 namespace ptb {
 
 constexpr int SS_THREADS = 256;
-constexpr int SS_CAP = 8;
-constexpr int SS_MAX_CLASSES = 32;
 constexpr int SS_FWD_TILE = 32;
 #define SS_INF __builtin_inff()
 
@@ -473,18 +472,22 @@ static int ss_problem(int64_t B, int C, int K, int64_t H, int64_t W, int iterati
     return PTB_OK;
 }
 
-static int ss_classes(const int* classes, int C, int K, int (&cls)[SS_MAX_CLASSES]) {
-    if (!classes || K < 1 || K > SS_MAX_CLASSES) return K > SS_MAX_CLASSES ? PTB_EUNSUPPORTED : PTB_EINVAL;
-    for (int k = 0; k < K; ++k) {
-        if (classes[k] < 0 || classes[k] >= C) return PTB_EINVAL;
-        for (int i = 0; i < k; ++i)
-            if (classes[i] == classes[k]) return PTB_EINVAL;
-        cls[k] = classes[k];
-    }
-    return PTB_OK;
+// ptb_softskel_host.h: the rank-agnostic kernels for the volume unit
+void ss_launch_finish(const double* slots, unsigned per_class, int K, float smooth, float* loss, float* coef, hipStream_t stream) {
+    hipLaunchKernelGGL(ss_finish_kernel, dim3(1), dim3(SS_THREADS), 0, stream, slots, per_class, K, smooth, loss, coef);
 }
 
-static bool ss_bad_prob(int prob) { return prob != PTB_PROB_SOFTMAX && prob != PTB_PROB_SIGMOID && prob != PTB_PROB_IDENTITY; }
+int ss_launch_act_bwd(const float* x, const float* dp, const float* upstream, float* grad, const int* cls, int K, int C, int prob, size_t B, size_t S,
+                      hipStream_t stream) {
+    const size_t positions = B * S, blocks = (positions + SS_THREADS - 1) / SS_THREADS;        // the streaming pass: a lane a position
+    if (blocks > 0x7fffffffULL) return PTB_EUNSUPPORTED;
+    SsActArgs g{};
+    g.x = x; g.dp = dp; g.upstream = upstream; g.grad = grad;
+    for (int k = 0; k < K; ++k) g.cls[k] = cls[k];
+    g.S = S; g.total = positions; g.C = C; g.K = K; g.act = prob;
+    hipLaunchKernelGGL(ss_act_bwd_kernel, dim3((unsigned)blocks), dim3(SS_THREADS), 0, stream, g);
+    return PTB_OK;
+}
 
 }  // namespace ptb
 
@@ -525,7 +528,7 @@ extern "C" int ptb_soft_cldice_fwd(const float* x, const int64_t* labels, const 
     with_at_most<5, 10>(iterations + 2, [&](auto r) {
         hipLaunchKernelGGL((ss_fwd_kernel<r(), true>), dim3((unsigned)slots), dim3(SS_THREADS), 0, s, a);
     });
-    hipLaunchKernelGGL(ss_finish_kernel, dim3(1), dim3(SS_THREADS), 0, s, a.slots, (unsigned)(B * a.tiles), K, smooth, loss, coef);
+    ss_launch_finish(a.slots, (unsigned)(B * a.tiles), K, smooth, loss, coef, s);
     return check_launch();
 }
 
@@ -539,17 +542,12 @@ extern "C" int ptb_soft_cldice_bwd(const float* x, const int64_t* labels, const 
     if (int rc = ss_problem(B, C, K, H, W, iterations, T, a)) return rc;
     a.x = x; a.labels = reinterpret_cast<const long long*>(labels); a.dense = dense; a.st = const_cast<float*>(st); a.act = prob;
     a.coef = coef; a.dp = dp;
-    const size_t positions = (size_t)B * (size_t)H * (size_t)W, blocks = (positions + SS_THREADS - 1) / SS_THREADS;        // the streaming pass: a lane a position
-    if (blocks > 0x7fffffffULL) return PTB_EUNSUPPORTED;
+    if (((size_t)B * (size_t)H * (size_t)W + SS_THREADS - 1) / SS_THREADS > 0x7fffffffULL) return PTB_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((long long)K * B * a.tiles));
     if (T == 32) hipLaunchKernelGGL((ss_bwd_kernel<SsBwd<32, 5>>), grid, dim3(SS_THREADS), 0, s, a);
     else if (T == 24) hipLaunchKernelGGL((ss_bwd_kernel<SsBwd<24, 7>>), grid, dim3(SS_THREADS), 0, s, a);
     else hipLaunchKernelGGL((ss_bwd_kernel<SsBwd<16, 10>>), grid, dim3(SS_THREADS), 0, s, a);
-    SsActArgs g{};
-    g.x = x; g.dp = dp; g.upstream = upstream; g.grad = grad;
-    for (int k = 0; k < K; ++k) g.cls[k] = a.cls[k];
-    g.S = (size_t)H * (size_t)W; g.total = positions; g.C = C; g.K = K; g.act = prob;
-    hipLaunchKernelGGL(ss_act_bwd_kernel, dim3((unsigned)blocks), dim3(SS_THREADS), 0, s, g);
+    ss_launch_act_bwd(x, dp, upstream, grad, a.cls, K, C, prob, (size_t)B, (size_t)H * (size_t)W, s);
     return check_launch();
 }

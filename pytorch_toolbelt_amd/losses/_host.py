@@ -257,24 +257,33 @@ def quality_focal(predictions, targets, beta, reduction):
 
 
 def soft_skeleton(x, iterations):
-    """``softskel_k`` of the planes ``x [N, C, H, W]`` (losses/cldice.py holds the definition): the chain of the published ``soft_skel`` on
-    ``max_pool2d``, whose padding of ``-inf`` is "positions outside the plane never take part"; autograd gives its backward."""
+    """``softskel_k`` of the planes ``x [N, C, H, W]`` or the volumes ``x [N, C, D, H, W]`` (losses/cldice.py holds the definition): the chain of the
+    published ``soft_skel`` on ``max_pool2d`` / ``max_pool3d``, whose padding of ``-inf`` is "positions outside never take part"; autograd gives its
+    backward."""
+    n = x.dim() - 2
+    pool = F.max_pool3d if n == 3 else F.max_pool2d
+    lines = [(tuple(3 if a == b else 1 for a in range(n)), tuple(1 if a == b else 0 for a in range(n))) for b in range(n)]
+
     def erode(v):
-        return -torch.maximum(F.max_pool2d(-v, (3, 1), 1, (1, 0)), F.max_pool2d(-v, (1, 3), 1, (0, 1)))
+        out = pool(-v, lines[0][0], 1, lines[0][1])
+        for kernel, pad in lines[1:]:
+            out = torch.maximum(out, pool(-v, kernel, 1, pad))
+        return -out
 
     v, skel = x, None
     for _ in range(iterations + 1):
         nxt = erode(v)
-        delta = F.relu(v - F.max_pool2d(nxt, 3, 1, 1))
+        delta = F.relu(v - pool(nxt, 3, 1, 1))
         skel = delta if skel is None else skel + F.relu(delta - skel * delta)
         v = nxt
     return skel
 
 
 def soft_cldice(p, g, iterations, smooth):
-    """the soft-clDice loss of probabilities ``p`` and targets ``g``, both ``[B, K, H, W]``: per class, then the mean"""
+    """the soft-clDice loss of probabilities ``p`` and targets ``g``, both ``[B, K, (D,) H, W]``: per class, then the mean"""
     g = g.detach()
     sp, st = soft_skeleton(p, iterations), soft_skeleton(g, iterations)
-    tprec = ((sp * g).sum((0, 2, 3)) + smooth) / (sp.sum((0, 2, 3)) + smooth)
-    tsens = ((st * p).sum((0, 2, 3)) + smooth) / (st.sum((0, 2, 3)) + smooth)
+    over = (0,) + tuple(range(2, p.dim()))
+    tprec = ((sp * g).sum(over) + smooth) / (sp.sum(over) + smooth)
+    tsens = ((st * p).sum(over) + smooth) / (st.sum(over) + smooth)
     return (1.0 - 2.0 * tprec * tsens / (tprec + tsens)).mean()

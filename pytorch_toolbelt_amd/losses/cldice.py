@@ -18,6 +18,12 @@ target of a selected class ``c``, ``SP = softskel_k(p_c)``, ``ST = softskel_k(g_
 Per class and then the mean, like ``DiceLoss`` here: for ``binary`` mode or one selected class this is the published value; the paper pools
 all foreground channels into one set of sums instead (left out).
 
+VOLUMES (``dims=3``).  For one volume ``x`` of ``D x H x W`` values the chain, the loss and the mean are the same and only the stencils change:
+``E(x)(p)`` is the minimum over ``p`` and its 6 face neighbours inside the volume, ``D(x)(p)`` the maximum over the 3 x 3 x 3 window inside the volume;
+positions outside the volume never take part -- the published 5-D ``soft_erode`` / ``soft_dilate``: three ``max_pool3d`` of ``(3,1,1)``, ``(1,3,1)``,
+``(1,1,3)``, and one of ``(3,3,3)``.  Tie order of the gradient, z slowest: ``E``: z-1, y-1, x-1, centre, x+1, y+1, z+1; ``D``: the 27 offsets with
+``dz``, then ``dy``, then ``dx`` ascending.
+
 GRADIENT.  ``relu'(0) = 0``: comparisons are strict.  ``E`` and ``D`` pass the adjoint to the one position they select; among equal values of a window
 the first in row-major window order (``E``: up, left, centre, right, down).  When all values of a plane are distinct, every tie inside the
 chain traces back to one source position and the gradient does not depend on this rule.  No gradient flows into the target.
@@ -27,9 +33,17 @@ kernel with the stencil blocked in time in LDS, a one-workgroup finish, and for 
 atomics: the same bits on every run) followed by a streaming pass for the activation.  It keeps the logits, the target and ``ST`` (4 bytes per
 position and selected class) instead of the ``4 (k + 1)`` planes autograd keeps of the torch chain.  ``1 <= iterations <= 8`` and at most 32
 selected classes run natively; above either cap CUDA tensors raise ``NotImplementedError``.  CPU tensors take the ``max_pool2d`` chain of
-``losses/_host.py``: the same definitions, autograd's backward.
+``losses/_host.py`` (``max_pool3d`` for volumes): the same definitions, autograd's backward.
 
-Left out: 3-D volumes (a fused 3-D halo does not fit LDS; 5-D input raises for CPU and CUDA alike), ``ignore_index``, ``reduction="none"``, the
+With ``dims=3`` CUDA tensors run ``csrc/ptb_softskel3d.hip``, again as ONE autograd node: blocking ``k + 1`` stages in time would need a halo of ``k + 2``
+in three axes, so every stage is a launch of its own -- an 8 x 8 x 32 tile with a halo of 2 in LDS, a lane walking a column in z -- and the
+levels travel through HBM as fp32.  The backward is a pointwise kernel over the stored ``delta_j``, one gather launch per level (selection
+bytes in LDS, no atomics: the same bits on every run) and the same activation pass.  The node keeps the logits, the target, ``ST`` and a
+workspace of ``2 (k + 1) + 3`` fp32 values per position and selected class (``v_j+1`` and ``delta_j`` of every stage; the backward reuses the
+rest as its scratch and overwrites the deltas, so one backward per forward); under ``torch.no_grad()`` or without a gradient on the
+prediction no level is kept (5 values).  A 5-D prediction under the default ``dims=2`` raises ``NotImplementedError``: pass ``dims=3``.
+
+Left out: ``ignore_index``, ``reduction="none"``, anisotropic windows for volumes, more than one stage per launch for volumes, the
 pooled-channels form of the paper, a combined Dice + clDice class (add ``DiceLoss`` yourself), a differentiable ``soft_skeleton``, and native
 fp16 / bf16 reads (half precision is widened first, like the other losses)."""
 from typing import List, Optional
@@ -48,6 +62,12 @@ from ._region import BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE
 __all__ = ["SoftClDiceLoss", "soft_cldice_loss"]
 
 MAX_CLASSES = 32                                 # SS_MAX_CLASSES of csrc/ptb_softskel.hip
+
+
+def _check_dims(what, dims):
+    if isinstance(dims, bool) or dims not in (2, 3):
+        raise ValueError(f"{what}: dims must be 2 or 3, got {dims!r}")
+    return int(dims)
 
 
 def _check_config(what, mode, classes, iterations, smooth):
@@ -101,23 +121,65 @@ class _SoftClDice(torch.autograd.Function):
         return grad, None, None, None, None, None, None
 
 
+class _SoftClDice3d(torch.autograd.Function):
+    """``ptb_soft_cldice_3d_fwd`` / ``ptb_soft_cldice_3d_bwd``.  x fp32 ``[B, C, D, H, W]``; labels int64 ``[B, D, H, W]`` or dense fp32 like x.  When a
+    gradient is wanted the workspace holds the two level stores and is saved; the backward uses it up, so a second backward raises."""
+
+    @staticmethod
+    def forward(ctx, x, labels, dense, cls, prob, iterations, smooth, keep):
+        B, C, D, H, W = x.shape
+        Kn = len(cls)
+        dev = x.device
+        keep = int(keep)                                                     # (the caller's grad mode: needs_input_grad does not know torch.no_grad())
+        nbytes = int(N.load().ptb_soft_cldice_3d_workspace(B, Kn, D, H, W, iterations, keep))
+        if nbytes < 0:
+            N.check(nbytes, "soft_cldice_loss")
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        st = torch.empty((B, Kn, D, H, W), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        coef = torch.empty((Kn, 3), dtype=torch.float32, device=dev)
+        N.launch("ptb_soft_cldice_3d_fwd", dev, x.data_ptr(), N.ptr(labels), N.ptr(dense), B, C, D, H, W, N.int_array(cls), Kn, prob, iterations, smooth,
+                 keep, st.data_ptr(), ws.data_ptr(), 8 * ws.numel(), loss.data_ptr(), coef.data_ptr(), what="soft_cldice_loss")
+        if keep:
+            ctx.save_for_backward(x, labels, dense, st, coef, ws)
+            ctx.cfg = (cls, prob, iterations)
+            ctx.spent = False
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, labels, dense, st, coef, ws = ctx.saved_tensors
+        cls, prob, iterations = ctx.cfg
+        if ctx.spent:
+            raise RuntimeError("soft_cldice_loss (backward): dims=3 keeps its levels in a workspace the first backward overwrites, so a second backward "
+                               "(retain_graph=True included, unlike dims=2) needs the forward again")
+        ctx.spent = True
+        B, C, D, H, W = x.shape
+        up = g.to(torch.float32).reshape(1).contiguous()                     # the upstream scalar stays on the device
+        grad = torch.empty_like(x)
+        N.launch("ptb_soft_cldice_3d_bwd", x.device, x.data_ptr(), N.ptr(labels), N.ptr(dense), B, C, D, H, W, N.int_array(cls), len(cls), prob, iterations,
+                 st.data_ptr(), coef.data_ptr(), up.data_ptr(), ws.data_ptr(), 8 * ws.numel(), grad.data_ptr(), what="soft_cldice_loss (backward)")
+        return grad, None, None, None, None, None, None, None
+
+
 def soft_cldice_loss(y_pred: Tensor, y_true: Tensor, mode: str, classes: Optional[List[int]] = None, iterations: int = 3, smooth: float = 1.0,
-                     from_logits: bool = True) -> Tensor:
-    """The soft-clDice loss of the module docstring as a 0-dim float32 tensor.  ``y_pred``: ``[B, C, H, W]`` in fp32, fp16 or bf16 (widened first);
-    ``y_true``: integer labels ``[B, H, W]`` for ``mode="multiclass"`` (softmax), dense ``[B, C, H, W]`` (``[B, 1, H, W]`` for ``"binary"``) otherwise
-    (sigmoid); ``from_logits=False``: ``y_pred`` already holds probabilities.  ``classes``: the channels that count (default: all)."""
+                     from_logits: bool = True, dims: int = 2) -> Tensor:
+    """The soft-clDice loss of the module docstring as a 0-dim float32 tensor.  ``y_pred``: ``[B, C, H, W]`` (``dims=3``: ``[B, C, D, H, W]``) in fp32, fp16 or
+    bf16 (widened first); ``y_true``: integer labels ``[B, (D,) H, W]`` for ``mode="multiclass"`` (softmax), dense like ``y_pred`` (one channel for
+    ``"binary"``) otherwise (sigmoid); ``from_logits=False``: ``y_pred`` already holds probabilities.  ``classes``: the channels that count (default: all)."""
     what = "soft_cldice_loss"
     classes, iterations, smooth = _check_config(what, mode, classes, iterations, smooth)
+    dims = _check_dims(what, dims)
     if not isinstance(y_pred, torch.Tensor) or not isinstance(y_true, torch.Tensor):
         raise TypeError(f"{what}: y_pred and y_true must be tensors")
     if y_pred.dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise TypeError(f"{what}: y_pred must be float32, float16 or bfloat16, got {y_pred.dtype}")
-    if y_pred.dim() == 5:
-        raise NotImplementedError(f"{what}: 3-D volumes are not supported (a fused 3-D halo does not fit LDS); got {tuple(y_pred.shape)}")
-    if y_pred.dim() != 4:
-        raise ValueError(f"{what}: y_pred must be [B, C, H, W], got {tuple(y_pred.shape)}")
-    B, C, H, W = y_pred.shape
-    if B * C * H * W == 0:
+    if dims == 2 and y_pred.dim() == 5:
+        raise NotImplementedError(f"{what}: 3-D volumes take dims=3 (the default dims=2 reads [B, C, H, W]); got {tuple(y_pred.shape)}")
+    if y_pred.dim() != dims + 2:
+        raise ValueError(f"{what}: y_pred must be [B, C, {'D, ' if dims == 3 else ''}H, W] for dims={dims}, got {tuple(y_pred.shape)}")
+    B, C, *space = y_pred.shape
+    if y_pred.numel() == 0:
         raise ValueError(f"{what}: empty prediction of shape {tuple(y_pred.shape)}")
     if mode == BINARY_MODE and C != 1:
         raise ValueError(f"{what}: mode='binary' takes one channel, got {C}")
@@ -129,23 +191,26 @@ def soft_cldice_loss(y_pred: Tensor, y_true: Tensor, mode: str, classes: Optiona
     x = y_pred.float().contiguous()
     labels = dense = None
     if mode == MULTICLASS_MODE:
-        if y_true.is_floating_point() or tuple(y_true.shape) != (B, H, W):
-            raise ValueError(f"{what}: a multiclass target holds integer labels [B, H, W]; got {y_true.dtype} {tuple(y_true.shape)} for {tuple(y_pred.shape)}")
+        if y_true.is_floating_point() or tuple(y_true.shape) != (B, *space):
+            raise ValueError(f"{what}: a multiclass target holds integer labels [B, {'D, ' if dims == 3 else ''}H, W]; got {y_true.dtype} {tuple(y_true.shape)} "
+                             f"for {tuple(y_pred.shape)}")
         labels = y_true.to(torch.int64).contiguous()
         prob = K.PROB_SOFTMAX if from_logits else K.PROB_IDENTITY
     else:
-        if y_true.numel() != B * C * H * W:
+        if y_true.numel() != y_pred.numel():
             raise ValueError(f"{what}: target shape {tuple(y_true.shape)} does not match prediction shape {tuple(y_pred.shape)}")
-        dense = y_true.detach().float().contiguous().reshape(B, C, H, W)
+        dense = y_true.detach().float().contiguous().reshape(x.shape)
         prob = K.PROB_SIGMOID if from_logits else K.PROB_IDENTITY
     if not x.is_cuda:
         p = torch.softmax(x, dim=1) if prob == K.PROB_SOFTMAX else torch.sigmoid(x) if prob == K.PROB_SIGMOID else x
-        g = dense[:, cls] if labels is None else (labels.unsqueeze(1) == torch.tensor(cls, dtype=torch.int64).reshape(1, -1, 1, 1)).to(p.dtype)
+        g = dense[:, cls] if labels is None else (labels.unsqueeze(1) == torch.tensor(cls, dtype=torch.int64).reshape(1, -1, *([1] * dims))).to(p.dtype)
         return _host.soft_cldice(p[:, cls], g, iterations, smooth).to(torch.float32)
     if iterations > _softskel.MAX_ITERATIONS:
         raise _softskel.over_cap(what, iterations)
     if len(cls) > MAX_CLASSES:
         raise NotImplementedError(f"{what}: {len(cls)} selected classes; the HIP kernels take at most {MAX_CLASSES} (name fewer in classes=)")
+    if dims == 3:                                                            # no level store under torch.no_grad() or without a gradient on the prediction
+        return _SoftClDice3d.apply(x, labels, dense, tuple(cls), prob, iterations, smooth, torch.is_grad_enabled() and x.requires_grad)
     return _SoftClDice.apply(x, labels, dense, tuple(cls), prob, iterations, smooth)
 
 
@@ -157,11 +222,15 @@ class SoftClDiceLoss(_Loss):
     softmax) or ``"multilabel"`` (dense targets ``[B, C, H, W]``, sigmoid).  ``classes``: the channels that count (usually the foreground:
     ``classes=[1, ..., C - 1]``).  ``iterations``: the steps of the soft skeleton, about the largest half-width of the structures in
     positions; at most 8 on CUDA tensors.  ``smooth``: added to all four sums.  ``from_logits=False``: ``y_pred`` already holds probabilities.
+    ``dims=3``: volumes -- logits ``[B, C, D, H, W]``, labels ``[B, D, H, W]``, ``E`` over the 6 face neighbours and ``D`` over the 3 x 3 x 3 window.
     The published training loss is ``(1 - alpha) DiceLoss + alpha SoftClDiceLoss``; add ``DiceLoss`` yourself."""
 
-    def __init__(self, mode: str, classes: Optional[List[int]] = None, iterations: int = 3, smooth: float = 1.0, from_logits: bool = True):
+    def __init__(self, mode: str, classes: Optional[List[int]] = None, iterations: int = 3, smooth: float = 1.0, from_logits: bool = True,
+                 dims: int = 2):
         classes, iterations, smooth = _check_config(type(self).__name__, mode, classes, iterations, smooth)
+        dims = _check_dims(type(self).__name__, dims)
         super().__init__()
+        self.dims = dims
         self.mode = mode
         self.classes = classes
         self.iterations = iterations
@@ -169,4 +238,4 @@ class SoftClDiceLoss(_Loss):
         self.from_logits = bool(from_logits)
 
     def forward(self, y_pred: Tensor, y_true: Tensor) -> Tensor:
-        return soft_cldice_loss(y_pred, y_true, self.mode, self.classes, self.iterations, self.smooth, self.from_logits)
+        return soft_cldice_loss(y_pred, y_true, self.mode, self.classes, self.iterations, self.smooth, self.from_logits, self.dims)
