@@ -1101,6 +1101,40 @@ int ptb_centerline_dice(const void* pred, int pred_elem_bytes, const void* truth
                         const int64_t* class_values, int K, int object_rule, int method, int64_t* counts, float* cldice, float* tprec,
                         float* tsens, int32_t* took, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Skeletons of volumes by 3-D thinning, and their centreline Dice (no counterpart in the reference) ---------------
+ * Positions are (z, y, x); positions outside the entry are background; the object is 26-connected, the background 6-connected; N26(p),
+ * N18(p), N6(p) are the usual punctured neighbourhoods.  p is SIMPLE (Bertrand & Malandain 1994) iff the object positions of N26(p) form
+ * exactly one 26-connected component and the background positions of N18(p) that a 6-path within N18(p) joins to a background member of
+ * N6(p) form exactly one 6-connected component (so there is such a member).  p is an END POINT iff N26(p) holds exactly one object
+ * position; a position with none is not simple and stays.  The SUBFIELD of p is (z & 1) * 4 + (y & 1) * 2 + (x & 1), coordinates within
+ * the entry: two positions of one subfield are never 26-adjacent.  One ITERATION is six DIRECTION PASSES in the order z-1, z+1, y-1, y+1,
+ * x-1, x+1; a pass first marks its CANDIDATES from the state at its start -- the object positions whose neighbour in the pass's direction
+ * is background -- and then runs eight SUB-STEPS, subfield 0 to 7: sub-step f deletes every candidate of subfield f that is simple and no
+ * end point in the state before that sub-step.  The decisions of a sub-step cannot see each other, so topology is kept by construction
+ * and no order or tie rule enters the result.  THE SKELETON and THE ITERATION COUNT as above.
+ *   ptb_thin3d_rule      HOST ONLY, no stream, no GPU: 1 iff a position whose neighbourhood is code26 is simple and no end point, as the
+ *                        kernel evaluates it.  The cube around p is 27 bits, bit n = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); code26 is
+ *                        the cube without p's bit 13 (the bits above it one place lower); bits above 26 are ignored.
+ *   ptb_thin3d_geometry  HOST ONLY: out[5] = the brick a workgroup owns (z, y, x extents), its halo in z and y, and the direction
+ *                        passes of one launch (6 / passes launches make an iteration).
+ *   ptb_skeleton3d       as ptb_skeleton on labels [B, D, H, W] (out likewise); the guard is D + H + W iterations; max_iterations cuts
+ *                        between whole iterations.
+ *   ptb_centerline_dice3d  as ptb_centerline_dice on [B, D, H, W] maps.
+ * STATE: the bit planes above with D * H rows an entry.  Launches on `stream`: the pack kernel, LAUNCHES of the 3-D thinning kernel --
+ * a workgroup holds its brick with the halo (one whole word in x) and the candidate bits of the pass in LDS and runs `passes` direction
+ * passes there, in place; a tile runs iff it or one of its 26 neighbours changed in one of the 6 / passes launches before, and the call
+ * has converged when that many launches in a row changed nothing --, then unpack or count and finish.  Read-backs, the synchronisation of
+ * the stream, determinism and the codes are those above.  workspace: as above with D * H for H, per brick 12 bytes, and 16 more. */
+int ptb_thin3d_rule(uint32_t code26);
+int ptb_thin3d_geometry(int32_t* out);
+int ptb_skeleton3d_plan(int64_t B, int64_t D, int64_t H, int64_t W, int64_t* workspace_bytes);
+int ptb_skeleton3d(const void* labels, int elem_bytes, int64_t B, int64_t D, int64_t H, int64_t W, int object_rule, int64_t value, int64_t max_iterations,
+                   void* out, int32_t* took, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+int ptb_centerline_dice3d_plan(int64_t B, int64_t D, int64_t H, int64_t W, int K, int64_t* workspace_bytes);
+int ptb_centerline_dice3d(const void* pred, int pred_elem_bytes, const void* truth, int truth_elem_bytes, int64_t B, int64_t D, int64_t H, int64_t W,
+                          const int64_t* class_values, int K, int object_rule, int64_t* counts, float* cldice, float* tprec, float* tsens, int32_t* took,
+                          void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+
 /* ---- Soft skeleton and the soft-clDice training loss (no counterpart in the reference; Shit et al., CVPR 2021) -------
  * For one plane x of H x W values in [0, 1] and k = iterations: E(x)(p) = the minimum of x over p and its 4 edge neighbours inside the
  * plane, D(x)(p) = the maximum over the 3 x 3 window inside the plane; positions outside the plane never take part.

@@ -282,12 +282,13 @@ struct RelaxPlan {
     long long off_gate, off_start, off_flags, bytes;
 };
 
-static inline int relax_plan(int dims, long long B, long long D, long long H, long long W, RelaxPlan& p) {
+// the plan over tiles of TA x TB x TX positions: RelaxTile's for relax_tile, a unit's own for a kernel with a tile of its own (the 3-D thinning)
+static inline int relax_plan_tiles(int dims, long long B, long long D, long long H, long long W, int TA, int TB, int TX, RelaxPlan& p) {
     if (int rc = check_shape(dims, B, D, H, W)) return rc;
     RelaxGeom& g = p.g;
     p.dims = dims; p.B = B; g.W = (int)W;
     g.EA = dims == 2 ? (int)H : (int)D; g.EB = dims == 2 ? 1 : (int)H;
-    g.TA = dims == 2 ? RelaxTile<2>::A : RelaxTile<3>::A; g.TB = dims == 2 ? RelaxTile<2>::B : RelaxTile<3>::B; g.TX = dims == 2 ? RelaxTile<2>::X : RelaxTile<3>::X;
+    g.TA = TA; g.TB = TB; g.TX = TX;
     g.nta = (g.EA + g.TA - 1) / g.TA; g.ntb = (g.EB + g.TB - 1) / g.TB; g.ntx = (g.W + g.TX - 1) / g.TX;
     g.per_entry = (unsigned)(D * H * W); p.total = B * D * H * W;
     g.tiles_per_entry = (unsigned)((long long)g.nta * g.ntb * g.ntx); p.tiles = B * g.tiles_per_entry;        // (a tile holds a position: tiles <= total)
@@ -297,6 +298,11 @@ static inline int relax_plan(int dims, long long B, long long D, long long H, lo
     p.off_flags = o; o += 2 * up16(4 * p.tiles);
     p.bytes = o;
     return PTB_OK;
+}
+
+static inline int relax_plan(int dims, long long B, long long D, long long H, long long W, RelaxPlan& p) {
+    return dims == 2 ? relax_plan_tiles(dims, B, D, H, W, RelaxTile<2>::A, RelaxTile<2>::B, RelaxTile<2>::X, p)
+                     : relax_plan_tiles(dims, B, D, H, W, RelaxTile<3>::A, RelaxTile<3>::B, RelaxTile<3>::X, p);
 }
 
 static inline int relax_hip(hipError_t e) {
@@ -323,9 +329,10 @@ static inline int relax_flags(char* ws, const RelaxPlan& p, hipStream_t st, Rela
 
 // One phase: launch(k, prev, cur) enqueues sweep k, which reads the tile flags prev and writes cur, until a sweep changes nothing.
 // `sweeps` gets the number of sweeps that ran: 1 + the last one that changed something, or max_sweeps with PTB_ENOTCONVERGED; it is
-// left alone when a launch or a HIP call fails.
+// left alone when a launch or a HIP call fails.  `quiet`: the sweeps in a row that must change nothing before the phase has ended (1, but
+// for a kernel whose sweeps take turns at different work: the 3-D thinning's direction passes).
 template <class Launch>
-static inline int relax_sweeps(unsigned* gate, const RelaxFlags& f, int max_sweeps, hipStream_t st, int& sweeps, Launch&& launch) {
+static inline int relax_sweeps(unsigned* gate, const RelaxFlags& f, int max_sweeps, hipStream_t st, int& sweeps, Launch&& launch, int quiet = 1) {
     int done = 0;
     for (;;) {                                                                 // (each trip launches at least one sweep: at most max_sweeps trips)
         const int n = std::min(RELAX_BATCH, max_sweeps - done);
@@ -335,8 +342,8 @@ static inline int relax_sweeps(unsigned* gate, const RelaxFlags& f, int max_swee
         unsigned last = 0;                                                     // 1 + the last sweep that changed something
         if (int rc = relax_hip(hipMemcpyAsync(&last, gate, sizeof(last), hipMemcpyDeviceToHost, st))) return rc;
         if (int rc = relax_hip(hipStreamSynchronize(st))) return rc;
-        if (last < (unsigned)done) {                                           // sweep `last` ran and changed nothing
-            sweeps = (int)last + 1;
+        if (last + (unsigned)quiet <= (unsigned)done) {                        // sweeps `last` .. `last + quiet - 1` ran and changed nothing
+            sweeps = (int)last + quiet;
             return PTB_OK;
         }
         if (done >= max_sweeps) {

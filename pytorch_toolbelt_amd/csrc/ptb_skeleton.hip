@@ -29,6 +29,7 @@
 #include "ptb_common.h"
 #include "ptb_dispatch.h"
 #include "ptb_relax_device.h"
+#include "ptb_skeleton_device.h"
 #include "ptb_thin_device.h"
 
 namespace ptb {
@@ -38,8 +39,6 @@ namespace ptb {
 #endif
 constexpr int THIN_STEPS = PTB_THIN_STEPS;
 static_assert(THIN_STEPS % 2 == 0 && THIN_STEPS >= 2 && THIN_STEPS <= 32, "both kinds of sub-iteration in every launch; the halo is one word wide");
-constexpr int SK_THREADS = RELAX_THREADS;
-constexpr int SK_MAX_CLASSES = 32;
 
 struct ThinLds {
     static constexpr int ROWS = RelaxTile<2>::A + 2 * THIN_STEPS, WORDS = RelaxTile<2>::X / 32 + 2, CELLS = ROWS * WORDS;
@@ -48,60 +47,14 @@ struct ThinLds {
 };
 
 // ---------------------------------------------------------------------------------------------------------- pack
-struct SkPackArgs {
-    const void* labels;         // [B, H, W]
-    unsigned* a;                // the two thinning planes and (or NULL) the mask plane: [planes, H, WW] each
-    unsigned* b;
-    unsigned* v;
-    unsigned* start_flags;      // [planes * tiles_per_entry] zeroed by the caller
-    long long values[SK_MAX_CLASSES];
-    unsigned held;              // bit k: the element type holds values[k] (else it occurs nowhere)
-    int K, not_equal;           // the object of class k: labels == values[k], or (K == 1) labels != values[0]
-    unsigned plane0;            // plane of (entry b, class k) = plane0 + b * K + k
-    unsigned words;             // B * H * WW
-    int H, W, WW;
-    RelaxGeom g;
+// (SkPackArgs and the body: ptb_skeleton_device.h.)  A tile is 64 rows of 2 words.
+struct SkTile2 {
+    __device__ __forceinline__ unsigned operator()(const SkPackArgs& a, unsigned y, unsigned w) const { return (y / (unsigned)a.g.TA) * (unsigned)a.g.ntx + w / 2u; }
 };
 
 template <int EB, bool WIDE>
 __global__ __launch_bounds__(SK_THREADS) void sk_pack_kernel(const SkPackArgs a) {
-    using T = label_t<EB>;
-    const unsigned idx = blockIdx.x * (unsigned)SK_THREADS + threadIdx.x;
-    if (idx >= a.words) return;
-    const unsigned w = idx % (unsigned)a.WW, row = idx / (unsigned)a.WW, y = row % (unsigned)a.H, e = row / (unsigned)a.H;
-    const int x0 = (int)w * 32;
-    const T* src = reinterpret_cast<const T*>(a.labels) + (size_t)row * (size_t)a.W + (size_t)x0;
-    T el[32];
-    if constexpr (WIDE) {                                                      // the base and every row are 16-byte aligned, W is whole chunks
-        constexpr int CH = 16 / EB;
-#pragma unroll
-        for (int c = 0; c < 32 / CH; ++c) {
-#pragma unroll
-            for (int j = 0; j < CH; ++j) el[c * CH + j] = (T)0;
-            if (x0 + c * CH < a.W) __builtin_memcpy(&el[c * CH], __builtin_assume_aligned(src + c * CH, 16), 16);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) el[j] = x0 + j < a.W ? src[j] : (T)0;
-    }
-    const int n = min(32, a.W - x0);
-    const unsigned valid = n == 32 ? 0xFFFFFFFFu : (1u << n) - 1u;             // bits at columns >= W are 0
-    const unsigned tile = ((y / (unsigned)a.g.TA) * (unsigned)a.g.ntx + w / 2u);
-    for (int k = 0; k < a.K; ++k) {
-        const T val = (T)a.values[k];
-        unsigned m = 0u;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) m |= (el[j] == val ? 1u : 0u) << j;
-        if (!(a.held >> k & 1u)) m = 0u;
-        if (a.not_equal) m = ~m;
-        m &= valid;
-        const unsigned plane = a.plane0 + e * (unsigned)a.K + (unsigned)k;
-        const size_t at = (size_t)plane * ((size_t)a.H * (size_t)a.WW) + (size_t)y * (size_t)a.WW + w;
-        a.a[at] = m;
-        a.b[at] = m;
-        if (a.v) a.v[at] = m;
-        if (m) a.start_flags[plane * a.g.tiles_per_entry + tile] = 1u;          // (every writer stores the same value)
-    }
+    sk_pack_body<EB, WIDE>(a, SkTile2{});
 }
 
 // ---------------------------------------------------------------------------------------------------------- thin
@@ -255,38 +208,18 @@ __global__ __launch_bounds__(SK_THREADS) void sk_finish_kernel(const unsigned lo
 }
 
 // ---------------------------------------------------------------------------------------------------------- host side
-// The workspace: the sweep words and tile flags (RelaxPlan), then the planes A and B and, for clDice, the masks: 4 H WW bytes per plane.
-struct SkPlan : RelaxPlan {
-    long long planes, WW, plane_words, off_a, off_b, off_v;
-};
-
+// (SkPlan and the layout of the planes: ptb_skeleton_device.h)
 static int sk_plan(long long planes, long long H, long long W, bool masks, SkPlan& p) {
     if (int rc = relax_plan(2, planes, 1, H, W, p)) return rc;
-    p.planes = planes; p.WW = (W + 31) / 32; p.plane_words = H * p.WW;
-    const long long bytes = up16(4 * planes * p.plane_words);
-    p.off_a = p.bytes; p.bytes += bytes;
-    p.off_b = p.bytes; p.bytes += bytes;
-    p.off_v = masks ? p.bytes : -1;
-    if (masks) p.bytes += bytes;
+    sk_plan_planes(planes, H, W, masks, p);
     return PTB_OK;
 }
 
 static void sk_pack(const void* labels, int elem_bytes, long long B, int K, const int64_t* values, int not_equal, unsigned plane0, const SkPlan& p,
                     char* ws, const RelaxFlags& f, hipStream_t st) {
-    SkPackArgs a{};
-    a.labels = labels;
-    a.a = reinterpret_cast<unsigned*>(ws + p.off_a); a.b = reinterpret_cast<unsigned*>(ws + p.off_b);
-    a.v = p.off_v >= 0 ? reinterpret_cast<unsigned*>(ws + p.off_v) : nullptr;
-    a.start_flags = f.start;
-    for (int k = 0; k < K; ++k) {
-        a.values[k] = values[k];
-        if (holds(elem_bytes, values[k])) a.held |= 1u << k;
-    }
-    a.K = K; a.not_equal = not_equal; a.plane0 = plane0;
-    a.words = (unsigned)(B * p.plane_words);
-    a.H = p.g.EA; a.W = p.g.W; a.WW = (int)p.WW; a.g = p.g;
-    const bool wide = aligned16(labels) && ((long long)a.W * elem_bytes) % 16 == 0;
-    const unsigned blocks = (a.words + SK_THREADS - 1) / SK_THREADS;
+    bool wide;
+    unsigned blocks;
+    const SkPackArgs a = sk_pack_args(labels, elem_bytes, B, K, values, not_equal, plane0, p, p.g.EA, ws, f, wide, blocks);
     with_value<1, 2, 4, 8>(elem_bytes, [&](auto eb) {
         with_bool(wide, [&](auto wd) {
             hipLaunchKernelGGL((sk_pack_kernel<eb(), wd()>), dim3(blocks), dim3(SK_THREADS), 0, st, a);
@@ -335,6 +268,20 @@ static int sk_thin(const SkPlan& p, char* ws, const RelaxFlags& f, int method, l
 
 static bool sk_bad_method(int method) { return method != PTB_THIN_ZHANG && method != PTB_THIN_GUO_HALL; }
 
+void sk_unpack(const unsigned* plane, void* out, unsigned words, long long W, long long WW, hipStream_t st) {
+    with_bool(W % 16 == 0, [&](auto wd) {
+        hipLaunchKernelGGL((sk_unpack_kernel<wd()>), dim3((words + SK_THREADS - 1) / SK_THREADS), dim3(SK_THREADS), 0, st, plane, reinterpret_cast<unsigned char*>(out), words,
+                           (int)W, (int)WW);
+    });
+}
+
+void sk_count_finish(const unsigned* skel, const unsigned* mask, long long planes, long long plane_words, unsigned BK, int64_t* counts, float* cldice, float* tprec,
+                     float* tsens, hipStream_t st) {
+    const unsigned blocks = (unsigned)std::min<long long>((plane_words + SK_THREADS - 1) / SK_THREADS, std::max<long long>(1, std::min<long long>(1024, (1LL << 30) / planes)));
+    hipLaunchKernelGGL(sk_count_kernel, dim3(blocks * 2u * BK), dim3(SK_THREADS), 0, st, skel, mask, reinterpret_cast<unsigned long long*>(counts), (unsigned)plane_words, BK, blocks);
+    hipLaunchKernelGGL(sk_finish_kernel, dim3(1), dim3(SK_THREADS), 0, st, reinterpret_cast<const unsigned long long*>(counts), cldice, tprec, tsens, BK);
+}
+
 }  // namespace ptb
 
 using namespace ptb;
@@ -371,11 +318,7 @@ extern "C" int ptb_skeleton(const void* labels, int elem_bytes, int64_t B, int64
     sk_pack(labels, elem_bytes, B, 1, &value, object_rule == PTB_THIN_NOT_EQUAL, 0u, p, ws, f, st);
     int final_plane = 0;
     if (int rc = sk_thin(p, ws, f, method, max_iterations, st, took, final_plane)) return rc;
-    const unsigned words = (unsigned)(B * p.plane_words);
-    with_bool(W % 16 == 0, [&](auto wd) {
-        hipLaunchKernelGGL((sk_unpack_kernel<wd()>), dim3((words + SK_THREADS - 1) / SK_THREADS), dim3(SK_THREADS), 0, st,
-                           reinterpret_cast<const unsigned*>(ws + (final_plane ? p.off_b : p.off_a)), reinterpret_cast<unsigned char*>(out), words, (int)W, (int)p.WW);
-    });
+    sk_unpack(reinterpret_cast<const unsigned*>(ws + (final_plane ? p.off_b : p.off_a)), out, (unsigned)(B * p.plane_words), W, p.WW, st);
     return check_launch();
 }
 
@@ -411,9 +354,7 @@ extern "C" int ptb_centerline_dice(const void* pred, int pred_elem_bytes, const 
     sk_pack(truth, truth_elem_bytes, B, K, class_values, not_equal, BK, p, ws, f, st);
     int final_plane = 0;
     if (int rc = sk_thin(p, ws, f, method, -1, st, took, final_plane)) return rc;
-    const unsigned blocks = (unsigned)std::min<long long>((p.plane_words + SK_THREADS - 1) / SK_THREADS, std::max<long long>(1, std::min<long long>(1024, (1LL << 30) / p.planes)));
-    hipLaunchKernelGGL(sk_count_kernel, dim3(blocks * 2u * BK), dim3(SK_THREADS), 0, st, reinterpret_cast<const unsigned*>(ws + (final_plane ? p.off_b : p.off_a)),
-                       reinterpret_cast<const unsigned*>(ws + p.off_v), reinterpret_cast<unsigned long long*>(counts), (unsigned)p.plane_words, BK, blocks);
-    hipLaunchKernelGGL(sk_finish_kernel, dim3(1), dim3(SK_THREADS), 0, st, reinterpret_cast<const unsigned long long*>(counts), cldice, tprec, tsens, BK);
+    sk_count_finish(reinterpret_cast<const unsigned*>(ws + (final_plane ? p.off_b : p.off_a)), reinterpret_cast<const unsigned*>(ws + p.off_v), p.planes, p.plane_words, BK, counts,
+                    cldice, tprec, tsens, st);
     return check_launch();
 }

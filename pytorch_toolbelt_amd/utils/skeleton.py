@@ -7,9 +7,10 @@ structures of the label-map chain (roads, vessels, neurites, cracks, membranes),
 
 The reference has no counterpart, so the names and meanings below are this library's.  CUDA tensors run the HIP kernels of
 ``csrc/ptb_skeleton.hip`` (a missing kernel is an error, never a silent host computation), CPU tensors take the host form below with the
-same bits -- the device the caller names decides.
+same bits -- the device the caller names decides.  ``dims=3`` thins volumes ``[*stack, D, H, W]`` (``csrc/ptb_skeleton3d.hip``; definitions further down);
+``dims=2``, the default, thins planes, and a 3-D tensor is then a stack of planes.
 
-DEFINITIONS (the published papers are the source; these formulae are the definition).  The neighbours of a position P1 = ``(y, x)``::
+DEFINITIONS, ``dims=2`` (the published papers are the source; these formulae are the definition).  The neighbours of a position P1 = ``(y, x)``::
 
     P9 (y-1, x-1)   P2 (y-1, x)   P3 (y-1, x+1)
     P8 (y,   x-1)   P1            P4 (y,   x+1)
@@ -30,7 +31,23 @@ THE SKELETON is the state after the first iteration that deletes nothing; with `
 (``n = 0``: the object mask).  THE ITERATION COUNT is the number of iterations that deleted something.  ``zhang`` deletes a 2 x 2 square
 entirely (and so can lose a component); ``guo_hall`` keeps one position of it.
 
-Left out: 3-D thinning (Lee 1994 / Palagyi; there is no ``dims`` argument yet), the medial axis with distances (compose it as
+DEFINITIONS, ``dims=3`` (``method="subfield"``, the only one and the default there; Bertrand & Malandain 1994 for "simple").  Positions are ``(z, y, x)``;
+positions outside the entry are background; the object is 26-connected and the background 6-connected; N26(p), N18(p) and N6(p) are the
+usual punctured neighbourhoods of p.
+
+* ``p`` is SIMPLE iff the object positions in N26(p) form exactly one 26-connected component, and the background positions in N18(p) that a
+  6-path within N18(p) joins to a background member of N6(p) form exactly one 6-connected component (so there is such a member).
+* ``p`` is an END POINT iff it has exactly one object position in N26(p).  A position with none is not simple, so it stays.
+* The SUBFIELD of p is ``(z & 1) * 4 + (y & 1) * 2 + (x & 1)``, coordinates within the entry.  Two positions of one subfield are never 26-adjacent.
+* One ITERATION is six DIRECTION PASSES, in the order ``z-1, z+1, y-1, y+1, x-1, x+1``.  A pass first marks its CANDIDATES from the state at the
+  start of the pass: the object positions whose neighbour in the pass's direction is background.  It then runs eight SUB-STEPS, subfield 0 to
+  7: sub-step ``f`` deletes every candidate of subfield ``f`` that is still simple and is not an end point in the state before that sub-step.
+  (Marking candidates once per pass keeps a pass from peeling two layers.)
+* Decisions inside one sub-step cannot see each other, so a sub-step equals deleting simple points one at a time: topology is preserved by
+  construction, and the result has no order or tie rule in it.
+* Skeleton, iteration count and ``max_iterations`` are as above; the guard of a run to stability is ``D + H + W`` iterations.
+
+Left out: surface skeletons, the template sets of Lee 1994 and of Palagyi, the medial axis with distances (compose it as
 ``skeletonize(m) * distance_transform(m)``), pruning of spurs and node / branch classification, and ``ignore_index``.  The
 soft-clDice training loss is ``losses.SoftClDiceLoss``.
 """
@@ -45,8 +62,10 @@ from . import _maps as M
 __all__ = ["skeletonize", "centerline_dice"]
 
 _METHODS = {"zhang": 0, "guo_hall": 1}          # PTB_THIN_*
+_SUBFIELD = "subfield"                          # the method of dims=3
 _EQUAL, _NOT_EQUAL = 0, 1                       # PTB_THIN_EQUAL / PTB_THIN_NOT_EQUAL
 STEPS = 32                                      # THIN_STEPS of csrc/ptb_skeleton.hip: the sub-iterations of one launch
+BRICK, HALO, PASSES = (16, 16, 64), 9, 1         # csrc/ptb_skeleton3d.hip (ptb_thin3d_geometry): the brick of a workgroup (z, y, x), its halo, the direction passes of a launch
 MAX_CLASSES = 32
 DEFAULT_WORKSPACE_BYTES = 4 << 30
 
@@ -91,6 +110,95 @@ def _thin_host(s, method, max_iterations):
     return s, done
 
 
+# the 27-bit cube of a neighbourhood, bit n = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); the 26-bit code leaves the centre's bit 13 out
+_U = np.uint32
+_CUBE, _X0, _Y0 = 0x7FFFFFF, 0x1249249, 0x7 | 0x7 << 9 | 0x7 << 18
+_NOT_X0, _NOT_X2, _NOT_Y0, _NOT_Y2 = (_U(_CUBE & ~m) for m in (_X0, _X0 << 2, _Y0, _Y0 << 6))
+_N6 = _U(sum(1 << n for n in (4, 10, 12, 14, 16, 22)))
+_N18 = _U(_CUBE & ~sum(1 << n for n in (0, 2, 6, 8, 13, 18, 20, 24, 26)))
+_OFFSETS = [(n, n // 9 - 1, n // 3 % 3 - 1, n % 3 - 1) for n in range(27) if n != 13]
+_DIRECTIONS = ((1, -1), (1, 1), (2, -1), (2, 1), (3, -1), (3, 1))     # (axis of [B, D, H, W], step) of the six direction passes
+
+
+def _flood(seed, within, faces_only):
+    """the positions of the cubes ``within`` that the positions ``seed`` reach, all codes at once: dilate, mask, until nothing grows"""
+    reach = seed
+    for _ in range(27):
+        x = (reach << _U(1) & _NOT_X0) | (reach >> _U(1) & _NOT_X2)
+        if faces_only:
+            grown = reach | x | (reach << _U(3) & _NOT_Y0) | (reach >> _U(3) & _NOT_Y2) | reach << _U(9) | reach >> _U(9)
+        else:
+            grown = reach | x
+            grown = grown | (grown << _U(3) & _NOT_Y0) | (grown >> _U(3) & _NOT_Y2)
+            grown = grown | grown << _U(9) | grown >> _U(9)
+        grown &= within
+        if np.array_equal(grown, reach):
+            break
+        reach = grown
+    return reach
+
+
+def _deletable_host(codes):
+    """"simple and not an end point" of the 26-bit codes ``codes`` (uint32): the vectorised twin of thin3d_deletable"""
+    obj = (codes & _U(0x1FFF)) | (codes >> _U(13) & _U(0x1FFF)) << _U(14)
+    several = (obj & (obj - _U(1))) != 0                                       # none: not simple; one: an end point
+    one_object = _flood(obj & (~obj + _U(1)), obj, False) == obj
+    bg = _N18 & ~obj
+    faces = bg & _N6
+    one_background = (faces & ~_flood(faces & (~faces + _U(1)), bg, True)) == 0
+    return several & one_object & (faces != 0) & one_background
+
+
+def _decide(codes, memo):
+    """``_deletable_host`` of every code, each distinct code decided once per call of ``_thin3_host``: ``memo`` = [sorted codes, their answers]"""
+    u, inverse = np.unique(codes, return_inverse=True)
+    at = np.minimum(np.searchsorted(memo[0], u), max(len(memo[0]) - 1, 0))
+    known = memo[0][at] == u if len(memo[0]) else np.zeros(u.shape, bool)
+    if not known.all():
+        new = u[~known]
+        allc = np.concatenate([memo[0], new])
+        order = np.argsort(allc, kind="stable")
+        memo[0], memo[1] = allc[order], np.concatenate([memo[1], _deletable_host(new)])[order]
+        at = np.searchsorted(memo[0], u)
+    return memo[1][at][inverse.reshape(-1)]
+
+
+def _thin3_host(s, max_iterations):
+    """``(skeleton, iteration count)`` of the bool volumes ``s`` ``[B, D, H, W]``, all thinned together: the docstring's passes and sub-steps, the
+    neighbourhood codes of a sub-step's candidates gathered from a zero-padded copy"""
+    B, D, H, W = s.shape
+    padded = np.zeros((B, D + 2, H + 2, W + 2), bool)
+    padded[:, 1:-1, 1:-1, 1:-1] = s
+    s = padded[:, 1:-1, 1:-1, 1:-1]
+    memo = [np.zeros(0, _U), np.zeros(0, bool)]
+    done = 0
+    while max_iterations is None or done < max_iterations:
+        any_deleted = False
+        for axis, step in _DIRECTIONS:
+            window = [slice(None), slice(1, D + 1), slice(1, H + 1), slice(1, W + 1)]
+            window[axis] = slice(1 + step, 1 + step + s.shape[axis])
+            cand = s & ~padded[tuple(window)]
+            if not cand.any():
+                continue
+            for f in range(8):
+                sub = (slice(None), slice(f >> 2 & 1, None, 2), slice(f >> 1 & 1, None, 2), slice(f & 1, None, 2))
+                b, z, y, x = np.nonzero(cand[sub] & s[sub])
+                if not b.size:
+                    continue
+                z, y, x = 2 * z + (f >> 2 & 1), 2 * y + (f >> 1 & 1), 2 * x + (f & 1)
+                codes = np.zeros(b.shape, _U)
+                for n, dz, dy, dx in _OFFSETS:
+                    codes |= padded[b, z + 1 + dz, y + 1 + dy, x + 1 + dx].astype(_U) << _U(n - (n > 13))
+                go = _decide(codes, memo)
+                if go.any():
+                    any_deleted = True
+                    s[b[go], z[go], y[go], x[go]] = False
+        if not any_deleted:
+            break
+        done += 1
+    return s.copy(), done
+
+
 def _object_host(x, rule, value):
     """the object of a label map as a bool array; ``value``: None for one the dtype cannot hold"""
     a = x.numpy()
@@ -99,23 +207,32 @@ def _object_host(x, rule, value):
 
 
 # ---------------------------------------------------------------------------------------------------------------- public
-def _method(what, method):
+def _method(what, method, dims):
+    """the code of a 2-D method, None for the one of ``dims=3``; ``method=None``: the default of ``dims``"""
+    M.check_dims(what, dims)
+    if dims == 3:
+        if method not in (None, _SUBFIELD):
+            raise ValueError(f"{what}: method must be 'subfield' (or None) for dims=3, got {method!r}")
+        return None
+    if method is None:
+        method = "guo_hall"
     if method not in _METHODS:
         raise ValueError(f"{what}: method must be 'guo_hall' or 'zhang', got {method!r}")
     return _METHODS[method]
 
 
-def _not_converged(what, H, W, took):
-    raise RuntimeError(f"{what}: the thinning did not converge within the guard of H + W = {H + W} iterations: {int(took[1])} launches run")
+def _not_converged(what, D, H, W, took, dims):
+    guard = f"D + H + W = {D + H + W}" if dims == 3 else f"H + W = {H + W}"
+    raise RuntimeError(f"{what}: the thinning did not converge within the guard of {guard} iterations: {int(took[1])} launches run")
 
 
-def skeletonize(labels, background=0, foreground=None, method="guo_hall", max_iterations=None, out=None, return_iterations=False):
+def skeletonize(labels, background=0, foreground=None, method=None, max_iterations=None, out=None, return_iterations=False, dims=2):
     """The skeleton of the object of ``labels`` by parallel thinning (the module docstring's definitions), as a ``bool`` tensor of the input's shape.
 
-    ``labels``: ``[*stack, H, W]`` of ``bool``, ``uint8``, ``int16``, ``int32`` or ``int64``; the entries of ``stack`` are thinned independently, all in the same
-    launches.  The object is, with ``foreground=None``, the positions that do not hold ``background`` and, with ``foreground=c``, the positions that
+    ``labels``: ``[*stack, H, W]`` (``dims=3``: ``[*stack, D, H, W]``) of ``bool``, ``uint8``, ``int16``, ``int32`` or ``int64``; the entries of ``stack`` are thinned
+    independently, all in the same launches.  The object is, with ``foreground=None``, the positions that do not hold ``background`` and, with ``foreground=c``, the positions that
     hold ``c`` -- ``distance_transform``'s pair of arguments: one class of a multi-class map without making ``labels == c``.  A value the dtype
-    cannot hold occurs nowhere.  ``method``: ``"guo_hall"`` or ``"zhang"``.
+    cannot hold occurs nowhere.  ``method``: ``"guo_hall"`` (``None`` under ``dims=2``) or ``"zhang"``; under ``dims=3`` ``"subfield"`` (``None``).
 
     ``max_iterations=None`` runs to stability; ``n >= 0`` stops after at most ``n`` iterations (0 returns the object mask).  ``out``: a ``bool`` or ``uint8``
     tensor of the input's shape and device that receives the result (and is returned); it may be the input.  ``return_iterations=True``:
@@ -127,49 +244,59 @@ def skeletonize(labels, background=0, foreground=None, method="guo_hall", max_it
     iteration count), so THE CALL SYNCHRONISES ITS STREAM AND CANNOT BE CAPTURED into a graph.  Running to stability is guarded by
     ``H + W`` iterations; a call that gets there raises ``RuntimeError`` (the guard is not a claimed bound: the largest count seen is
     ``min(H, W) / 2``).  The result is a function of the input alone: the same bits on every run.  Bad arguments raise before anything is
-    launched; empty inputs return without a launch."""
+    launched; empty inputs return without a launch.
+
+    ``dims=3``: the same call on volumes.  The kernel of ``csrc/ptb_skeleton3d.hip`` holds a brick of ``BRICK`` positions with a halo of ``HALO`` in LDS and
+    runs ``PASSES`` direction pass(es) per launch, in place; a brick runs while it or a neighbour changed within the last ``6 / PASSES`` launches.  The
+    guard is ``D + H + W`` iterations.  CPU tensors: numpy, the neighbourhood codes of a sub-step's candidates decided once per distinct code."""
     what = "skeletonize"
     M.check_labels(what, "labels", labels)
-    _, B, _, H, W = M.extent(what, "labels", labels, 2)
+    code = _method(what, method, dims)
+    _, B, D, H, W = M.extent(what, "labels", labels, dims)
     background = M.check_int(what, "background", background, allow_none=True)
     foreground = M.check_int(what, "foreground", foreground, allow_none=True)
     if foreground is None and background is None:
         raise ValueError(f"{what}: background=None needs foreground= (there would be no object)")
     rule, value = (_NOT_EQUAL, background) if foreground is None else (_EQUAL, foreground)
-    code = _method(what, method)
     max_iterations = M.check_int(what, "max_iterations", max_iterations, allow_none=True)
     if max_iterations is not None and max_iterations < 0:
         raise ValueError(f"{what}: max_iterations must be None or >= 0, got {max_iterations}")
     M.check_out(what, out, out.dtype if isinstance(out, torch.Tensor) and out.dtype == torch.uint8 else torch.bool, labels)
     dev = labels.device
     iterations = 0
-    if B * H * W == 0:
+    if B * D * H * W == 0:
         res = out if out is not None else torch.empty(labels.shape, dtype=torch.bool, device=dev)
     elif not labels.is_cuda:
-        obj = _object_host(labels.contiguous().reshape(B, H, W), rule, value if M.fits(value, labels.dtype) else None)
-        skel, iterations = _thin_host(obj, code, max_iterations)
+        obj = _object_host(labels.contiguous().reshape((B, D, H, W) if dims == 3 else (B, H, W)), rule, value if M.fits(value, labels.dtype) else None)
+        skel, iterations = _thin3_host(obj, max_iterations) if dims == 3 else _thin_host(obj, code, max_iterations)
         res = torch.from_numpy(skel).reshape(labels.shape)
     else:
         x = labels.contiguous()
         res = out if M.direct_out(out, x) else torch.empty(x.shape, dtype=torch.bool, device=dev)
-        ws, nbytes = M.workspace(N.load().ptb_skeleton_plan, what, dev, B, H, W)
         took = (ctypes.c_int * 2)(0, 0)
-        rc = N.launch("ptb_skeleton", dev, x.data_ptr(), M.ELEM_BYTES[x.dtype], B, H, W, rule, value, code, -1 if max_iterations is None else max_iterations,
-                      res.data_ptr(), took, ws.data_ptr(), nbytes, raw=True)     # (a bool tensor's bytes are the uint8 the kernels write)
+        limit = -1 if max_iterations is None else max_iterations
+        if dims == 3:
+            ws, nbytes = M.workspace(N.load().ptb_skeleton3d_plan, what, dev, B, D, H, W)
+            rc = N.launch("ptb_skeleton3d", dev, x.data_ptr(), M.ELEM_BYTES[x.dtype], B, D, H, W, rule, value, limit, res.data_ptr(), took, ws.data_ptr(), nbytes, raw=True)
+        else:
+            ws, nbytes = M.workspace(N.load().ptb_skeleton_plan, what, dev, B, H, W)
+            rc = N.launch("ptb_skeleton", dev, x.data_ptr(), M.ELEM_BYTES[x.dtype], B, H, W, rule, value, code, limit,
+                          res.data_ptr(), took, ws.data_ptr(), nbytes, raw=True)     # (a bool tensor's bytes are the uint8 the kernels write)
         if rc == N.PTB_ENOTCONVERGED:
-            _not_converged(what, H, W, took)
+            _not_converged(what, D, H, W, took, dims)
         N.check(rc, what)
         iterations = int(took[0])
     res = M.finish_out(out, res)
     return (res, iterations) if return_iterations else res
 
 
-def _plan(what, B, H, W, K, cap):
+def _plan(what, B, H, W, K, cap, D=1, dims=2):
     """the workspace bytes of a ``centerline_dice`` call; the errors of a shape or a cap that cannot be served"""
-    if 2 * K * B * H * W > M.MAX_POSITIONS:
-        raise ValueError(f"{what}: 2 x {K} x {B * H * W} positions (both sides of every class) in one thinning run; at most 2^31 - 2 = {M.MAX_POSITIONS}: split the stack")
+    if 2 * K * B * D * H * W > M.MAX_POSITIONS:
+        raise ValueError(f"{what}: 2 x {K} x {B * D * H * W} positions (both sides of every class) in one thinning run; at most 2^31 - 2 = {M.MAX_POSITIONS}: split the stack")
     nbytes = ctypes.c_int64()
-    N.check(N.load().ptb_centerline_dice_plan(B, H, W, K, ctypes.byref(nbytes)), what)
+    lib = N.load()
+    N.check(lib.ptb_centerline_dice3d_plan(B, D, H, W, K, ctypes.byref(nbytes)) if dims == 3 else lib.ptb_centerline_dice_plan(B, H, W, K, ctypes.byref(nbytes)), what)
     if nbytes.value > cap:
         raise ValueError(f"{what}: the call needs a workspace of {nbytes.value} bytes, above max_workspace_bytes={cap}")
     return nbytes.value
@@ -188,9 +315,9 @@ def _ratios(counts):
     return d.astype(np.float32), p.astype(np.float32), s.astype(np.float32)
 
 
-def centerline_dice(pred, truth, labels=None, method="guo_hall", background=0, max_workspace_bytes=DEFAULT_WORKSPACE_BYTES):
-    """The centreline Dice (clDice, Shit et al., CVPR 2021) of two label maps ``pred`` and ``truth`` of one shape ``[*stack, H, W]`` on one device, each of a
-    label dtype of its own.  ``labels=None``: one object, the positions that do not hold ``background`` (K = 1).  Otherwise ``labels`` is a sequence of
+def centerline_dice(pred, truth, labels=None, method=None, background=0, max_workspace_bytes=DEFAULT_WORKSPACE_BYTES, dims=2):
+    """The centreline Dice (clDice, Shit et al., CVPR 2021) of two label maps ``pred`` and ``truth`` of one shape ``[*stack, H, W]`` (``dims=3``: ``[*stack, D, H, W]``,
+    skeletons by 3-D thinning, ``method`` as in ``skeletonize``) on one device, each of a label dtype of its own.  ``labels=None``: one object, the positions that do not hold ``background`` (K = 1).  Otherwise ``labels`` is a sequence of
     at most 32 class values.  With ``S`` the skeleton (``method``, run to stability) and ``V`` the mask of a class in each map::
 
         tprec = |S_P & V_T| / |S_P|        tsens = |S_T & V_P| / |S_T|        cldice = 2 tprec tsens / (tprec + tsens)
@@ -211,8 +338,8 @@ def centerline_dice(pred, truth, labels=None, method="guo_hall", background=0, m
         raise ValueError(f"{what}: pred and truth must have the same shape, got {tuple(pred.shape)} and {tuple(truth.shape)}")
     if pred.device != truth.device:
         raise ValueError(f"{what}: pred and truth must be on the same device, got {pred.device} and {truth.device}")
-    stack, B, _, H, W = M.extent(what, "pred and truth", pred, 2)
-    code = _method(what, method)
+    code = _method(what, method, dims)
+    stack, B, D, H, W = M.extent(what, "pred and truth", pred, dims)
     if labels is None:
         values, rule = [M.check_int(what, "background", background)], _NOT_EQUAL
     else:
@@ -228,28 +355,36 @@ def centerline_dice(pred, truth, labels=None, method="guo_hall", background=0, m
     if cap < 1:
         raise ValueError(f"{what}: max_workspace_bytes must be positive, got {cap}")
     dev = pred.device
-    if B * H * W == 0:
+    if B * D * H * W == 0:
         counts = torch.zeros(stack + (K, 4), dtype=torch.int64, device=dev)
         nan = torch.full(stack + (K,), float("nan"), dtype=torch.float32, device=dev)
         return {"cldice": nan, "tprec": nan.clone(), "tsens": nan.clone(), "counts": counts}
     if not pred.is_cuda:
-        masks = [np.stack([_object_host(t.contiguous().reshape(B, H, W), rule, v if M.fits(v, t.dtype) else None) for v in values], axis=1) for t in (pred, truth)]
-        both = np.stack(masks)                                                  # [2, B, K, H, W]
-        skel = _thin_host(both.reshape(-1, H, W), code, None)[0].reshape(both.shape)
-        counts = np.stack([(skel[0] & both[1]).sum((-1, -2)), skel[0].sum((-1, -2)), (skel[1] & both[0]).sum((-1, -2)), skel[1].sum((-1, -2))], axis=-1).astype(np.int64)
+        entry = (B, D, H, W) if dims == 3 else (B, H, W)
+        masks = [np.stack([_object_host(t.contiguous().reshape(entry), rule, v if M.fits(v, t.dtype) else None) for v in values], axis=1) for t in (pred, truth)]
+        both = np.stack(masks)                                                  # [2, B, K, (D,) H, W]
+        flat = both.reshape((-1,) + entry[1:])
+        skel = (_thin3_host(flat, None) if dims == 3 else _thin_host(flat, code, None))[0].reshape(both.shape)
+        over = tuple(range(-dims, 0))
+        counts = np.stack([(skel[0] & both[1]).sum(over), skel[0].sum(over), (skel[1] & both[0]).sum(over), skel[1].sum(over)], axis=-1).astype(np.int64)
         d, p, s = _ratios(counts)
         res = {"cldice": torch.from_numpy(d), "tprec": torch.from_numpy(p), "tsens": torch.from_numpy(s), "counts": torch.from_numpy(counts)}
     else:
-        nbytes = _plan(what, B, H, W, K, cap)
+        nbytes = _plan(what, B, H, W, K, cap, D, dims)
         x, y = pred.contiguous(), truth.contiguous()
         ws = M.scratch(nbytes, dev)
         counts = torch.empty((B, K, 4), dtype=torch.int64, device=dev)
         ratios = torch.empty((3, B, K), dtype=torch.float32, device=dev)
         took = (ctypes.c_int * 2)(0, 0)
-        rc = N.launch("ptb_centerline_dice", dev, x.data_ptr(), M.ELEM_BYTES[x.dtype], y.data_ptr(), M.ELEM_BYTES[y.dtype], B, H, W, N.i64_array(values), K, rule,
-                      code, counts.data_ptr(), ratios[0].data_ptr(), ratios[1].data_ptr(), ratios[2].data_ptr(), took, ws.data_ptr(), nbytes, raw=True)
+        tail = (counts.data_ptr(), ratios[0].data_ptr(), ratios[1].data_ptr(), ratios[2].data_ptr(), took, ws.data_ptr(), nbytes)
+        if dims == 3:
+            rc = N.launch("ptb_centerline_dice3d", dev, x.data_ptr(), M.ELEM_BYTES[x.dtype], y.data_ptr(), M.ELEM_BYTES[y.dtype], B, D, H, W, N.i64_array(values), K, rule,
+                          *tail, raw=True)
+        else:
+            rc = N.launch("ptb_centerline_dice", dev, x.data_ptr(), M.ELEM_BYTES[x.dtype], y.data_ptr(), M.ELEM_BYTES[y.dtype], B, H, W, N.i64_array(values), K, rule,
+                          code, *tail, raw=True)
         if rc == N.PTB_ENOTCONVERGED:
-            _not_converged(what, H, W, took)
+            _not_converged(what, D, H, W, took, dims)
         N.check(rc, what)
         res = {"cldice": ratios[0], "tprec": ratios[1], "tsens": ratios[2], "counts": counts}
     return {k: v.reshape(stack + (K, 4) if k == "counts" else stack + (K,)) for k, v in res.items()}
