@@ -1101,6 +1101,49 @@ int ptb_centerline_dice(const void* pred, int pred_elem_bytes, const void* truth
                         const int64_t* class_values, int K, int object_rule, int method, int64_t* counts, float* cldice, float* tprec,
                         float* tsens, int32_t* took, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
 
+/* ---- Grey and binary morphology with a flat structuring element (no counterpart in the reference) -------------------
+ * THE FOOTPRINT F has shape (fh, fw) and anchor (fh / 2, fw / 2); its offsets are O = {(i - fh / 2, j - fw / 2) : F[i, j]}, every one with
+ * |dy|, |dx| <= PTB_MORPH_REACH.  It arrives as its horizontal RUNS: runs HOST int32 [n_runs][3] = (dy, a, b), the maximal stretches of
+ * set columns a .. b of row dy, 1 <= n_runs <= PTB_MORPH_MAX_RUNS (PTB_EINVAL otherwise).
+ *   E(x)(p) = min over o in O of x(p + o);   D(x)(p) = max over o in O of x(p - o)  (the reflected footprint: scipy's convention);
+ *   opening = D o E, closing = E o D, gradient = D - E, white top-hat = x - opening, black top-hat = closing - x.
+ *   ptb_morphology   image, out [B, H, W] contiguous of dtype (PTB_F32, PTB_F16, PTB_BF16, PTB_U8, PTB_I16), B * H * W <= 2^31 - 2
+ *                    (PTB_EUNSUPPORTED above); out must not overlap image.  border = 0: positions outside the entry never take part, and a
+ *                    window that lies wholly outside gives the highest value of the type (+inf for floats) for E, the lowest for D;
+ *                    border = 1: they hold border_value (not a NaN; the caller sees to it that it is exact in dtype).  Values are compared
+ *                    as ordered 32-bit keys of their float32 value -- -0 counts as +0 and comes back as +0, a NaN with the sign bit clear
+ *                    lies above +inf and one with it set below -inf -- and only selected: results are exact.  The differences subtract in
+ *                    the type: integers saturate, floats take one float32 subtraction rounded once to nearest even.
+ *   ptb_binary_morphology   labels [B, H, W] of elem_bytes under object_rule / value as for ptb_skeleton (PTB_THIN_EQUAL | PTB_THIN_NOT_EQUAL);
+ *                    op: PTB_MORPH_EROSION .. PTB_MORPH_CLOSING.  border = -1: outside never takes part; 0 | 1: outside holds that.
+ *                    out [B, H, W] bytes 0 | 1; it must not overlap labels.
+ *   ptb_morphology_plan   the workspace of a call: 0 for a plain erosion or dilation; for the compound forms the intermediate, B * H * W
+ *                    elements of elem_bytes (1, 2, 4), or with elem_bytes = 0 (ptb_binary_morphology) a bit plane of 4 * ceil(W / 32)
+ *                    bytes a row; rounded up to 16.  workspace: DEVICE, 16-byte aligned (may be NULL when the plan says 0).
+ *   ptb_morphology_geometry   HOST ONLY: out[4] = the columns of a strip and the rows of a band of the grey walk, the owned words of a
+ *                    strip and the rows of a band of the bit-plane walk.
+ * Launches on `stream`: one walk per erosion or dilation, two for the compound forms, the differences in the store stage of the second.
+ * A workgroup owns a column strip of one entry and a band of its rows, walks the input rows of the band (and those the footprint reaches
+ * above and below it) once, builds the windowed minima of the levels 2^p the runs use along the row in LDS and folds every run into the
+ * accumulator row of the output row it belongs to, a ring of rows in LDS that is stored and reset when complete.  The binary walk does the
+ * same on bit planes with funnel shifts, the object rule packed from the labels in registers.  No atomics, no read-back: the calls are
+ * asynchronous and can be captured.  The result is a function of the inputs alone. */
+#define PTB_MORPH_REACH 31
+#define PTB_MORPH_MAX_RUNS 256
+#define PTB_MORPH_EROSION 0
+#define PTB_MORPH_DILATION 1
+#define PTB_MORPH_OPENING 2
+#define PTB_MORPH_CLOSING 3
+#define PTB_MORPH_GRADIENT 4
+#define PTB_MORPH_WHITE_TOPHAT 5
+#define PTB_MORPH_BLACK_TOPHAT 6
+int ptb_morphology_geometry(int32_t* out);
+int ptb_morphology_plan(int64_t B, int64_t H, int64_t W, int op, int elem_bytes, int64_t* workspace_bytes);
+int ptb_morphology(const void* image, int dtype, int64_t B, int64_t H, int64_t W, int op, const int32_t* runs, int n_runs, int border,
+                   float border_value, void* out, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+int ptb_binary_morphology(const void* labels, int elem_bytes, int64_t B, int64_t H, int64_t W, int object_rule, int64_t value, int op,
+                          const int32_t* runs, int n_runs, int border, void* out, void* workspace, int64_t workspace_bytes, ptb_stream_t stream);
+
 /* ---- Skeletons of volumes by 3-D thinning, and their centreline Dice (no counterpart in the reference) ---------------
  * Positions are (z, y, x); positions outside the entry are background; the object is 26-connected, the background 6-connected; N26(p),
  * N18(p), N6(p) are the usual punctured neighbourhoods.  p is SIMPLE (Bertrand & Malandain 1994) iff the object positions of N26(p) form

@@ -206,6 +206,10 @@ SIGNATURES = {
     "ptb_skeleton": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_int, _c_i64, _vp, _ip, _vp, _c_i64, _vp]),
     "ptb_centerline_dice_plan": (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _i64p]),
     "ptb_centerline_dice": (_c_int, [_vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_i64, _i64p, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _ip, _vp, _c_i64, _vp]),
+    "ptb_morphology_geometry": (_c_int, [_ip]),
+    "ptb_morphology_plan": (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _c_int, _i64p]),
+    "ptb_morphology": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _ip, _c_int, _c_int, _c_f, _vp, _vp, _c_i64, _vp]),
+    "ptb_binary_morphology": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_int, _ip, _c_int, _c_int, _vp, _vp, _c_i64, _vp]),
     "ptb_thin3d_rule": (_c_int, [ctypes.c_uint32]),
     "ptb_thin3d_geometry": (_c_int, [_ip]),
     "ptb_skeleton3d_plan": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, _i64p]),
