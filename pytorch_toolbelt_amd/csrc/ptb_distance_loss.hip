@@ -8,9 +8,10 @@
 //   3. dl_finish_kernel  and one workgroup per result adds the slots of that result in index order (a lane per run of neighbouring slots,
 //                        then lane 0 over the 256 lanes): loss = sum / count, 1 / count for the backward, NaN under a raised label flag.
 //   4. dl_bwd_kernel     the gradient for all C channels; the maps are constants.
-// Lanes take FOUR NEIGHBOURING POSITIONS: 16-byte loads of logits / maps, 4-byte mask stores where the bases and S % 4 allow (WIDE), a
-// peeled instance otherwise.  A softmax sweeps the channels at stride S and keeps them in registers for C <= 16 (buckets 4 / 8 / 16 like
-// the other loss kernels; CR = 0: a second sweep instead); sigmoid / identity channels are independent and streamed (CR = -1).
+// Lanes take FOUR NEIGHBOURING POSITIONS under the contract of ptb_logits4.h (load4 / store4, labels4): 16-byte loads of logits /
+// maps, 4-byte mask stores where the bases and S % 4 allow (WIDE), a peeled instance otherwise.  A softmax sweeps the channels at stride S
+// and keeps them in registers for C <= 16 (buckets 4 / 8 / 16 like the other loss kernels; CR = 0: a second sweep instead); sigmoid /
+// identity channels are independent and streamed (CR = -1).
 // The grid is a function of the shape alone, a workgroup per 1024 positions of a sample, and the sums are added in a fixed order: a
 // second run gives the same bits.  Every loop is bounded by C or K; no workgroup waits for another one.
 #include <algorithm>
@@ -19,6 +20,7 @@
 #include "ptb_common.h"
 #include "ptb_dispatch.h"
 #include "ptb_edt_common.h"
+#include "ptb_logits4.h"
 
 namespace ptb {
 
@@ -45,30 +47,6 @@ struct DlArgs {
     unsigned S, bps;            // positions per sample; workgroups per sample
     int C, K, act, has_ignore, maps_f32, amode, per_sample;
 };
-
-// ---------------------------------------------------------------------------------------------------------- four positions
-template <bool WIDE, class T>
-__device__ __forceinline__ void dl_load4(const T* q, unsigned p0, unsigned S, T (&v)[4], T fill) {
-    if constexpr (WIDE) {                                                      // S % 4 == 0 and an aligned base: p0 < S means p0 + 3 < S
-        constexpr int A = sizeof(T) * 4 < 16 ? sizeof(T) * 4 : 16;
-        __builtin_memcpy(v, __builtin_assume_aligned(q, A), sizeof(v));
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = p0 + j < S ? q[j] : fill;
-    }
-}
-
-template <bool WIDE, class T>
-__device__ __forceinline__ void dl_store4(T* q, unsigned p0, unsigned S, const T (&v)[4]) {
-    if constexpr (WIDE) {
-        constexpr int A = sizeof(T) * 4 < 16 ? sizeof(T) * 4 : 16;
-        __builtin_memcpy(__builtin_assume_aligned(q, A), v, sizeof(v));
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (p0 + j < S) q[j] = v[j];
-    }
-}
 
 // the signed distance a map value stands for; an entry without a boundary (+-inf, +-(2^31 - 1)) counts as 0
 __device__ __forceinline__ float dl_signed(int bits, int maps_f32) {
@@ -107,7 +85,7 @@ struct DlChannels {
 #pragma unroll
             for (int c = 0; c < CR; ++c) {
                 if (c < a.C) {
-                    dl_load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, xr[c], 0.0f);
+                    load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, xr[c], 0.0f);
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) xr[c][j] = -INFINITY;
@@ -133,7 +111,7 @@ struct DlChannels {
 #pragma unroll 1
             for (int c = 0; c < a.C; ++c) {                                    // the running maximum and the sum with respect to it
                 float v[4];
-                dl_load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
+                load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (v[j] > m[j]) {
@@ -177,7 +155,7 @@ struct DlChannels {
 #pragma unroll 1
             for (int c = 0; c < a.C; ++c) {
                 float v[4], p[4];
-                dl_load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
+                load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
                 prob(a, v, p);
                 f(c, a.slot ? a.slot[c] : c, p);
             }
@@ -198,15 +176,12 @@ struct DlTarget {
             live[j] = WIDE || p0 + j < a.S;
         }
         if (!a.labels) return;
-        dl_load4<WIDE>(a.labels + (size_t)b * a.S + p0, p0, a.S, lab, (long long)-1);
+        Label4 kind[4];
+        labels4<WIDE>(a.labels, b, p0, a.S, a.C, a.has_ignore, a.ignore_label, report, a.flag, lab, kind);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (!live[j]) continue;
-            if (a.has_ignore && lab[j] == a.ignore_label) live[j] = false;
-            else if (lab[j] < 0 || lab[j] >= a.C) {
-                if (report) *a.flag = 1;                                       // (every writer stores the same value)
-                lab[j] = -1;
-            }
+            live[j] = kind[j] >= LABEL_OUTSIDE;
+            if (kind[j] == LABEL_OUTSIDE) lab[j] = -1;
         }
     }
 };
@@ -229,11 +204,11 @@ __global__ __launch_bounds__(DL_THREADS) void dl_mask_kernel(const DlArgs a) {
                 for (int j = 0; j < 4; ++j) o[j] = t.live[j] && t.lab[j] == c;
             } else {
                 float d[4];
-                dl_load4<WIDE>(a.dense + ((size_t)b * a.C + c) * a.S + p0, p0, a.S, d, 0.0f);
+                load4<WIDE>(a.dense + ((size_t)b * a.C + c) * a.S + p0, p0, a.S, d, 0.0f);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o[j] = d[j] > 0.5f && !(a.has_ignore && d[j] == a.ignore_value);
             }
-            dl_store4<WIDE>(a.mask_t + ((size_t)b * a.K + k) * a.S + p0, p0, a.S, o);
+            store4<WIDE>(a.mask_t + ((size_t)b * a.K + k) * a.S + p0, p0, a.S, o);
         }
     }
     if (a.mask_p) {
@@ -245,7 +220,7 @@ __global__ __launch_bounds__(DL_THREADS) void dl_mask_kernel(const DlArgs a) {
             unsigned char o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = p[j] > 0.5f;                    // (a sigmoid's 1 / (1 + exp(-x)) > 0.5 is x > 0)
-            dl_store4<WIDE>(a.mask_p + ((size_t)b * a.K + k) * a.S + p0, p0, a.S, o);
+            store4<WIDE>(a.mask_p + ((size_t)b * a.K + k) * a.S + p0, p0, a.S, o);
         });
     }
 }
@@ -262,7 +237,7 @@ __device__ __forceinline__ void dl_element(const DlArgs& a, const DlTarget<WIDE>
         }
     } else {
         float d[4];
-        dl_load4<WIDE>(a.dense + ((size_t)b * a.C + c) * a.S + p0, p0, a.S, d, 0.0f);
+        load4<WIDE>(a.dense + ((size_t)b * a.C + c) * a.S + p0, p0, a.S, d, 0.0f);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             use[j] = t.live[j] && !(a.has_ignore && d[j] == a.ignore_value);
@@ -276,13 +251,13 @@ template <int KIND, bool WIDE>
 __device__ __forceinline__ void dl_weight(const DlArgs& a, unsigned b, unsigned p0, int k, float (&w)[4]) {
     const size_t off = ((size_t)b * a.K + k) * a.S + p0;
     int vt[4];
-    dl_load4<WIDE>(reinterpret_cast<const int*>(a.phi_t) + off, p0, a.S, vt, 0);
+    load4<WIDE>(reinterpret_cast<const int*>(a.phi_t) + off, p0, a.S, vt, 0);
     if constexpr (KIND == PTB_DLOSS_BOUNDARY) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) w[j] = dl_signed(vt[j], a.maps_f32);
     } else {
         int vp[4];
-        dl_load4<WIDE>(reinterpret_cast<const int*>(a.phi_p) + off, p0, a.S, vp, 0);
+        load4<WIDE>(reinterpret_cast<const int*>(a.phi_p) + off, p0, a.S, vp, 0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) w[j] = dl_power(vp[j], a) + dl_power(vt[j], a);
     }
@@ -430,7 +405,7 @@ __global__ __launch_bounds__(DL_THREADS) void dl_bwd_kernel(const DlArgs a) {
             dterm(c, k, p, d);                                                 // (its loads hit the lines the sweep above brought in)
 #pragma unroll
             for (int j = 0; j < 4; ++j) r[j] = t.live[j] ? p[j] * (d[j] - dot[j]) : 0.0f;
-            dl_store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, r);
+            store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, r);
         });
     } else {
         ch.each(a, x0, p0, [&](int c, int k, const float (&p)[4]) {
@@ -438,22 +413,12 @@ __global__ __launch_bounds__(DL_THREADS) void dl_bwd_kernel(const DlArgs a) {
             dterm(c, k, p, d);
 #pragma unroll
             for (int j = 0; j < 4; ++j) r[j] = a.act == PTB_PROB_SIGMOID ? p[j] * (1.0f - p[j]) * d[j] : d[j];
-            dl_store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, r);
+            store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, r);
         });
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------- host side
-// CR of a launch: the register bucket of a softmax, 0 above 16 channels, -1 for independent channels
-template <class F>
-static void dl_with_channels(int prob, int C, F&& f) {
-    if (prob != PTB_PROB_SOFTMAX) f(int_c<-1>{});
-    else if (C > 16) f(int_c<0>{});
-    else with_at_most<4, 8, 16>(C, f);
-}
-
-static bool dl_aligned(const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
-
 static long long dl_blocks_per_sample(long long S) { return (S + DL_SPAN - 1) / DL_SPAN; }
 
 // what every entry point checks of the problem; fills the shape part of the arguments
@@ -475,10 +440,6 @@ static int dl_common(const float* logits, bool need_logits, const int64_t* label
     a.cls = class_table; a.slot = class_table ? class_table + K : nullptr;
     a.S = (unsigned)S; a.bps = (unsigned)dl_blocks_per_sample(S); a.C = C; a.K = K; a.act = prob;
     return PTB_OK;
-}
-
-static bool dl_wide_inputs(const DlArgs& a) {
-    return a.S % 4 == 0 && dl_aligned(a.x, 16) && dl_aligned(a.labels, 16) && dl_aligned(a.dense, 16);
 }
 
 static int dl_maps(int kind, const void* truth_maps, const void* pred_maps, int maps_kind, float alpha, DlArgs& a) {
@@ -537,13 +498,12 @@ extern "C" int ptb_dloss_masks(const float* logits, const int64_t* labels, const
     const size_t plane = (size_t)B * K * S;
     a.mask_t = truth ? masks : nullptr;
     a.mask_p = pred ? masks + (truth ? plane : 0) : nullptr;
-    const bool wide = dl_wide_inputs(a) && dl_aligned(masks, 4);
     auto launch = [&](auto cr) {
-        with_bool(wide, [&](auto w) {
+        with_bool(wide(S, {logits, labels, dense}) && aligned_to(masks, 4), [&](auto w) {      // (a lane's four mask bytes are one 4-byte store)
             hipLaunchKernelGGL((dl_mask_kernel<cr(), w()>), dim3((unsigned)B * a.bps), dim3(DL_THREADS), 0, (hipStream_t)stream, a);
         });
     };
-    if (pred) dl_with_channels(prob, C, launch);
+    if (pred) with_channels(prob != PTB_PROB_SOFTMAX, C, launch);
     else launch(int_c<-1>{});
     return check_launch();
 }
@@ -564,10 +524,9 @@ extern "C" int ptb_dloss_fwd(int kind, const float* logits, const int64_t* label
     a.flag = error_flag;
     hipStream_t st = (hipStream_t)stream;
     if (hipError_t e = hipMemsetAsync(error_flag, 0, sizeof(int), st); e != hipSuccess) { set_hip_error(e); return PTB_ELAUNCH; }
-    const bool wide = dl_wide_inputs(a) && dl_aligned(truth_maps, 16) && dl_aligned(pred_maps, 16);
     with_value<PTB_DLOSS_BOUNDARY, PTB_DLOSS_HAUSDORFF>(kind, [&](auto kd) {
-        dl_with_channels(prob, C, [&](auto cr) {
-            with_bool(wide, [&](auto w) {
+        with_channels(prob != PTB_PROB_SOFTMAX, C, [&](auto cr) {
+            with_bool(wide(S, {logits, labels, dense, truth_maps, pred_maps}), [&](auto w) {
                 hipLaunchKernelGGL((dl_fwd_kernel<kd(), cr(), w()>), dim3((unsigned)slots), dim3(DL_THREADS), 0, st, a);
             });
         });
@@ -589,10 +548,9 @@ extern "C" int ptb_dloss_bwd(int kind, const float* logits, const int64_t* label
     if (int rc = dl_maps(kind, truth_maps, pred_maps, maps_kind, alpha, a)) return rc;
     a.has_ignore = has_ignore != 0; a.ignore_label = ignore_label; a.ignore_value = ignore_value;
     a.coef = coef; a.grad = grad; a.per_sample = per_sample != 0;
-    const bool wide = dl_wide_inputs(a) && dl_aligned(truth_maps, 16) && dl_aligned(pred_maps, 16) && dl_aligned(grad, 16);
     with_value<PTB_DLOSS_BOUNDARY, PTB_DLOSS_HAUSDORFF>(kind, [&](auto kd) {
-        dl_with_channels(prob, C, [&](auto cr) {
-            with_bool(wide, [&](auto w) {
+        with_channels(prob != PTB_PROB_SOFTMAX, C, [&](auto cr) {
+            with_bool(wide(S, {logits, labels, dense, truth_maps, pred_maps, grad}), [&](auto w) {
                 hipLaunchKernelGGL((dl_bwd_kernel<kd(), cr(), w()>), dim3((unsigned)B * a.bps), dim3(DL_THREADS), 0, (hipStream_t)stream, a);
             });
         });

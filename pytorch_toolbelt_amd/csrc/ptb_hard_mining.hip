@@ -13,14 +13,15 @@
 // The OHEM rule needs no branch of its own: with at least min(min_kept, n) losses above t0 the kept set is those losses, which are the
 // `count above t0` largest ones, so both rules are "the kept largest" with a `kept` computed on the device.
 // Loss bits of values >= +0 order like unsigned integers.  Histograms and counts are integer atomics (exact); floating-point sums go to
-// per-workgroup slots only, so a second run gives the same bits.  Lanes take four neighbouring positions as in ptb_distance_loss.hip
-// (16-byte accesses in the WIDE instances, a peeled instance otherwise); a softmax keeps C <= 16 channels in registers (buckets 4 / 8 /
-// 16; CR = 0: a running maximum over memory), sigmoid channels are independent elements (CR = -1).  Every grid is a function of the shape
-// alone, every loop is bounded by C or a constant, no workgroup waits for another one and nothing is read back.
+// per-workgroup slots only, so a second run gives the same bits.  Lanes take four neighbouring positions under the contract of ptb_logits4.h
+// (WIDE: 16-byte accesses, a peeled instance otherwise); a softmax keeps C <= 16 channels in registers (buckets 4 / 8 / 16; CR = 0: a
+// running maximum over memory), sigmoid channels are independent elements (CR = -1).  Every grid is a function of the shape alone, every
+// loop is bounded by C or a constant, no workgroup waits for another one and nothing is read back.
 #include <cmath>
 
 #include "ptb_common.h"
 #include "ptb_dispatch.h"
+#include "ptb_logits4.h"
 
 namespace ptb {
 
@@ -47,30 +48,6 @@ struct HmArgs {
     int C, has_ignore, per_sample;
 };
 
-// ---------------------------------------------------------------------------------------------------------- four positions
-template <bool WIDE, class T>
-__device__ __forceinline__ void hm_load4(const T* q, unsigned p0, unsigned S, T (&v)[4], T fill) {
-    if constexpr (WIDE) {                                                      // S % 4 == 0 and an aligned base: p0 < S means p0 + 3 < S
-        constexpr int A = sizeof(T) * 4 < 16 ? sizeof(T) * 4 : 16;
-        __builtin_memcpy(v, __builtin_assume_aligned(q, A), sizeof(v));
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = p0 + j < S ? q[j] : fill;
-    }
-}
-
-template <bool WIDE, class T>
-__device__ __forceinline__ void hm_store4(T* q, unsigned p0, unsigned S, const T (&v)[4]) {
-    if constexpr (WIDE) {
-        constexpr int A = sizeof(T) * 4 < 16 ? sizeof(T) * 4 : 16;
-        __builtin_memcpy(__builtin_assume_aligned(q, A), v, sizeof(v));
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (p0 + j < S) q[j] = v[j];
-    }
-}
-
 // the key of a loss: its bits, +0 for -0; a NaN (infinite logits) keeps one positive pattern so that no key but HM_IGNORED has the top bit
 __device__ __forceinline__ unsigned hm_key(float l) {
     const unsigned u = __float_as_uint(l);
@@ -92,7 +69,7 @@ struct HmSoftmax {
 #pragma unroll
             for (int c = 0; c < CR; ++c) {
                 if (c < a.C) {
-                    hm_load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, xr[c], 0.0f);
+                    load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, xr[c], 0.0f);
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) xr[c][j] = -INFINITY;
@@ -121,7 +98,7 @@ struct HmSoftmax {
 #pragma unroll 1
             for (int c = 0; c < a.C; ++c) {
                 float v[4];
-                hm_load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
+                load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (v[j] > m[j]) {
@@ -137,22 +114,15 @@ struct HmSoftmax {
     }
 };
 
-// the labels of four positions; live: the position exists, its label is not ignored and lies in [0, C) (one outside raises the flag)
+// the labels of four positions; live: the position exists, its label is not ignored and lies in [0, C) -- every other label reads -1
 template <bool WIDE>
 __device__ __forceinline__ void hm_labels(const HmArgs& a, unsigned b, unsigned p0, bool report, long long (&lab)[4], bool (&live)[4]) {
-    hm_load4<WIDE>(a.labels + (size_t)b * a.S + p0, p0, a.S, lab, (long long)-1);
+    Label4 kind[4];
+    labels4<WIDE>(a.labels, b, p0, a.S, a.C, a.has_ignore, a.ignore_label, report, a.flag, lab, kind);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        live[j] = WIDE || p0 + j < a.S;
-        if (!live[j]) continue;
-        if (a.has_ignore && lab[j] == a.ignore_label) {
-            live[j] = false;
-            lab[j] = -1;
-        } else if (lab[j] < 0 || lab[j] >= a.C) {
-            if (report) *a.flag = 1;                                           // (every writer stores the same value)
-            live[j] = false;
-            lab[j] = -1;
-        }
+        live[j] = kind[j] == LABEL_VALID;
+        if (!live[j]) lab[j] = -1;
     }
 }
 
@@ -190,15 +160,15 @@ __global__ __launch_bounds__(HM_THREADS) void hm_loss_kernel(const HmArgs a) {
                 key[j] = live[j] ? hm_key((sm.m[j] - sm.xl[j]) + logf(sm.s[j])) : HM_IGNORED;       // both terms are >= 0: s >= 1
                 hm_count(key[j], t0_key, hist, n, above);
             }
-            hm_store4<WIDE>(a.map + (size_t)b * a.S + p0, p0, a.S, key);
+            store4<WIDE>(a.map + (size_t)b * a.S + p0, p0, a.S, key);
         } else {
 #pragma unroll 1
             for (int c = 0; c < a.C; ++c) {
                 const size_t off = ((size_t)b * a.C + c) * a.S + p0;
                 float v[4], g[4];
                 unsigned key[4];
-                hm_load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
-                hm_load4<WIDE>(a.dense + off, p0, a.S, g, 0.0f);
+                load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
+                load4<WIDE>(a.dense + off, p0, a.S, g, 0.0f);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const bool live = (WIDE || p0 + j < a.S) && !(a.has_ignore && g[j] == a.ignore_value);
@@ -207,7 +177,7 @@ __global__ __launch_bounds__(HM_THREADS) void hm_loss_kernel(const HmArgs a) {
                     key[j] = live ? hm_key(l) : HM_IGNORED;
                     hm_count(key[j], t0_key, hist, n, above);
                 }
-                hm_store4<WIDE>(a.map + off, p0, a.S, key);
+                store4<WIDE>(a.map + off, p0, a.S, key);
             }
         }
     }
@@ -251,7 +221,7 @@ __device__ __forceinline__ void hm_entries(const HmSelectArgs& a, unsigned set, 
         const unsigned e0 = chunk * HM_CHUNK + (i * HM_THREADS + threadIdx.x) * 4u;       // (per_set < 2^31: no wrap)
         if (e0 >= a.per_set) continue;
         unsigned key[4];
-        hm_load4<WIDE>(base + e0, e0, a.per_set, key, HM_IGNORED);
+        load4<WIDE>(base + e0, e0, a.per_set, key, HM_IGNORED);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (key[j] != HM_IGNORED) f(key[j]);
@@ -438,7 +408,7 @@ __global__ __launch_bounds__(HM_THREADS) void hm_bwd_kernel(const HmArgs a) {
     const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if constexpr (CR >= 0) {
         unsigned key[4];
-        hm_load4<WIDE>(a.map + (size_t)b * a.S + p0, p0, a.S, key, HM_IGNORED);
+        load4<WIDE>(a.map + (size_t)b * a.S + p0, p0, a.S, key, HM_IGNORED);
         float w[4];
         bool any = false;
 #pragma unroll
@@ -448,7 +418,7 @@ __global__ __launch_bounds__(HM_THREADS) void hm_bwd_kernel(const HmArgs a) {
         }
         if (!__any(any)) {                                                     // nothing kept in the whole wave (a uniform branch): the logits are not read
 #pragma unroll 1
-            for (int c = 0; c < a.C; ++c) hm_store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, zero);
+            for (int c = 0; c < a.C; ++c) store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, zero);
             return;
         }
         long long lab[4];
@@ -463,7 +433,7 @@ __global__ __launch_bounds__(HM_THREADS) void hm_bwd_kernel(const HmArgs a) {
                 const float d = expf(v[j] - sm.m[j]) / sm.s[j] - (lab[j] == c ? 1.0f : 0.0f);
                 r[j] = w[j] != 0.0f ? w[j] * d : 0.0f;                         // (exact zeros where nothing is kept, whatever the logits hold)
             }
-            hm_store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, r);
+            store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, r);
         };
         if constexpr (CR > 0) {
 #pragma unroll
@@ -473,7 +443,7 @@ __global__ __launch_bounds__(HM_THREADS) void hm_bwd_kernel(const HmArgs a) {
 #pragma unroll 1
             for (int c = 0; c < a.C; ++c) {
                 float v[4];
-                hm_load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
+                load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
                 channel(c, v);
             }
         }
@@ -482,38 +452,28 @@ __global__ __launch_bounds__(HM_THREADS) void hm_bwd_kernel(const HmArgs a) {
         for (int c = 0; c < a.C; ++c) {
             const size_t off = ((size_t)b * a.C + c) * a.S + p0;
             unsigned key[4];
-            hm_load4<WIDE>(a.map + off, p0, a.S, key, HM_IGNORED);
+            load4<WIDE>(a.map + off, p0, a.S, key, HM_IGNORED);
             bool any = false;
 #pragma unroll
             for (int j = 0; j < 4; ++j) any = any || (key[j] >= cut && key[j] != HM_IGNORED);
             if (!__any(any)) {
-                hm_store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, zero);
+                store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, zero);
                 continue;
             }
             float v[4], g[4], r[4];
-            hm_load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
-            hm_load4<WIDE>(a.dense + off, p0, a.S, g, 0.0f);
+            load4<WIDE>(x0 + (size_t)c * a.S, p0, a.S, v, 0.0f);
+            load4<WIDE>(a.dense + off, p0, a.S, g, 0.0f);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float w = weight(key[j]);
                 r[j] = w != 0.0f ? w * (1.0f / (1.0f + expf(-v[j])) - g[j]) : 0.0f;
             }
-            hm_store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, r);
+            store4<WIDE>(g0 + (size_t)c * a.S, p0, a.S, r);
         }
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------- host side
-// CR of a launch: the register bucket of a softmax, 0 above 16 channels, -1 for the independent channels of dense targets
-template <class F>
-static void hm_with_channels(bool dense, int C, F&& f) {
-    if (dense) f(int_c<-1>{});
-    else if (C > 16) f(int_c<0>{});
-    else with_at_most<4, 8, 16>(C, f);
-}
-
-static bool hm_aligned(const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
-
 struct HmShape {
     long long sets, per_set, cps, bps;      // selection sets, entries of one, histogram / sum workgroups of one, loss workgroups per sample
 };
@@ -559,7 +519,7 @@ extern "C" int ptb_hardce_fwd(const float* logits, const int64_t* labels, const 
     }
     HmShape h{};
     if (int rc = hm_shape(dense != nullptr, B, C, S, per_sample, h)) return rc;
-    if (!aligned16(workspace) || workspace_bytes < hm_workspace(h) || !hm_aligned(map, 4) || !hm_aligned(select, 4)) return PTB_EINVAL;
+    if (!aligned16(workspace) || workspace_bytes < hm_workspace(h) || !aligned_to(map, 4) || !aligned_to(select, 4)) return PTB_EINVAL;
     const long long slots = h.sets * h.cps;
     HmSelectArgs s{};
     s.map = reinterpret_cast<const unsigned*>(map);
@@ -578,13 +538,12 @@ extern "C" int ptb_hardce_fwd(const float* logits, const int64_t* labels, const 
     hipStream_t st = (hipStream_t)stream;
     if (hipError_t e = hipMemsetAsync(error_flag, 0, sizeof(int), st); e != hipSuccess) { set_hip_error(e); return PTB_ELAUNCH; }
     if (hipError_t e = hipMemsetAsync(s.state, 0, (size_t)h.sets * HM_STATE * 4, st); e != hipSuccess) { set_hip_error(e); return PTB_ELAUNCH; }
-    const bool wide = S % 4 == 0 && hm_aligned(logits, 16) && hm_aligned(labels, 16) && hm_aligned(dense, 16) && hm_aligned(map, 16);
-    hm_with_channels(dense != nullptr, C, [&](auto cr) {
-        with_bool(wide, [&](auto w) {
+    with_channels(dense != nullptr, C, [&](auto cr) {
+        with_bool(wide(S, {logits, labels, dense, map}), [&](auto w) {
             hipLaunchKernelGGL((hm_loss_kernel<cr(), w()>), dim3((unsigned)(B * h.bps)), dim3(HM_THREADS), 0, st, a);
         });
     });
-    const bool wide_map = h.per_set % 4 == 0 && hm_aligned(map, 16);
+    const bool wide_map = wide(h.per_set, {map});
     const dim3 grid((unsigned)slots);
     for (int shift = 24; shift >= 0; shift -= 8) {
         s.shift = shift;
@@ -606,15 +565,14 @@ extern "C" int ptb_hardce_bwd(const float* logits, const int64_t* labels, const 
     if (!logits || (labels != nullptr) == (dense != nullptr) || !map || !coef || !select || !grad) return PTB_EINVAL;
     HmShape h{};
     if (int rc = hm_shape(dense != nullptr, B, C, S, per_sample, h)) return rc;
-    if (!hm_aligned(map, 4) || !hm_aligned(select, 4)) return PTB_EINVAL;
+    if (!aligned_to(map, 4) || !aligned_to(select, 4)) return PTB_EINVAL;
     HmArgs a{};
     a.x = logits; a.labels = reinterpret_cast<const long long*>(labels); a.dense = dense;
     a.map = const_cast<unsigned*>(reinterpret_cast<const unsigned*>(map));
     a.coef = coef; a.select = reinterpret_cast<const unsigned*>(select); a.grad = grad;
     a.S = (unsigned)S; a.bps = (unsigned)h.bps; a.C = C; a.per_sample = per_sample != 0;
-    const bool wide = S % 4 == 0 && hm_aligned(logits, 16) && hm_aligned(labels, 16) && hm_aligned(dense, 16) && hm_aligned(map, 16) && hm_aligned(grad, 16);
-    hm_with_channels(dense != nullptr, C, [&](auto cr) {
-        with_bool(wide, [&](auto w) {
+    with_channels(dense != nullptr, C, [&](auto cr) {
+        with_bool(wide(S, {logits, labels, dense, map, grad}), [&](auto w) {
             hipLaunchKernelGGL((hm_bwd_kernel<cr(), w()>), dim3((unsigned)(B * h.bps)), dim3(HM_THREADS), 0, (hipStream_t)stream, a);
         });
     });

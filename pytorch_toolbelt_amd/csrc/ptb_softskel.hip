@@ -36,6 +36,7 @@
 
 #include "ptb_common.h"
 #include "ptb_dispatch.h"
+#include "ptb_logits4.h"
 #include "ptb_softskel_host.h"
 
 namespace ptb {
@@ -58,27 +59,6 @@ struct SsArgs {
 };
 
 // ---------------------------------------------------------------------------------------------------------- the values of a cell
-__device__ __forceinline__ float ss_prob(const SsArgs& a, size_t b, int ch, size_t pos) {
-    const size_t S = (size_t)a.H * (size_t)a.W;
-    const float* x0 = a.x + b * (size_t)a.C * S + pos;
-    const float v = x0[(size_t)ch * S];
-    if (a.act == PTB_PROB_IDENTITY) return v;
-    if (a.act == PTB_PROB_SIGMOID) return 1.0f / (1.0f + expf(-v));
-    float m = x0[0];
-#pragma unroll 1
-    for (int c = 1; c < a.C; ++c) m = fmaxf(m, x0[(size_t)c * S]);
-    float s = 0.0f;
-#pragma unroll 1
-    for (int c = 0; c < a.C; ++c) s += expf(x0[(size_t)c * S] - m);
-    return expf(v - m) / s;
-}
-
-__device__ __forceinline__ float ss_target(const SsArgs& a, size_t b, int ch, size_t pos) {
-    const size_t S = (size_t)a.H * (size_t)a.W;
-    if (a.labels) return a.labels[b * S + pos] == (long long)ch ? 1.0f : 0.0f;
-    return a.dense[(b * (size_t)a.C + (size_t)ch) * S + pos];
-}
-
 // the plane of a tile at (ty0, tx0) with a halo of HALO cells and the ring: the values of the image, +inf elsewhere
 template <int LP, int HALO, bool TARGET>
 __device__ __forceinline__ void ss_load(const SsArgs& a, float* dst, size_t b, int ch, int ty0, int tx0) {
@@ -88,8 +68,8 @@ __device__ __forceinline__ void ss_load(const SsArgs& a, float* dst, size_t b, i
         const int gy = ty0 - HALO - 1 + r, gx = tx0 - HALO - 1 + q;
         float v = SS_INF;
         if (r >= 1 && r <= LP - 2 && q >= 1 && q <= LP - 2 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
-            const size_t pos = (size_t)gy * (size_t)a.W + (size_t)gx;
-            v = TARGET ? ss_target(a, b, ch, pos) : ss_prob(a, b, ch, pos);
+            const size_t S = (size_t)a.H * (size_t)a.W, pos = (size_t)gy * (size_t)a.W + (size_t)gx;
+            v = TARGET ? target(a.labels, a.dense, b, ch, a.C, S, pos) : prob(a.x + b * (size_t)a.C * S + pos, ch, a.C, S, a.act);
         }
         dst[c] = v;
     }
@@ -176,7 +156,7 @@ template <int R, bool LOSS>
 __global__ __launch_bounds__(SS_THREADS) void ss_fwd_kernel(const SsArgs a) {
     constexpr int T = SS_FWD_TILE, LP = T + 2 * R + 2, PER = T * T / SS_THREADS;
     __shared__ float P[2][LP * LP];
-    __shared__ double wsum[SS_THREADS / 64][4];
+    __shared__ double wsum[SS_THREADS / 64][4];                              // (block_sums, ptb_logits4.h)
     unsigned k, b;
     int ty0, tx0;
     ss_place(a, k, b, ty0, tx0, T);
@@ -217,20 +197,8 @@ __global__ __launch_bounds__(SS_THREADS) void ss_fwd_kernel(const SsArgs a) {
             s[2] += (double)(skel[1][u] * own[0][u]);
             s[3] += (double)skel[1][u];
         }
-        // the workgroup's sums: a fixed tree inside every wave, then the four waves in order
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) s[q] += __shfl_down(s[q], d);
-            if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][q] = s[q];
-        }
-        __syncthreads();
-        if (threadIdx.x < 4) {
-            double r = wsum[0][threadIdx.x];
-#pragma unroll
-            for (int w = 1; w < SS_THREADS / 64; ++w) r += wsum[w][threadIdx.x];
-            a.slots[(size_t)blockIdx.x * 4 + threadIdx.x] = r;
-        }
+        const double r = block_sums(s, wsum);
+        if (threadIdx.x < 4) a.slots[(size_t)blockIdx.x * 4 + threadIdx.x] = r;
     }
 }
 
@@ -332,7 +300,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_bwd_kernel(const SsArgs a) {
             active |= 1u << u;
             pos[u] = (size_t)gy * (size_t)a.W + (size_t)gx;
             if (gy >= ty0 && gy < ty0 + T && gx >= tx0 && gx < tx0 + T) inner |= 1u << u;
-            gS[u] = ca * ss_target(a, b, ch, pos[u]) + cb;                     // w = a g + b
+            gS[u] = ca * target(a.labels, a.dense, b, ch, a.C, S, pos[u]) + cb;                     // w = a g + b
         }
     }
     __syncthreads();

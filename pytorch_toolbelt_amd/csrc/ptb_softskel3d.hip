@@ -35,6 +35,7 @@
 
 #include "ptb_common.h"
 #include "ptb_dispatch.h"
+#include "ptb_logits4.h"
 #include "ptb_softskel_host.h"
 
 namespace ptb {
@@ -80,26 +81,6 @@ struct Ss3GatherArgs {
     const float* coef;
     float* dp;
 };
-
-// ---------------------------------------------------------------------------------------------------------- the values of a cell
-__device__ __forceinline__ float ss3_prob(const Ss3Shape& s, const float* x, size_t S, size_t b, int ch, size_t pos) {
-    const float* x0 = x + b * (size_t)s.C * S + pos;
-    const float v = x0[(size_t)ch * S];
-    if (s.act == PTB_PROB_IDENTITY) return v;
-    if (s.act == PTB_PROB_SIGMOID) return 1.0f / (1.0f + expf(-v));
-    float m = x0[0];
-#pragma unroll 1
-    for (int c = 1; c < s.C; ++c) m = fmaxf(m, x0[(size_t)c * S]);
-    float sum = 0.0f;
-#pragma unroll 1
-    for (int c = 0; c < s.C; ++c) sum += expf(x0[(size_t)c * S] - m);
-    return expf(v - m) / sum;
-}
-
-__device__ __forceinline__ float ss3_target(const Ss3Shape& s, const long long* labels, const float* dense, size_t S, size_t b, int ch, size_t pos) {
-    if (labels) return labels[b * S + pos] == (long long)ch ? 1.0f : 0.0f;
-    return dense[(b * (size_t)s.C + (size_t)ch) * S + pos];
-}
 
 // where a workgroup stands: side, class, batch entry, the origin of its tile
 struct Ss3Place {
@@ -164,19 +145,19 @@ template <bool FIRST, bool LAST, bool SAVE>
 __global__ __launch_bounds__(SS3_THREADS) void ss3_stage_kernel(const Ss3Args a) {
     __shared__ float A[AN];                         // v_j on the tile + 2
     __shared__ float Bv[BN];                        // v_j+1 on the tile + 1
-    __shared__ double wsum[SS3_THREADS / 64][2];
+    __shared__ double wsum[SS3_THREADS / 64][2];    // (block_sums, ptb_logits4.h)
     const Ss3Shape& s = a.s;
     const Ss3Place p = ss3_place(s);
-    const bool target = p.side != 0u;
+    const bool is_target = p.side != 0u;
     const int ch = s.cls[p.k];
     const size_t S = (size_t)s.D * (size_t)s.H * (size_t)s.W, base = ((size_t)p.b * s.K + p.k) * S;
-    const float* vin = target ? a.vin1 : a.vin0;
+    const float* vin = is_target ? a.vin1 : a.vin0;
 #pragma unroll 1
     for (int c = (int)threadIdx.x; c < AN; c += SS3_THREADS) {
         size_t pos;
         float v = SS3_INF;
         if (ss3_cell<AY, AX, 2>(s, p, c, pos)) {
-            if constexpr (FIRST) v = target ? ss3_target(s, a.labels, a.dense, S, p.b, ch, pos) : ss3_prob(s, a.x, S, p.b, ch, pos);
+            if constexpr (FIRST) v = is_target ? target(a.labels, a.dense, p.b, ch, s.C, S, pos) : prob(a.x + (size_t)p.b * s.C * S + pos, ch, s.C, S, s.act);
             else v = vin[base + pos];
         }
         A[c] = v;
@@ -197,12 +178,12 @@ __global__ __launch_bounds__(SS3_THREADS) void ss3_stage_kernel(const Ss3Args a)
 
     const int ly = (int)threadIdx.x / TX, lx = (int)threadIdx.x % TX;
     const bool column = p.y0 + ly < s.H && p.x0 + lx < s.W;
-    const bool save = SAVE && !target;
-    float* Sp = target ? a.S1 : a.S0;
-    float* vout = target ? a.vout1 : a.vout0;
+    const bool save = SAVE && !is_target;
+    float* Sp = is_target ? a.S1 : a.S0;
+    float* vout = is_target ? a.vout1 : a.vout0;
     const size_t at0 = base + ((size_t)p.z0 * (size_t)s.H + (size_t)(p.y0 + ly)) * (size_t)s.W + (size_t)(p.x0 + lx), plane = (size_t)s.H * (size_t)s.W;
     const int cb0 = (ly + 1) * BX + lx + 1;         // the column in plane 0 of the tile + 1 block
-    double s0 = 0.0, s1 = 0.0;                      // prediction: sum SP g, sum SP; target: sum ST p, sum ST
+    double sums[2] = {0.0, 0.0};                    // prediction: sum SP g, sum SP; target: sum ST p, sum ST
     float m0 = ss3_plane_max(Bv, cb0), m1 = ss3_plane_max(Bv, cb0 + BY * BX);
 #pragma unroll
     for (int z = 0; z < TZ; ++z) {
@@ -224,9 +205,9 @@ __global__ __launch_bounds__(SS3_THREADS) void ss3_stage_kernel(const Ss3Args a)
             if constexpr (LAST) {
                 if (a.slots) {
                     const size_t pos = at - base;
-                    const float other = target ? ss3_prob(s, a.x, S, p.b, ch, pos) : ss3_target(s, a.labels, a.dense, S, p.b, ch, pos);
-                    s0 += (double)(skel * other);
-                    s1 += (double)skel;
+                    const float other = is_target ? prob(a.x + (size_t)p.b * s.C * S + pos, ch, s.C, S, s.act) : target(a.labels, a.dense, p.b, ch, s.C, S, pos);
+                    sums[0] += (double)(skel * other);
+                    sums[1] += (double)skel;
                 }
             }
         }
@@ -235,23 +216,10 @@ __global__ __launch_bounds__(SS3_THREADS) void ss3_stage_kernel(const Ss3Args a)
     }
     if constexpr (LAST) {
         if (!a.slots) return;                       // (uniform: a kernel argument)
-        // the workgroup's sums: a fixed tree inside every wave, then the four waves in order
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            s0 += __shfl_down(s0, d);
-            s1 += __shfl_down(s1, d);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            wsum[threadIdx.x >> 6][0] = s0;
-            wsum[threadIdx.x >> 6][1] = s1;
-        }
-        __syncthreads();
+        const double r = block_sums(sums, wsum);
         if (threadIdx.x < 2) {
-            double r = wsum[0][threadIdx.x];
-#pragma unroll
-            for (int w = 1; w < SS3_THREADS / 64; ++w) r += wsum[w][threadIdx.x];
             const size_t slot = ((size_t)p.k * s.B + p.b) * s.tiles + blockIdx.x % s.tiles;
-            a.slots[slot * 4 + (target ? 2 : 0) + threadIdx.x] = r;
+            a.slots[slot * 4 + (is_target ? 2 : 0) + threadIdx.x] = r;
         }
     }
 }
@@ -272,7 +240,7 @@ __global__ __launch_bounds__(SS3_THREADS) void ss3_direct_kernel(const Ss3Direct
     if (i >= a.total) return;
     const size_t bk = i / a.S, pos = i - bk * a.S, b = bk / (size_t)a.K;
     const int k = (int)(bk - b * (size_t)a.K), ch = a.cls[k];
-    const float g = a.labels ? (a.labels[b * a.S + pos] == (long long)ch ? 1.0f : 0.0f) : a.dense[(b * (size_t)a.C + (size_t)ch) * a.S + pos];
+    const float g = target(a.labels, a.dense, b, ch, a.C, a.S, pos);
     float d[SS_CAP + 1], below[SS_CAP + 1];       // delta_j; S_j-1
     float skel = 0.0f;
 #pragma unroll
@@ -311,7 +279,7 @@ __global__ __launch_bounds__(SS3_THREADS) void ss3_gather_kernel(const Ss3Gather
     for (int c = (int)threadIdx.x; c < AN; c += SS3_THREADS) {
         size_t pos;
         float v = SS3_INF;
-        if (ss3_cell<AY, AX, 2>(s, p, c, pos)) v = FINAL ? ss3_prob(s, a.x, S, p.b, ch, pos) : a.v[base + pos];
+        if (ss3_cell<AY, AX, 2>(s, p, c, pos)) v = FINAL ? prob(a.x + (size_t)p.b * s.C * S + pos, ch, s.C, S, s.act) : a.v[base + pos];
         V[c] = v;
     }
 #pragma unroll 1

@@ -34,24 +34,7 @@ def region_statistics(y_pred, y_true, mode, from_logits, ignore_index):
         from ..parallel import sync_region_statistics
 
         return sync_region_statistics.apply(H.region_statistics(y_pred, y_true, mode, from_logits, ignore_index))
-    bs = y_true.size(0)
-    x = K.as_f32(y_pred, "region loss")
-    if mode == MULTICLASS_MODE:
-        x = x.reshape(bs, x.size(1), -1)
-        labels = y_true.to(device=x.device).reshape(bs, -1)
-        if labels.dtype != torch.int64:
-            labels = labels.long()
-        labels = labels.contiguous()
-        if labels.size(1) != x.size(2):
-            raise RuntimeError(f"target shape {tuple(y_true.shape)} does not match prediction shape {tuple(y_pred.shape)}")
-        prob = K.PROB_SOFTMAX if from_logits else K.PROB_IDENTITY
-        stats = K.RegionStats.apply(x, labels, None, prob, ignore_index is not None, int(ignore_index) if ignore_index is not None else 0, 0.0)
-    else:
-        C = 1 if mode == BINARY_MODE else x.size(1)
-        x = x.reshape(bs, C, -1)
-        dense = _dense_target(y_true, x, bs, C, y_pred)
-        prob = K.PROB_SIGMOID if from_logits else K.PROB_IDENTITY
-        stats = K.RegionStats.apply(x, None, dense, prob, ignore_index is not None, 0, float(ignore_index) if ignore_index is not None else 0.0)
+    stats = K.RegionStats.apply(*_inputs(y_pred, y_true, mode, from_logits, ignore_index))
     from ..parallel import sync_region_statistics   # batch sharded over ranks: sum the [C] partials (no-op by default)
 
     return sync_region_statistics.apply((stats[0].float(), stats[1].float(), stats[2].float()))

@@ -57,7 +57,7 @@ from .. import _native as N
 from ..utils import softskel as _softskel
 from . import _host
 from . import _kernels as K
-from ._region import BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE
+from . import _problem as P
 
 __all__ = ["SoftClDiceLoss", "soft_cldice_loss"]
 
@@ -71,14 +71,8 @@ def _check_dims(what, dims):
 
 
 def _check_config(what, mode, classes, iterations, smooth):
-    if mode not in (BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE):
-        raise ValueError(f"{what}: mode must be 'binary', 'multiclass' or 'multilabel', got {mode!r}")
-    if classes is not None:
-        if mode == BINARY_MODE:
-            raise ValueError(f"{what}: masking classes is not supported with mode='binary'")
-        classes = [int(c) for c in classes]
-        if not classes or len(set(classes)) != len(classes) or min(classes) < 0:
-            raise ValueError(f"{what}: classes must be distinct non-negative ints, got {classes!r}")
+    P.check_mode(what, mode)
+    classes = P.check_classes(what, mode, classes)
     iterations = _softskel.check_iterations(what, iterations)
     smooth = float(smooth)
     if not (smooth >= 0.0 and np.isfinite(smooth)):
@@ -170,37 +164,14 @@ def soft_cldice_loss(y_pred: Tensor, y_true: Tensor, mode: str, classes: Optiona
     what = "soft_cldice_loss"
     classes, iterations, smooth = _check_config(what, mode, classes, iterations, smooth)
     dims = _check_dims(what, dims)
-    if not isinstance(y_pred, torch.Tensor) or not isinstance(y_true, torch.Tensor):
-        raise TypeError(f"{what}: y_pred and y_true must be tensors")
-    if y_pred.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-        raise TypeError(f"{what}: y_pred must be float32, float16 or bfloat16, got {y_pred.dtype}")
-    if dims == 2 and y_pred.dim() == 5:
-        raise NotImplementedError(f"{what}: 3-D volumes take dims=3 (the default dims=2 reads [B, C, H, W]); got {tuple(y_pred.shape)}")
-    if y_pred.dim() != dims + 2:
-        raise ValueError(f"{what}: y_pred must be [B, C, {'D, ' if dims == 3 else ''}H, W] for dims={dims}, got {tuple(y_pred.shape)}")
-    B, C, *space = y_pred.shape
-    if y_pred.numel() == 0:
-        raise ValueError(f"{what}: empty prediction of shape {tuple(y_pred.shape)}")
-    if mode == BINARY_MODE and C != 1:
-        raise ValueError(f"{what}: mode='binary' takes one channel, got {C}")
+    pr = P.problem(what, y_pred, y_true, mode, from_logits, dims=dims, half_or_single=True, exact_labels=True, detach_target=True)
+    C, prob = pr.C, pr.prob
     cls = list(range(C)) if classes is None else classes
     if max(cls) >= C:
         raise ValueError(f"{what}: classes {cls} name a channel outside [0, {C})")
-    if y_true.device != y_pred.device:
-        y_true = y_true.to(y_pred.device)
-    x = y_pred.float().contiguous()
-    labels = dense = None
-    if mode == MULTICLASS_MODE:
-        if y_true.is_floating_point() or tuple(y_true.shape) != (B, *space):
-            raise ValueError(f"{what}: a multiclass target holds integer labels [B, {'D, ' if dims == 3 else ''}H, W]; got {y_true.dtype} {tuple(y_true.shape)} "
-                             f"for {tuple(y_pred.shape)}")
-        labels = y_true.to(torch.int64).contiguous()
-        prob = K.PROB_SOFTMAX if from_logits else K.PROB_IDENTITY
-    else:
-        if y_true.numel() != y_pred.numel():
-            raise ValueError(f"{what}: target shape {tuple(y_true.shape)} does not match prediction shape {tuple(y_pred.shape)}")
-        dense = y_true.detach().float().contiguous().reshape(x.shape)
-        prob = K.PROB_SIGMOID if from_logits else K.PROB_IDENTITY
+    x = pr.x.reshape(pr.B, C, *pr.spatial)                                   # the problem in its planes / volumes again
+    labels = None if pr.labels is None else pr.labels.reshape(pr.B, *pr.spatial)
+    dense = None if pr.dense is None else pr.dense.reshape(x.shape)
     if not x.is_cuda:
         p = torch.softmax(x, dim=1) if prob == K.PROB_SOFTMAX else torch.sigmoid(x) if prob == K.PROB_SIGMOID else x
         g = dense[:, cls] if labels is None else (labels.unsqueeze(1) == torch.tensor(cls, dtype=torch.int64).reshape(1, -1, *([1] * dims))).to(p.dtype)

@@ -29,7 +29,8 @@ from .. import _native as N
 from ..utils import _maps as M
 from ..utils import distance as _distance
 from . import _kernels as K
-from ._region import BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE
+from . import _problem as P
+from ._region import MULTICLASS_MODE
 
 __all__ = ["BoundaryLoss", "HausdorffDTLoss", "boundary_loss", "hausdorff_dt_loss"]
 
@@ -40,37 +41,10 @@ _NAMES = {BOUNDARY: "boundary_loss", HAUSDORFF: "hausdorff_dt_loss"}
 
 # ---------------------------------------------------------------------------------------------------------------- arguments
 def _problem(what, y_pred, y_true, mode, classes, from_logits, ignore_index, spacing, dist_maps):
-    """The tensors as the kernels take them -- x fp32 ``[B, C, S]``, labels int64 ``[B, S]`` or dense fp32 ``[B, C, S]`` -- and the rest of a call."""
-    if mode not in (BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE):
-        raise ValueError(f"{what}: mode must be 'binary', 'multiclass' or 'multilabel', got {mode!r}")
-    if not isinstance(y_pred, torch.Tensor) or not isinstance(y_true, torch.Tensor):
-        raise TypeError(f"{what}: y_pred and y_true must be tensors")
-    if not y_pred.is_floating_point():
-        raise TypeError(f"{what}: y_pred must be a floating-point tensor, got {y_pred.dtype}")
-    dims = y_pred.dim() - 2
-    if dims not in (2, 3):
-        raise ValueError(f"{what}: y_pred must be [B, C, H, W] or [B, C, D, H, W], got {tuple(y_pred.shape)}")
-    B, C = y_pred.shape[0], y_pred.shape[1]
-    spatial = tuple(y_pred.shape[2:])
-    S = int(np.prod(spatial))
-    if B * C * S == 0:
-        raise ValueError(f"{what}: empty prediction of shape {tuple(y_pred.shape)}")
-    if mode == BINARY_MODE and C != 1:
-        raise ValueError(f"{what}: mode='binary' takes one channel, got {C}")
-    if y_true.device != y_pred.device:
-        y_true = y_true.to(y_pred.device)
-    x = y_pred.float().contiguous().reshape(B, C, S)          # (fp16 / bf16 logits are widened first, like the other losses)
-    labels = dense = None
-    if mode == MULTICLASS_MODE:
-        if y_true.is_floating_point() or y_true.numel() != B * S:
-            raise ValueError(f"{what}: a multiclass target holds integer labels [B, *spatial]; got {y_true.dtype} {tuple(y_true.shape)} for {tuple(y_pred.shape)}")
-        labels = y_true.reshape(B, S).to(torch.int64).contiguous()
-        prob = K.PROB_SOFTMAX if from_logits else K.PROB_IDENTITY
-    else:
-        if y_true.numel() != B * C * S:
-            raise ValueError(f"{what}: target shape {tuple(y_true.shape)} does not match prediction shape {tuple(y_pred.shape)}")
-        dense = y_true.float().contiguous().reshape(B, C, S)
-        prob = K.PROB_SIGMOID if from_logits else K.PROB_IDENTITY
+    """The shared ``Problem`` of a call and what belongs to distances: class table, spacing, geometry, the caller's maps as ``[B, K, S]``."""
+    pr = P.problem(what, y_pred, y_true, mode, from_logits, ignore_index)
+    x, B, C, spatial, S = pr.x, pr.B, pr.C, pr.spatial, pr.S
+    dims = len(spatial)
     table = _distance.class_table(what, classes, C, x.device)
     sp = M.spacing(what, spacing, dims)
     D = spatial[0] if dims == 3 else 1
@@ -84,9 +58,7 @@ def _problem(what, y_pred, y_true, mode, classes, from_logits, ignore_index, spa
         elif dist_maps.dtype != torch.float32:
             raise TypeError(f"{what}: dist_maps must be float32 distances, or with unit spacing the int32 of squared=True; got {dist_maps.dtype}")
         dist_maps = dist_maps.contiguous().reshape(B, table[0], S)
-    has_ignore = ignore_index is not None
-    ignore = (has_ignore, int(ignore_index) if has_ignore and labels is not None else 0, float(ignore_index) if has_ignore and dense is not None else 0.0)
-    return x, labels, dense, prob, table, sp, geometry, ignore, dist_maps
+    return pr, table, sp, geometry, dist_maps
 
 
 # ---------------------------------------------------------------------------------------------------------------- device
@@ -198,8 +170,8 @@ def _loss(kind, y_pred, y_true, mode, classes, from_logits, ignore_index, spacin
     alpha = float(alpha)
     if not (alpha > 0.0 and np.isfinite(alpha)):
         raise ValueError(f"{what}: alpha must be positive and finite, got {alpha}")
-    x, labels, dense, prob, table, sp, geometry, ignore, dist_maps = _problem(what, y_pred, y_true, mode, classes, from_logits, ignore_index, spacing,
-                                                                              dist_maps)
+    pr, table, sp, geometry, dist_maps = _problem(what, y_pred, y_true, mode, classes, from_logits, ignore_index, spacing, dist_maps)
+    x, labels, dense, prob, ignore = pr.x, pr.labels, pr.dense, pr.prob, pr.ignore
     per_sample = reduction == "none"
     if not x.is_cuda:
         return _host_loss(kind, x, labels, dense, prob, table, sp, geometry, ignore, dist_maps, alpha, per_sample)
@@ -225,19 +197,15 @@ class _DistanceLoss(_Loss):
     def __init__(self, mode: str, classes: Optional[List[int]] = None, from_logits: bool = True, ignore_index: Optional[int] = None, spacing=None,
                  reduction: str = "mean", alpha: float = 2.0):
         what = type(self).__name__
-        if mode not in (BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE):
-            raise ValueError(f"{what}: mode must be 'binary', 'multiclass' or 'multilabel', got {mode!r}")
-        if classes is not None and mode == BINARY_MODE:
-            raise ValueError(f"{what}: masking classes is not supported with mode='binary'")
+        P.check_mode(what, mode)
+        classes = P.check_classes(what, mode, classes)
         if reduction not in ("mean", "none"):
             raise ValueError(f"{what}: reduction must be 'mean' or 'none', got {reduction!r}")
         if not (float(alpha) > 0.0 and np.isfinite(float(alpha))):
             raise ValueError(f"{what}: alpha must be positive and finite, got {alpha}")
         super().__init__()
         self.mode = mode
-        self.classes = None if classes is None else [int(c) for c in classes]
-        if self.classes is not None and (not self.classes or len(set(self.classes)) != len(self.classes) or min(self.classes) < 0):
-            raise ValueError(f"{what}: classes must be distinct non-negative ints, got {classes!r}")
+        self.classes = classes
         self.from_logits = bool(from_logits)
         self.ignore_index = ignore_index
         self.spacing = None if spacing is None else tuple(float(v) for v in spacing)

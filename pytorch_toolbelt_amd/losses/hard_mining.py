@@ -40,8 +40,8 @@ from torch.nn.modules.loss import _Loss
 
 from .. import _native as N
 from . import _kernels as K
-from ._region import BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE
-from .distance_losses import _problem
+from . import _problem as P
+from ._region import MULTICLASS_MODE
 
 __all__ = ["TopKCrossEntropyLoss", "OhemCrossEntropyLoss", "topk_cross_entropy", "ohem_cross_entropy"]
 
@@ -175,7 +175,8 @@ def _host_loss(x, labels, dense, rule, k, t0, min_kept, ignore, per_sample):
 def _loss(rule, y_pred, y_true, mode, k, thresh, min_kept, ignore_index, per_sample, reduction, return_threshold):
     what = _NAMES[rule]
     rule, k, t0, min_kept = _rule(what, rule, k, thresh, min_kept, per_sample, reduction)
-    x, labels, dense, _, _, _, _, ignore, _ = _problem(what, y_pred, y_true, mode, None, True, ignore_index, None, None)
+    pr = P.problem(what, y_pred, y_true, mode, True, ignore_index)
+    x, labels, dense, ignore = pr.x, pr.labels, pr.dense, pr.ignore
     per_sample = bool(per_sample)
     if x.is_cuda:
         loss, thr, kept = HardMinedCrossEntropy.apply(x, labels, dense, (what, rule, k, t0, min_kept, ignore, per_sample))
@@ -204,8 +205,7 @@ class _HardMinedLoss(_Loss):
 
     def __init__(self, mode, k, thresh, min_kept, ignore_index, per_sample, reduction):
         what = type(self).__name__
-        if mode not in (BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE):
-            raise ValueError(f"{what}: mode must be 'binary', 'multiclass' or 'multilabel', got {mode!r}")
+        P.check_mode(what, mode)
         _rule(what, self._rule, k, thresh, min_kept, per_sample, reduction)
         super().__init__()
         self.mode = mode
